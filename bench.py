@@ -1,12 +1,21 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: Mpixels/s of encode+decode (qarv_base, batch of 8 synthetic 512x768 images per
-GPU) with the speedtest-lvae.py protocol (/root/reference/scripts/speedtest-lvae.py:13-44): image tensors already
-resident in HBM, `compress` then `decompress`, device sync after each phase, host rANS coding INSIDE the timed region.
+GPU) with the protocol of the reference's scripts/speedtest-lvae.py:13-44: image tensors already resident in HBM,
+`compress` then `decompress`, device sync after each phase, host rANS coding INSIDE the timed region.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                             (+ every side measurement listed below)
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/<name>.npy)
 
 A "step" = one pass of the hot path over one batch: compress_batch(8 images) + decompress_batch(8 strings).
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: metric, value, unit, higher_is_better,
+dtype, ms_per_step (wall time of one timed step), enc / dec ms per step, step_spread, bpp / psnr of the batch and
+roofline_e2e (algorithmic FLOPs from the plans the timed steps ran: no extra run).
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's batch): reconstruction.npy (float32,
+B x 3 x H x W: decompress_batch's tensor), bitstreams.npy (float32: the byte values of compress_batch's B strings, concatenated)
+and bitstream_lengths.npy (float64: bytes per string); 64 MiB at most in all, beyond that a fixed, seeded sample of an array's
+elements.  Weights and images are seeded: the same arguments give the same inputs in every run.
+--full adds these objects to the line, each from extra steps after the timed region (the headline is not changed by them):
   roofline      -- the dominant kernel family (the PLAIN channel-mixing GEMMs: MLP fc1/fc2 + 1x1 convs, 87% of the path's FLOPs):
                    algorithmic FLOPs of those launches / their HIP-event-measured durations (extra steps after the timed region on the timed
                    region's own plans, the pipeline groups replayed one after the other).  Default arithmetic f16x2: against 2500/3 = 833.3 TFLOP/s (three fp16 MFMAs per fp32-accurate
@@ -45,6 +54,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 PROFILE = os.environ.get('LVAE_BENCH_PROFILE', 'typical')   # seeded-weight profile (lossy-vae_amd/seeded_init.py)
+DUMP_LIMIT = 64 * 2 ** 20           # --dump-outputs: bytes of all arrays together
 PEAK_BF16_MFMA_TFLOPS = 2500.0
 PEAK_FP32_MFMA_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md "Peak FP32 (matrix)"
 
@@ -442,6 +452,25 @@ def noise_batch(B, H, W, rank):
     return torch.from_numpy(np.stack(ims)).permute(0, 3, 1, 2).float().div(255).contiguous()
 
 
+def _fit(a, limit, seed):
+    """float array `a` as it is if it holds at most `limit` bytes, else a fixed seeded sample of its elements (flat, in index order)."""
+    if a.nbytes <= limit:
+        return a
+    k = max(1, limit // a.itemsize)
+    pick = np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))
+    return a.reshape(-1)[pick]
+
+
+def dump_outputs(out_dir, strings, xhat):
+    """What one step returned to its caller: the B compressed strings and the (B,3,H,W) reconstruction, as float .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    lengths = np.array([len(t) for t in strings], dtype=np.float64)
+    streams = _fit(np.frombuffer(b''.join(bytes(t) for t in strings), dtype=np.uint8).astype(np.float32), DUMP_LIMIT // 4, seed=1)
+    rec = _fit(xhat.detach().float().cpu().numpy(), DUMP_LIMIT - lengths.nbytes - streams.nbytes, seed=2)
+    for name, a in (('bitstream_lengths', lengths), ('bitstreams', streams), ('reconstruction', rec)):
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -450,6 +479,11 @@ def main():
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--height', type=int, default=512)
     ap.add_argument('--width', type=int, default=768)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, every side measurement as well (roofline pass, other precisions, sizes and models, coder '
+                         'workloads, host coder rate, cpu_baseline); the --no-* / --*-steps options below shape them.  Off: the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (rank 0's batch) as DIR/<name>.npy, float32 / float64, 64 MiB at most")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--roofline-steps', type=int, default=3)
@@ -478,6 +512,8 @@ def main():
                     help='extra steps per coder-workload row after the timed region -> coder_workloads: typical / calibrated (latents drawn from the '
                          "model's own prior) / worst_case (wide-profile weights on uniform-noise images) x (batch of 8, single image, config 5) (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -565,6 +601,8 @@ def main():
         t = torch.tensor([dt, t_enc], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, t_enc = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, strings, out)
 
     # rate / distortion stats of this rank's batch, collated over ranks with one all_gather
     bpp = float(np.mean([len(s) * 8 / (H * W) for s in strings]))
@@ -590,8 +628,9 @@ def main():
         'note': 'algorithmic 2*M*N*K of EVERY GEMM launch of one step (the fused MLP launches counted as their two GEMMs) / wall time of the '
                 'step (host rANS, depthwise and pointwise kernels included in the time, not in the FLOPs)'}
 
+    # ---------------------------------------------------------------- --full only: side measurements after the timed region
     roof = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # Roofline pass: the timed region above runs the product configuration -- the pipeline groups' plans on their own HIP streams,
         # launched concurrently from their threads, so an event pair around one launch would also time the other group's kernels.
         # The SAME plans (same kernels, same launch mix: nothing is rebuilt and pipeline_groups is not touched) are therefore replayed
@@ -635,7 +674,7 @@ def main():
         attach_traffic(roof, args.precision, B, H, W)
 
     fp32_mode = None
-    if world == 1 and args.fp32_steps > 0 and args.precision in ('f16x2', 'bf16x3'):
+    if args.full and world == 1 and args.fp32_steps > 0 and args.precision in ('f16x2', 'bf16x3'):
         # the same workload with the exact fp32 MFMA arithmetic (v_mfma_f32_32x32x2_f32), product configuration (two groups)
         model.pipeline_groups = int(os.environ.get('LVAE_GROUPS', '2'))
         model.set_gemm_precision('fp32')
@@ -651,7 +690,7 @@ def main():
     # ... and with the EXACT-operand split arithmetic (3-term bf16, 6 MFMAs per product step: round-1/2 default): what the headline's
     # cheaper 2-term fp16 split bought, visible to the driver
     bf16x3_mode = None
-    if world == 1 and args.fp32_steps > 0 and args.precision == 'f16x2':
+    if args.full and world == 1 and args.fp32_steps > 0 and args.precision == 'f16x2':
         model.pipeline_groups = int(os.environ.get('LVAE_GROUPS', '2'))
         model.set_gemm_precision('bf16x3')
         step(); step()
@@ -666,7 +705,7 @@ def main():
     # The reference's own protocol (scripts/speedtest-lvae.py:28-44; qarv/model.py:521 -- batch 1 only): ONE 512x768 image, synchronise after
     # compress and after decompress, mean over the steps; its README quotes 0.098 s + 0.061 s on an RTX 3080 Ti for this.
     b1 = None
-    if world == 1 and args.b1_steps > 0 and (H, W) == (512, 768) and B > 1:
+    if args.full and world == 1 and args.b1_steps > 0 and (H, W) == (512, 768) and B > 1:
         try:
             model.pipeline_groups = int(os.environ.get('LVAE_GROUPS', '2'))
             im1 = ims[:1]
@@ -691,7 +730,7 @@ def main():
 
     # BASELINE.json configs[2]: qres34m (12 latent blocks, fixed rate), a batch of 8 x 512x768, seeded weights, same step definition
     qres = None
-    if world == 1 and args.qres_steps > 0 and (B, H, W) == (8, 512, 768) and args.precision in ('f16x2', 'bf16x3'):
+    if args.full and world == 1 and args.qres_steps > 0 and (B, H, W) == (8, 512, 768) and args.precision in ('f16x2', 'bf16x3'):
         try:
             import lvae
             import seeded_init
@@ -731,7 +770,7 @@ def main():
     # BASELINE.json configs[4] beside the headline: the reduced-precision mode (bf16 activation storage + MX-fp8 MFMA GEMMs, operands
     # quantised by their producers) on 4 x 1216x1216 (1200x1200 padded) -- a few steps after the timed region, product configuration
     config5 = None
-    if world == 1 and args.config5_steps > 0 and args.precision in ('f16x2', 'bf16x3') and (B, H, W) == (8, 512, 768):
+    if args.full and world == 1 and args.config5_steps > 0 and args.precision in ('f16x2', 'bf16x3') and (B, H, W) == (8, 512, 768):
         try:
             model.pipeline_groups = int(os.environ.get('LVAE_GROUPS', '2'))
             model.set_gemm_precision('fp8')
@@ -804,7 +843,7 @@ def main():
     # batch of 4 and a CLIC-2022-sized image pair -- config 4 shards such images over the node's GPUs with no data-path collective, so
     # its per-GPU rate is this row's.
     other_sizes = None
-    if world == 1 and args.size_steps > 0 and args.precision in ('f16x2', 'bf16x3') and (B, H, W) == (8, 512, 768):
+    if args.full and world == 1 and args.size_steps > 0 and args.precision in ('f16x2', 'bf16x3') and (B, H, W) == (8, 512, 768):
         other_sizes = {}
         model.pipeline_groups = int(os.environ.get('LVAE_GROUPS', '2'))
         model.set_gemm_precision(args.precision)
@@ -836,7 +875,7 @@ def main():
     # 'worst_case' = the wide weight profile on uniform-noise images (every table row, escapes); each at the headline's batch, for ONE image
     # (the reference's protocol) and on config 5.
     coder_rows = None
-    if world == 1 and args.coder_steps > 0 and args.precision in ('f16x2', 'bf16x3') and (B, H, W) == (8, 512, 768):
+    if args.full and world == 1 and args.coder_steps > 0 and args.precision in ('f16x2', 'bf16x3') and (B, H, W) == (8, 512, 768):
         coder_rows = {}
         try:
             model.pipeline_groups = int(os.environ.get('LVAE_GROUPS', '2'))
@@ -869,7 +908,7 @@ def main():
         model.set_gemm_precision(args.precision)
 
     coder = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             model.pipeline_groups = 1
             strings1, _, _ = step()
@@ -905,20 +944,23 @@ def main():
                             'dec_ms': {'median': round(float(np.median([d_ for _, d_ in per_step])) * 1e3, 3), 'min': round(min(d_ for _, d_ in per_step) * 1e3, 3),
                                        'max': round(max(d_ for _, d_ in per_step) * 1e3, 3)},
                             'slowest_steps': sorted(range(len(per_step)), key=lambda i: -(per_step[i][0] + per_step[i][1]))[:3]},
-            'bpp': round(bpp, 4), 'psnr_db': round(-10 * np.log10(mse), 3),
-            'ref_3080ti_mpx_s': 2.47,
-            'roofline': roof, 'roofline_e2e': roofline_e2e, 'fp32_mfma_mode_value': fp32_mode, 'bf16x3_mode_value': bf16x3_mode,
-            'b1': b1, 'qres34m_value': None if not qres else qres.get('value'), 'qres34m': qres,
-            'config5_value': None if not config5 else config5.get('value'), 'config5': config5, 'other_sizes': other_sizes, 'coder_workloads': coder_rows, 'host_coder': coder,
+            'bpp': round(bpp, 4), 'psnr_db': round(-10 * np.log10(mse), 3), 'roofline_e2e': roofline_e2e, 'full': bool(args.full),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line.update({
+                'ref_3080ti_mpx_s': 2.47,
+                'roofline': roof, 'fp32_mfma_mode_value': fp32_mode, 'bf16x3_mode_value': bf16x3_mode,
+                'b1': b1, 'qres34m_value': None if not qres else qres.get('value'), 'qres34m': qres,
+                'config5_value': None if not config5 else config5.get('value'), 'config5': config5, 'other_sizes': other_sizes, 'coder_workloads': coder_rows, 'host_coder': coder,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             phys = args.cpu_threads or min(physical_cores(), len(os.sched_getaffinity(0)))
             # the node's cores as 8-thread oracle processes working on different images at once (a single process scales badly past
             # ~8 threads on these layer sizes: 0.2 Mpixels/s on 128 threads against 0.47 on 8); the single 8-thread figure -- what the
             # reference's README quotes a desktop CPU at -- is kept beside it
             line['cpu_baseline'] = cpu_baseline(sd, H, W, n_images=3, threads=8, procs=max(1, phys // 8))
             line['cpu_baseline_8core'] = cpu_baseline(sd, H, W, n_images=3, threads=8)
-        else:
+        elif args.full:
             line['cpu_baseline'] = None
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -425,10 +425,10 @@ def test_config4_eval_sharded_script_and_bench_two_ranks(offline_home, tmp_path)
 
 
 def test_bench_line_carries_a_measured_roofline(offline_home, tmp_path):
-    """The default single-GPU bench line (short run): the roofline object is MEASURED in that run -- launches > 0, an average launch
+    """The single-GPU bench line with --full (short run): the roofline object is MEASURED in that run -- launches > 0, an average launch
     duration, 0 < frac < 1 -- also now that the product path runs a pipeline group's loop natively (no per-launch hook: the
     roofline pass replays launch by launch), and value = pixels / time."""
-    out = _run([os.path.join(REPO, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--fp32-steps', '0',
+    out = _run([os.path.join(REPO, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--fp32-steps', '0',
                 '--config5-steps', '0', '--roofline-steps', '1', '--coder-steps', '2', '--size-steps', '1', '--qres-steps', '0'], offline_home, tmp_path)
     j = [json.loads(l) for l in out.splitlines() if l.startswith('{')][0]
     r = j['roofline']
@@ -457,6 +457,36 @@ def test_bench_line_carries_a_measured_roofline(offline_home, tmp_path):
     sp = j['step_spread']            # the timed steps one by one beside the contract's mean: min <= median <= max, the mean inside [min, max]
     for k, mean in (('enc_ms', j['enc_ms_per_step']), ('dec_ms', j['dec_ms_per_step'])):
         assert 0 < sp[k]['min'] <= sp[k]['median'] <= sp[k]['max'] and sp[k]['min'] - 0.05 <= mean <= sp[k]['max'] + 0.05, (k, sp[k], mean)
+
+
+def test_bench_plain_line_and_dumped_outputs(offline_home, tmp_path):
+    """A plain bench run (no --full): exactly the timed steps, the headline keys and none of the side measurements; --dump-outputs
+    writes the last timed step's strings and reconstruction, and a second run with the same arguments writes the same arrays."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f'dump{i}'
+        out = _run([os.path.join(REPO, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs', str(d)], offline_home, tmp_path)
+        j = [json.loads(l) for l in out.splitlines() if l.startswith('{')][0]
+        assert j['steps'] == 3 and j['full'] is False and j['higher_is_better'] is True and j['unit'] == 'Mpixels/s'
+        assert j['ms_per_step'] > 0 and abs(j['value'] - 8 * 512 * 768 / (j['ms_per_step'] * 1e3)) < 0.01 * j['value']
+        assert not {'roofline', 'b1', 'qres34m', 'config5', 'other_sizes', 'coder_workloads', 'host_coder', 'cpu_baseline'} & set(j), sorted(j)
+        dumps.append({n: np.load(str(d / f'{n}.npy')) for n in ('bitstream_lengths', 'bitstreams', 'reconstruction')})
+    a, b = dumps
+    assert a['reconstruction'].dtype == np.float32 and a['reconstruction'].shape == (8, 3, 512, 768)
+    assert a['bitstreams'].dtype == np.float32 and a['bitstream_lengths'].dtype == np.float64
+    assert a['bitstreams'].size == int(a['bitstream_lengths'].sum()) and a['bitstream_lengths'].shape == (8,)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+    # the dumped strings are the path's own: decoding them gives the dumped reconstruction
+    raw = a['bitstreams'].astype(np.uint8).tobytes()
+    ends = np.cumsum(a['bitstream_lengths'].astype(np.int64))
+    strings = [raw[e - n:e] for e, n in zip(ends, a['bitstream_lengths'].astype(np.int64))]
+    import bench
+    m, _ = bench.build_model(torch.device('cuda', 0))
+    m.set_gemm_precision('f16x2')                    # the bench's default arithmetic
+    x = m.decompress_batch(strings).cpu().numpy()
+    assert np.array_equal(x, a['reconstruction'])
 
 
 # ------------------------------------------------------------------------------------------------------------------ H2, f2

@@ -291,3 +291,23 @@ def test_published_numbers_fixture_and_gate_skips_cleanly(tmp_path):
         r = subprocess.run([sys.executable, os.path.join(repo, 'scripts', 'accept-published.py')] + args, env=env, capture_output=True,
                            text=True, timeout=300)
         assert r.returncode == 0 and r.stdout.startswith('SKIP: not available offline:'), (r.stdout, r.stderr)
+
+
+def test_bench_dump_outputs_format_and_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (no GPU needed for the writer): float32 / float64 files, the strings' bytes in order, and above the
+    size cap a fixed seeded sample -- the same elements in every run, so that two builds compare element for element."""
+    import bench
+    strings = [bytes([1, 2, 3]), bytes([255, 0])]
+    x = torch.arange(2 * 3 * 4 * 4, dtype=torch.float32).reshape(2, 3, 4, 4) / 100
+    bench.dump_outputs(str(tmp_path / 'a'), strings, x)
+    a = {n: np.load(str(tmp_path / 'a' / f'{n}.npy')) for n in ('bitstream_lengths', 'bitstreams', 'reconstruction')}
+    assert a['bitstream_lengths'].dtype == np.float64 and a['bitstream_lengths'].tolist() == [3, 2]
+    assert a['bitstreams'].dtype == np.float32 and a['bitstreams'].tolist() == [1, 2, 3, 255, 0]
+    assert a['reconstruction'].dtype == np.float32 and np.array_equal(a['reconstruction'], x.numpy())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 4 * 64)                  # above the cap: a seeded sample of the reconstruction
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), strings, x)
+    b, c = (np.load(str(tmp_path / d / 'reconstruction.npy')) for d in ('b', 'c'))
+    assert b.dtype == np.float32 and np.array_equal(b, c)
+    assert sum(os.path.getsize(str(tmp_path / 'b' / f)) - 128 for f in os.listdir(str(tmp_path / 'b'))) <= 4 * 64
+    assert np.all(np.diff(b) > 0) and set(b.tolist()) <= set(x.numpy().reshape(-1).tolist())

@@ -17,11 +17,12 @@ import seeded_init
 from oracle import qarv_oracle
 from oracle import compressai_semantics as cs
 
-# The goldens were generated in the build container (where /root/reference exists) from the imported reference; the oracle issues the same
-# PyTorch CPU ops, so THERE it must reproduce them exactly -- 0 flips, byte-identical containers.  On another host
-# (other CPU, other SIMD width => other summation order) a round() of a value within 1e-6 of .5 may fall the other way: small budget.
-EXACT = os.path.isdir('/root/reference') or os.environ.get('LVAE_ORACLE_EXACT') == '1'
-FLIP_BUDGET = 0.0 if EXACT else 2e-3
+# The goldens were generated from the imported reference; the oracle issues the same PyTorch CPU ops, so on a host that computes the
+# goldens' float bits (the `oracle_exact` fixture) it must reproduce them exactly -- 0 flips, byte-identical containers (VERDICT r02
+# item 1d).  On another host (other CPU, other SIMD width or thread count => other summation order) a round() of a value within 1e-6 of
+# .5 may fall the other way: small budget.
+def flip_budget(exact):
+    return 0.0 if exact else 2e-3
 
 
 @pytest.fixture(scope='module')
@@ -82,9 +83,10 @@ def test_cnx_block(golden_dir):
 
 
 @pytest.mark.parametrize('tag,seed', [('64x64', 0), ('128x192', 1), ('512x768', 7)])      # 512x768: the size the metric is quoted on
-def test_full_model(golden_dir, oracle_model, tag, seed):
+def test_full_model(golden_dir, oracle_model, oracle_exact, tag, seed):
+    EXACT = oracle_exact
     if tag == '512x768' and not EXACT:
-        pytest.skip('free-running full-size comparison: exact on the host that generated the golden; elsewhere one rounding flip cascades '
+        pytest.skip('free-running full-size comparison: exact only where the oracle computes the goldens\' float bits; elsewhere one rounding flip cascades '
                     '(the -m gpu tests hold the HIP path to this golden teacher-forced)')
     g = np.load(os.path.join(golden_dir, f'qarv_base_{tag}.npz'))
     h, w = g['hw'].tolist()
@@ -107,7 +109,7 @@ def test_full_model(golden_dir, oracle_model, tag, seed):
             nsym += sym.size
             flips += int((sym != g[f'{key}.b{bi}.symbols']).sum())
             iflips += int((idx != g[f'{key}.b{bi}.indexes']).sum())
-        assert flips <= FLIP_BUDGET * nsym and iflips <= FLIP_BUDGET * nsym, (flips, iflips, nsym)
+        assert flips <= flip_budget(EXACT) * nsym and iflips <= flip_budget(EXACT) * nsym, (flips, iflips, nsym)
         string = oracle_model.compress(im, lmb)
         if flips == 0 and iflips == 0:
             assert string == g[f'{key}.bitstream'].tobytes()

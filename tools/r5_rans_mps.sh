@@ -5,7 +5,7 @@ O=$R/gpurun_out/r5_rans_mps
 mkdir -p $O
 cd $R
 OLD=_bin/rans_before_mps/liblvae_hip.so
-BX="--no-cpu-baseline --no-kernel-timing --fp32-steps 0 --config5-steps 0 --qres-steps 0"
+BX="--full --no-cpu-baseline --no-kernel-timing --fp32-steps 0 --config5-steps 0 --qres-steps 0"
 pick='import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); b=j.get("b1") or {}; print(sys.argv[1], "B=8: %.1f Mpixels/s = %.3f ms = enc %.3f + dec %.3f" % (j["value"], j["ms_per_step"], j["enc_ms_per_step"], j["dec_ms_per_step"]), "| B=1: enc %.3f + dec %.3f ms" % (b.get("enc_ms", 0), b.get("dec_ms", 0)))'
 for i in 1 2 3; do
   python tools/bench_with_lib.py $OLD $BX 2>/dev/null | python -c "$pick" before >> $O/ab.txt

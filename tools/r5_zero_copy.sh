@@ -9,7 +9,7 @@ for Z in none dec both; do
   echo "== LVAE_ZERO_COPY=$Z" | tee -a $O/dec_timeline.txt
   LVAE_ZERO_COPY=$Z python tools/dec_timeline.py 8 20 2>&1 | grep -v "amdgpu\|lvae:" | tee -a $O/dec_timeline.txt
 done
-ARGS="--no-cpu-baseline --no-kernel-timing --fp32-steps 0 --qres-steps 0 --config5-steps 0 --steps 30"
+ARGS="--full --no-cpu-baseline --no-kernel-timing --fp32-steps 0 --qres-steps 0 --config5-steps 0 --steps 30"
 P='import sys,json; j=json.loads(sys.stdin.read()); print(sys.argv[1], j["value"], j["ms_per_step"], j["enc_ms_per_step"], j["dec_ms_per_step"], j["b1"])'
 for i in 1 2; do for Z in none dec both; do
   LVAE_ZERO_COPY=$Z python bench.py $ARGS 2>/dev/null | python -c "$P" $Z | tee -a $O/bench.txt

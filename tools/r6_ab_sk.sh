@@ -1,6 +1,6 @@
 # Round 6: the fused small-map MLP (csrc/mlp_sk.hip) on / off in the bench (same box, alternating): B=8 headline, B=1, calibrated rows
 R=$GRAFT_REPO_ROOT
-BX="--no-cpu-baseline --fp32-steps 0 --config5-steps 0 --qres-steps 0 --size-steps 0 --no-kernel-timing --steps 20"
+BX="--full --no-cpu-baseline --fp32-steps 0 --config5-steps 0 --qres-steps 0 --size-steps 0 --no-kernel-timing --steps 20"
 for rep in 1 2 3; do
 for v in 0 1024; do
   LVAE_MLP_SK_MAX_ROWS=$v python $R/bench.py $BX 2>/dev/null | python -c "
