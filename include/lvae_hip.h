@@ -161,7 +161,7 @@ typedef struct {
                                              k16-interleaved order [N][K/16][3][16] (lvae.models.base.pack_bf16x3) */
     int  cfg;                             /* tile configuration: 0 = library heuristic, k>0 = candidate k-1 of
                                              lvae_gemm_num_configs() (results are bit-identical for every choice;
-                                             the Python host autotunes this per shape at plan-build time) */
+                                             the Python host passes 0; tests force the others) */
     int  ksplit;                          /* split-K: S > 1 cuts K into S equal slices (K % (32*S) == 0) computed by S x tiles
                                              workgroups into `ws`, then reduced IN SLICE ORDER and passed through the epilogue by a
                                              second kernel -- deterministic; for the few-tile, long-K layers (stride 32/64 MLPs, 3x3

@@ -32,18 +32,11 @@
 // encoder and the decoder see the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <type_traits>
 #include <utility>
 
 #include "../../include/lvae_hip.h"
-
-// Timing studies (WRONG RESULTS by construction; tools/build_exp.sh builds only): LVAE_EXP_DW_NODMA re-reads the tile's first two rows
-// instead of fetching new ones (what is left without the row traffic), LVAE_EXP_DW_NOLN skips the LayerNorm phases and stores.
-#if !defined(LVAE_EXPERIMENTAL_BUILD) && (defined(LVAE_EXP_DW_NODMA) || defined(LVAE_EXP_DW_NOLN) || defined(LVAE_EXP_DW_NOREAD) || defined(LVAE_EXP_DW_LN_AT) || defined(LVAE_EXP_DW_PKHI))
-#error "LVAE_EXP_DW_* experiment hooks need -DLVAE_EXPERIMENTAL_BUILD (tools/build_exp.sh); never in liblvae_hip.so"
-#endif
 
 namespace {
 
@@ -94,7 +87,7 @@ __device__ __forceinline__ unsigned f2bf_rne(float x) {
 // same chain in scalar v_fma_f32, an MFMA-only kernel on a second stream) -> profiles/r04_ubench_pk_opsel_erratum_probe.txt:
 // 832 - 1360 wrong LOW-lane results in 1.0e11 chains with the selection on src1 beside the MFMA kernel, 0 alone; 0 with the selection on
 // src0, 0 in the high lane, 0 for the op_sel_hi-only broadcast used here.  A hardware erratum (MI355X, ROCm 7.2), not a race of this
-// kernel.  What an all-packed tap loop would buy was timed as well (-DLVAE_EXP_DW_PKHI, timing only: profiles/r04_dw_bench_all_packed_taps_ab.txt):
+// kernel.  What an all-packed tap loop would buy was timed as well (profiles/r04_dw_bench_all_packed_taps_ab.txt):
 // 90.2 -> 87.5 us on the 128x192x192 map, -3 ... -8 % on the k = 7 layers -- too little to stand next to an erratum for, even on the src0 form.
 __device__ __forceinline__ void pk_fma_wlo(f32x2& a, f32x2 x, f32x2 w) {
     asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(a) : "v"(x), "v"(w));
@@ -102,10 +95,6 @@ __device__ __forceinline__ void pk_fma_wlo(f32x2& a, f32x2 x, f32x2 w) {
 __device__ __forceinline__ void fmac_whi(f32x2& a, float x0, float x1, f32x2 w) {
     asm("v_fmac_f32 %0, %1, %2" : "+v"(a[0]) : "v"(x0), "v"(w[1]));
     asm("v_fmac_f32 %0, %1, %2" : "+v"(a[1]) : "v"(x1), "v"(w[1]));
-}
-// the all-packed form: the weight in the HIGH half of its pair, broadcast to both lanes (op_sel: the low lane selects the high dword)
-__device__ __forceinline__ void pk_fma_whi(f32x2& a, f32x2 x, f32x2 w) {
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(a) : "v"(x), "v"(w));
 }
 __device__ __forceinline__ f32x2 pair_of(float lo, float hi) {     // two plain moves (never v_pk_mov_b32 with op_sel)
     f32x2 p;
@@ -338,11 +327,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(cl_wave
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, oB), ro, (xs * C + chB) * 4, 0, 0);
         }
     };
-#ifdef LVAE_EXP_DW_LN_AT
-    constexpr int LN_AT = LVAE_EXP_DW_LN_AT < XW - 1 ? LVAE_EXP_DW_LN_AT : XW - 2;
-#else
     constexpr int LN_AT = 3;                           // pixel step of the next row at which the previous row's LayerNorm is finished
-#endif
 
     // The k x k weights (49 dword loads per lane, as many vector-memory instructions as 12 rows of DMA) are loaded once per workgroup and
     // serve tpw tiles; the launcher picks tpw so that the workgroups still fill the chip in whole rounds.
@@ -359,19 +344,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(cl_wave
     static_for<NR>([&](auto t_tag) {                                 // input row y0 - P + t feeds output rows th = t - i, 0 <= i < k
         constexpr int t = decltype(t_tag)::value;
         // row t + 2 -> the buffer row t came from (it is in registers since the end of the previous step)
-#ifndef LVAE_EXP_DW_NODMA
         if constexpr (t + 2 < NR) dma_row(y0 - P + t + 2, t % 2);
-#endif
         __builtin_amdgcn_sched_barrier(0);
         static_for<XW - 1>([&](auto s_tag) {                         // the pixel pair (s, s + 1)
             constexpr int s = decltype(s_tag)::value;
-#ifndef LVAE_EXP_DW_NOLN
             if constexpr (s == LN_AT && t - 1 >= KS - 1) {
                 lds_barrier();
                 ln_finish(y0 + t - 1 - (KS - 1), (t - 1) % 2);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#endif
             const float x0 = xp[s / 2][s % 2], x1 = xp[(s + 1) / 2][(s + 1) % 2];
             f32x2 xv;
             if constexpr (s % 2 == 0) xv = xp[s / 2];
@@ -387,11 +368,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(cl_wave
                         const int tap = i * KS + j;
                         if (!PACKW) pk_fma_wlo(acc[th][q / 2], xv, wp[tap]);
                         else if (tap % 2 == 0) pk_fma_wlo(acc[th][q / 2], xv, wp[tap / 2]);
-#ifdef LVAE_EXP_DW_PKHI
-                        else pk_fma_whi(acc[th][q / 2], xv, wp[tap / 2]);
-#else
                         else fmac_whi(acc[th][q / 2], x0, x1, wp[tap / 2]);
-#endif
                     }
                 }
             }
@@ -406,37 +383,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(cl_wave
             //  Round 5: warming L2 with one dword per 128-B line of the tile's rows 2 .. NR - 1 at the tile's start -- LDS-DMA touches older than the
             //  row DMAs, so that those hit L2 -- was measured SLOWER on every shape, 88 -> 95 us at k = 7 / C = 192, 61 -> 82 at C = 384:
             //  profiles/r05_dw_l2_touch_not_taken.txt.  The first wait of a tile then waits for all of them.)
-#ifdef LVAE_EXP_DW_NODMA
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(t + 2 < NR ? NG : 0) : "memory");
-#endif
-#ifndef LVAE_EXP_DW_NOREAD
             read_row(std::integral_constant<int, (t + 1) % 2>{});
-#endif
         }
-#ifndef LVAE_EXP_DW_NOLN
         if constexpr (t >= KS - 1) ln_local(acc[t - (KS - 1)], t % 2);
-#else
-        if constexpr (t >= KS - 1) { float sacc = 0.f; for (int q = 0; q < SW / 2; ++q) sacc += acc[t - (KS - 1)][q][0] + acc[t - (KS - 1)][q][1]; if (sacc == 1.2345e30f) ((float*)y)[0] = sacc; }
-#endif
     });
-#ifndef LVAE_EXP_DW_NOLN
     lds_barrier();
     ln_finish(y0 + TH - 1, (NR - 1) % 2);
     lds_barrier();                                     // the statistics buffers are free for the next tile
-#endif
     }
 }
-
-}  // namespace
-// tuning hook LVAE_DW_CL (experimental builds only): 0 = never (earlier forms), 10 * tpw + TH (TH = 1 / 4 / 8) = force, -1 = heuristic
-#if defined(LVAE_CL_BF16_TU) || defined(LVAE_CL_H2_TU) || defined(LVAE_CL_Q8_TU)
-extern int g_dw_cl;
-#else
-int g_dw_cl = -1;
-#endif
-namespace {
 
 template <int KS, int NW, int TH, bool BF, int OF>
 int launch_cl_th(const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y, int B, int H, int W,
@@ -474,8 +430,7 @@ int launch_cl(const void* x, const float* wt, const float* bias, const float* aw
             if (tpw >= n_ty) break;
         }
     }
-    int TH = best_th, tpw = best_tpw;
-    if (g_dw_cl > 0 && (KS > 1 || g_dw_cl % 10 == 1)) { TH = g_dw_cl % 10; tpw = g_dw_cl / 10 > 0 ? g_dw_cl / 10 : 1; }   // hook: 10 * tpw + TH
+    const int TH = best_th, tpw = best_tpw;
     if constexpr (KS > 1) {
         if (TH == 8) return launch_cl_th<KS, NW, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, st);
         if (TH >= 2) return launch_cl_th<KS, NW, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, st);
@@ -549,11 +504,6 @@ int lvae_dwln_cl_launch_q8(int C, int k, const void* x, const float* wt, const f
 int lvae_dwln_cl_try(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b, const float* shift,
                      const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, hipStream_t st, int* rc) {
     const int bf16 = fmt == 1 || fmt == 3;                              // fmt: 0 fp32 maps, 1 bf16 maps, 2 fp32 in / f16x2 planes out, 3 bf16 in / MX-fp8 out
-#ifdef LVAE_EXPERIMENTAL_BUILD      // tools/build_exp.sh copies only: the kernel family is part of the bitstream contract (its LayerNorm
-    static bool env_read = false;   // association differs from the sliding-window kernel's), so the product library has no switch
-    if (!env_read) { const char* e = getenv("LVAE_DW_CL"); if (e) g_dw_cl = atoi(e); env_read = true; }
-    if (g_dw_cl == 0) return 0;
-#endif
     if (ln_w && shift) return 0;
     if (!(C == 128 || C == 192 || C == 256 || C == 384 || C == 512) || !(k == 1 || k == 3 || k == 5 || k == 7)) return 0;
     // one image's map must fit a buffer descriptor (2 GiB, > 44 Mpixels at stride 4): an argument error, NOT a silent switch to the

@@ -9,16 +9,6 @@
 #include "../../include/lvae_hip.h"
 #include "device_math.h"
 
-// Experiment hooks of the round-1/2 kernel studies (docs/MEASUREMENT_HISTORY.md 5, 5b).  LVAE_EXP_NOSPLIT / LVAE_EXP_NOSTORE / LVAE_GEMM_NOLOAD give WRONG
-// RESULTS by construction (they remove work to time what is left); the others change scheduling only.  None of them can be switched on
-// in the product build: they compile only together with -DLVAE_EXPERIMENTAL_BUILD, which tools/build_exp.sh passes for its
-// side-by-side copies under _bin/ and lossy-vae_amd/build_native.py never does.
-#if !defined(LVAE_EXPERIMENTAL_BUILD) && (defined(LVAE_EXP_NOSPLIT) || defined(LVAE_EXP_NOSTORE) || defined(LVAE_EXP_PRIO) || defined(LVAE_EXP_H2_FULLLINE) || \
-    defined(LVAE_EXP_NO_RES_PREFETCH) || defined(LVAE_EPI_PRIO) || defined(LVAE_GEMM_NOLOAD) || defined(LVAE_GEMM_TRACE) || defined(LVAE_X3V2_TRACE) || \
-    defined(LVAE_EXP_PP_NOWAIT) || defined(LVAE_EXP_PP_NODMA) || defined(LVAE_EXP_PP_NODSR) || defined(LVAE_EXP_PP_NOBAR) || defined(LVAE_EXP_H2PP))
-#error "LVAE_EXP_* / *_TRACE / *_NOLOAD experiment hooks need -DLVAE_EXPERIMENTAL_BUILD (tools/build_exp.sh); never in liblvae_hip.so"
-#endif
-
 namespace {
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute: a process that drives several GPUs (or a second device later on)
@@ -62,22 +52,15 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
 
 
-// 4x4 transpose across the 4 lanes of a quad with DPP quad_perm moves (lane^1: [1,0,3,2] = 0xB1, lane^2: [2,3,0,1] =
-// 0x4E): afterwards lane j holds in (v0..v3) what lanes 0..3 of its quad held in register j.  Used to turn the MFMA
-// accumulator layout (4 consecutive ROWS per lane) into 4 consecutive COLUMNS per lane => 16-B stores / residual loads.
-__device__ __forceinline__ float dpp_xor1(float x) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_xor2(float x) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x4E, 0xF, 0xF, true));
-}
+// 4x4 transpose across the 4 lanes of a quad with DPP quad_perm moves (lane^1: [1,0,3,2], lane^2: [2,3,0,1]): afterwards
+// lane j holds in (v0..v3) what lanes 0..3 of its quad held in register j.  Used to turn the MFMA accumulator layout
+// (4 consecutive ROWS per lane) into 4 consecutive COLUMNS per lane => 16-B stores / residual loads.
 // Every call site passes j = lane & 3 (the lane's place in its quad), so the two select masks are the constants 0xAAAA... (odd lanes)
 // and 0xCCCC... (upper lane pair).  Form: each exchange step is ONE v_cndmask_b32_dpp per register -- dst = vcc ? own : dpp(partner's
 // register) -- instead of select + v_mov_dpp + two selects (with two wait states in front of every DPP read of a fresh select): 8 VALU
 // + 4 s_mov per 4 x 4 transpose instead of 16 VALU + 8 idle slots, in epilogues whose time is their VALU issue.  VOP2-DPP reads its
 // mask from VCC only, hence the s_mov pairs; the leading s_nop covers "VALU wrote the source, DPP reads it" (two wait states counting the
 // s_mov) for sources produced right in front of the call; inside, every DPP source is at least three instructions old.
-#ifndef LVAE_QUAD_TRANSPOSE_SELECT_FORM
 __device__ __forceinline__ void quad_transpose(float& v0, float& v1, float& v2, float& v3, int /* j == lane & 3 */) {
     float n0, n1, n2, n3, o0, o1, o2, o3;
     asm("s_mov_b64 vcc, %[m1]\n\t"
@@ -99,16 +82,6 @@ __device__ __forceinline__ void quad_transpose(float& v0, float& v1, float& v2, 
         : "vcc");
     v0 = o0; v1 = o1; v2 = o2; v3 = o3;
 }
-#else
-__device__ __forceinline__ void quad_transpose(float& v0, float& v1, float& v2, float& v3, int j) {
-    const bool o1 = (j & 1) != 0, o2 = (j & 2) != 0;
-    float t;
-    t = dpp_xor1(o1 ? v0 : v1); if (o1) v0 = t; else v1 = t;
-    t = dpp_xor1(o1 ? v2 : v3); if (o1) v2 = t; else v3 = t;
-    t = dpp_xor2(o2 ? v0 : v2); if (o2) v0 = t; else v2 = t;
-    t = dpp_xor2(o2 ? v1 : v3); if (o2) v1 = t; else v3 = t;
-}
-#endif
 
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -141,11 +114,7 @@ struct Cfg {
     static constexpr int RP = NT / CPR;           // tile rows staged per pass (CPR lanes x 16 B = one row segment)
     static constexpr int NA = (BM + RP - 1) / RP; // float4 loads per thread per k-tile (A)
     static constexpr int NB = (BN + RP - 1) / RP; // (W)
-#ifdef LVAE_GEMM_TRACE
-    static constexpr int LDS_BYTES = NBUF * (BM + BN) * LDT * 4 + 1024;
-#else
     static constexpr int LDS_BYTES = NBUF * (BM + BN) * LDT * 4;
-#endif
     static_assert(WGM * WGN == 4 || WGM * WGN == 8, "4 or 8 waves");
     static_assert(BM % RP == 0, "A tile must be a whole number of staging passes");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
@@ -159,9 +128,6 @@ __device__ __forceinline__ void gemm_epilogue(const lvae_gemm_desc& d, f32x16 (&
                                               int wave_n, int li, int lh) {
     // C/D layout of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
     // acc[][] is only ever indexed statically (a runtime index sends the whole accumulator tile to scratch).
-#ifdef LVAE_EPI_PRIO
-    __builtin_amdgcn_s_setprio(LVAE_EPI_PRIO);      // experiment: favour the epilogue's VALU/VMEM issue over a co-resident MFMA wave
-#endif
     const int rr = d.r, r2 = rr * rr;
     const int epi = d.epi, store = d.store;
     const int cp = (store == LVAE_ST_ROWMAJOR) ? 1 : d.N / r2;
@@ -191,11 +157,7 @@ __device__ __forceinline__ void gemm_epilogue(const lvae_gemm_desc& d, f32x16 (&
             }
         }
         const bool has_res = epi == LVAE_EPI_GAMMA_RES || epi == LVAE_EPI_RES;
-#ifdef LVAE_EXP_NO_RES_PREFETCH
-        const bool res_pf = false;
-#else
         const bool res_pf = has_res && store == LVAE_ST_ROWMAJOR;
-#endif
 #pragma unroll
         for (int a = 0; a < C::TM; ++a) {
             // The residual values of this 32-row block are requested up front, all 4 * TN of them back to back (rows and columns are
@@ -316,9 +278,6 @@ __device__ __forceinline__ void gemm_epilogue(const lvae_gemm_desc& d, f32x16 (&
     if (store == LVAE_ST_IMAGE && d.status && bad) atomicOr(d.status, LVAE_STATUS_NONFINITE_IMAGE);
 }
 
-#ifndef H2P_FULL_LINE
-#define H2P_FULL_LINE true
-#endif
 // Straight-line epilogue for the launches gemm_h2p_kernel exists for (fc1: + bias -> GELU -> pre-split store; fc2: + bias, * gamma,
 // + residual -> fp32 store; both row-major on a full-width tile).  gemm_epilogue decides epi / store / out_h2 / residual at RUN time
 // inside its unit loop: every 4-element unit is a chain of uniform branches, its store sits behind an exec-mask branch, and the

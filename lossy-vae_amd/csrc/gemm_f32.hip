@@ -26,18 +26,9 @@
 //    encoder and decoder (different M) derive bit-identical priors.  No split-K, no atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/lvae_hip.h"
 #include "device_math.h"
-
-#ifdef LVAE_GEMM_TRACE
-extern "C" __device__ long* lvae_trace_buf;          // [16 k-tiles][8 stamps], filled by one wave of one block
-// stamps go to LDS (beyond the tiles) so that they do not sit on the vmcnt queue the loader waits on; dumped at the end
-#define TRACE_STAMP(slot) do { if (tracing && kt < 16) ((long*)(smem + C::NBUF * (C::BM + C::BN) * C::LDT))[kt * 8 + (slot)] = clock64(); } while (0)
-#else
-#define TRACE_STAMP(slot) do {} while (0)
-#endif
 
 #include "gemm_common.h"
 
@@ -105,9 +96,6 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(const lvae_gemm_desc d, 
     constexpr int BK = C::BK, LDT = C::LDT;
     float* Ws = smem + C::NBUF * C::BM * LDT;  // [NBUF][BN][LDT]
 
-#ifdef LVAE_GEMM_TRACE
-    const long t_entry = clock64();
-#endif
     // XCD-aware bijective remap (block b runs on XCD b%8): each XCD gets a contiguous chunk of the tile list
     int t;
     {
@@ -187,22 +175,14 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(const lvae_gemm_desc d, 
     lstore(0);
     __syncthreads();
 
-#ifdef LVAE_GEMM_TRACE
-    const bool tracing = (blockIdx.x == gridDim.x / 2 + 3) && tid == 0;
-    const long t_prologue = clock64();
-#endif
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = (C::NBUF == 2) ? (kt & 1) : 0;
-        TRACE_STAMP(0);
         const bool more = kt + 1 < nk;
         // small wave tiles (<= 2 MFMA blocks, 1-2k cycles of MFMA per k-tile) are latency-bound: issue their loads first
         constexpr bool kSpreadLoads = C::TM * C::TN >= 4;
         // all slices go out in the FIRST half of the substeps so that the remaining MFMAs still cover their latency
         constexpr int kLoadSlices = (BK / 8 >= 4) ? BK / 16 : 1;
-#ifndef LVAE_GEMM_NOLOAD
         if (!kSpreadLoads && more) gload(kt + 1, 0, 1);
-#endif
-        TRACE_STAMP(1);
         const float* a_base = As + cur * C::BM * LDT + (wave_m * C::TM * 32 + li) * LDT + 4 * lh;
         const float* b_base = Ws + cur * C::BN * LDT + (wave_n * C::TN * 32 + li) * LDT + 4 * lh;
 #pragma unroll
@@ -219,38 +199,23 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(const lvae_gemm_desc d, 
 #pragma unroll
                     for (int b = 0; b < C::TN; ++b)
                         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a][j], bf[b][j], acc[a][b], 0, 0, 0);
-#ifndef LVAE_GEMM_NOLOAD
             if (kSpreadLoads) {
                 __builtin_amdgcn_sched_barrier(0);      // keep this slice of loads BEHIND the substep's MFMAs
                 if (more && s < kLoadSlices) gload(kt + 1, s, kLoadSlices);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#endif
         }
-        TRACE_STAMP(2);
         if (C::NBUF == 2) {
             if (kt + 1 < nk) lstore(cur ^ 1);
-            TRACE_STAMP(3);
             __syncthreads();
         } else if (kt + 1 < nk) {
             __syncthreads();                    // every wave has finished reading the (only) stage
             lstore(0);
-            TRACE_STAMP(3);
             __syncthreads();
         }
-        TRACE_STAMP(4);
     }
 
-#ifdef LVAE_GEMM_TRACE
-    const long t_loop = clock64();
-    if (tracing) for (int i = 0; i < 120; ++i) lvae_trace_buf[i] = ((long*)(smem + C::NBUF * (C::BM + C::BN) * C::LDT))[i];
-#define TRACE_END() do { if (tracing) { __builtin_amdgcn_s_waitcnt(0); lvae_trace_buf[120] = t_entry; lvae_trace_buf[121] = t_prologue; \
-                                         lvae_trace_buf[122] = t_loop; lvae_trace_buf[123] = clock64(); } } while (0)
-#else
-#define TRACE_END() do {} while (0)
-#endif
     gemm_finish<C>(d, acc, m0, n0, wave_m, wave_n, li, lh, (void*)smem, t);
-    TRACE_END();
 }
 
 // ---------------------------------------------------------------- reduced-precision variant (BASELINE config 5)
@@ -580,14 +545,6 @@ typedef Cfg<2, 2, 1, 1, 2, 64> CfgS64;   // 64 x 64, BK 64
 typedef Cfg<2, 2, 2, 1, 2, 64> CfgB64;   // 128 x 64, BK 64
 
 constexpr int kCUs = 256;
-}  // namespace
-// tuning hook (LVAE_GEMM_CFG env var): force a tile configuration id for N > 64; one object for the three translation units below
-#ifdef LVAE_GEMM_TU_AMODE
-extern int g_force_cfg;
-#else
-int g_force_cfg = -1;
-#endif
-namespace {
 
 // Estimated cost (arbitrary units ~ MFMA cycles on the critical CU) of running the problem with a BMxBN tile:
 // rounds of tiles over the CUs (workgroup slots) x per-tile work, plus a per-tile fixed cost (prologue + epilogue).
@@ -602,7 +559,7 @@ inline double tile_cost(int M, int N, int K, int BM, int BN, int wg_per_cu, doub
 template <int AMODE>
 int launch_mode(const lvae_gemm_desc* d, hipStream_t st) {
     const int N = d->N, M = d->M * ksp(d), K = d->K / ksp(d);      // split-K: S x the tiles, 1/S the depth
-    if (d->cfg <= 0 && g_force_cfg < 0) {
+    if (d->cfg <= 0) {
         if (N <= 32 || N == 96) return launch_cfg<CfgC, AMODE>(d, st);
         if (N <= 64) return launch_cfg<CfgB, AMODE>(d, st);
     }
@@ -622,7 +579,6 @@ int launch_mode(const lvae_gemm_desc* d, hipStream_t st) {
     consider(6, 256, 128, 1, 0.85);
     consider(8, 128, 192, 2, 0.92);     // measured: never slower than 256x192, 20% faster at (N=384, K=768)
     consider(7, 128, 256, 2, 0.84);
-    if (g_force_cfg >= 0) id = g_force_cfg;
     if (d->cfg > 0) id = d->cfg - 1;
     if (d->prec != 0 && id == 10) id = 2;
     if (d->prec != 0 && id == 11) id = 1;
@@ -686,20 +642,9 @@ int lvae_gemm_launch_patch2(const lvae_gemm_desc* d, hipStream_t st);           
 int lvae_gemm_launch_conv3(const lvae_gemm_desc* d, hipStream_t st);                         // gemm_f32_conv3.hip
 int lvae_gemm_lp_dispatch(const lvae_gemm_desc* d, hipStream_t st);                           // gemm_lp.hip
 int lvae_gemm_q8_dispatch(const lvae_gemm_desc* d, hipStream_t st);                           // gemm_q8.hip
-static int gemm_dispatch_impl(const lvae_gemm_desc* d, hipStream_t st, int x3v2, int x3v2_tn);
-static int gemm_dispatch(const lvae_gemm_desc* d, hipStream_t st, int x3v2, int x3v2_tn) { return gemm_dispatch_impl(d, st, x3v2, x3v2_tn); }
+static int gemm_dispatch(const lvae_gemm_desc* d, hipStream_t st);
 
 extern "C" int lvae_gemm_f32(const lvae_gemm_desc* d, void* stream) {
-    static int x3v2 = 1, x3v2_tn = 0;
-#ifdef LVAE_EXPERIMENTAL_BUILD             // tuning hooks of tools/build_exp.sh copies only (every choice gives the same bits; the product
-    static bool env_read = false;          // library's launch paths read no environment): LVAE_X3V2=0 keeps prec 2 on gemm_x3_kernel,
-    if (!env_read) {                       // LVAE_X3V2_TN forces its tile, LVAE_GEMM_CFG the legacy kernels' configuration
-        const char* e = getenv("LVAE_GEMM_CFG"); if (e) g_force_cfg = atoi(e);
-        e = getenv("LVAE_X3V2"); if (e) x3v2 = atoi(e);
-        e = getenv("LVAE_X3V2_TN"); if (e) x3v2_tn = atoi(e);
-        env_read = true;
-    }
-#endif
     if (!d || !d->A0 || (!d->Wt && !(d->prec != 0 && d->Wt16)) || !d->out || d->M <= 0 || d->N <= 0 || d->K <= 0) return -22;
     if ((d->K & 3) || (d->ldw & 3)) return -22;                       // 16-B operand loads
     if (d->prec < 0 || d->prec > 4) return -22;
@@ -723,7 +668,7 @@ extern "C" int lvae_gemm_f32(const lvae_gemm_desc* d, void* stream) {
         // pre-split operands: SERIAL split-K inside gemm_h2p_kernel (one workgroup adds the S slice sums in slice order: the parallel
         // form's bits without workspace or reduce launch)
         if (d->store != LVAE_ST_ROWMAJOR || (d->N & 3) || (d->ldo & 3) || (d->ldres & 3) || d->K % (32 * S)) return -22;
-        return gemm_dispatch(d, st, x3v2, x3v2_tn);
+        return gemm_dispatch(d, st);
     }
     if (S > 1 && d->prec == 4 && (d->cfg == 0 || d->cfg == 3)) {
         // narrow outputs over large maps: gemm_h2n_kernel walks the slices serially too (same bits, no workspace traffic, no reduction)
@@ -742,37 +687,28 @@ extern "C" int lvae_gemm_f32(const lvae_gemm_desc* d, void* stream) {
             d2.cnt = nullptr;
             return lvae_gemm_f32(&d2, stream);
         }
-        const int rc = gemm_dispatch(d, st, x3v2, x3v2_tn);
+        const int rc = gemm_dispatch(d, st);
         if (rc || d->cnt || d->defer_reduce) return rc;               // cnt: reduced in place by each tile's last-arriving slice; defer_reduce: by the consumer
         const long n = (long)d->M * (d->N >> 2);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *d, S);
         return (int)hipGetLastError();
     }
-    return gemm_dispatch(d, st, x3v2, x3v2_tn);
+    return gemm_dispatch(d, st);
 }
 
-static int gemm_dispatch_impl(const lvae_gemm_desc* d, hipStream_t st, int x3v2, int x3v2_tn) {
+static int gemm_dispatch(const lvae_gemm_desc* d, hipStream_t st) {
     if (d->prec == 4) {                  // f16x2: one kernel family; the host asks for it only where it applies (engine.h2_eligible)
-        static int h2_tn = 0, h2p_tile = 0;
-#ifdef LVAE_EXPERIMENTAL_BUILD             // tile sweeps (tools/h2p_sweep.sh) on experimental builds only
-        static bool h2_env = false;
-        if (!h2_env) {
-            const char* e = getenv("LVAE_H2_TN"); h2_tn = e ? atoi(e) : 0;
-            e = getenv("LVAE_H2P_TILE"); h2p_tile = e ? atoi(e) : 0;
-            h2_env = true;
-        }
-#endif
         int rc = 0;
         if (d->out_h2 && (d->store != LVAE_ST_ROWMAJOR || (d->epi != LVAE_EPI_BIAS && d->epi != LVAE_EPI_BIAS_GELU) || (d->N & 31) ||
                           d->ldo != d->N || (d->ksplit > 1 && !d->a_h2)))
             return -22;
-        if (d->a_h2) return lvae_gemm_h2p_try(d, st, d->cfg > 0 ? d->cfg : h2p_tile, &rc) ? rc : -22;      // cfg = 10 WM + TN: force a tile
-        return lvae_gemm_h2_try(d, st, d->cfg > 0 ? d->cfg : h2_tn, &rc) ? rc : -22;                          // cfg: gemm_h2.hip's force codes
+        if (d->a_h2) return lvae_gemm_h2p_try(d, st, d->cfg > 0 ? d->cfg : 0, &rc) ? rc : -22;     // cfg = 10 WM + TN: force a tile
+        return lvae_gemm_h2_try(d, st, d->cfg > 0 ? d->cfg : 0, &rc) ? rc : -22;                   // cfg: gemm_h2.hip's force codes
     }
-    if (d->prec == 2 && x3v2 && d->cfg == 0 &&
+    if (d->prec == 2 && d->cfg == 0 &&
         ((d->a_mode == LVAE_A_PLAIN && d->K0 + d->K1 == d->K) || d->a_mode == LVAE_A_CONV3)) {   // cfg -1: legacy kernel
         int rc = 0;
-        if (lvae_gemm_x3v2_try(d, st, x3v2_tn, &rc)) return rc;
+        if (lvae_gemm_x3v2_try(d, st, 0, &rc)) return rc;
     }
     switch (d->a_mode) {
         case LVAE_A_PLAIN:

@@ -80,9 +80,6 @@ __global__ __launch_bounds__(256, (TN == 1 ? 3 : 2)) void gemm_h2_kernel(const l
         a_voff[j] = (row * d.lda0 + ak4 * 4) * 4;
         a_voff1[j] = (row * (int)lda1 + ak4 * 4) * 4;
         a_st[j] = row * ROWB + ak4 * 8;
-#ifdef LVAE_EXP_H2_FULLLINE        // experiment (WRONG RESULTS): a wave's load instruction covers 8 rows x 128 B (whole cache lines)
-        a_voff[j] = ((c >> 3) * d.lda0 + (c & 7) * 4) * 4;
-#endif
     }
     // 3x3-tap gather (implicit GEMM over an NHWC map, K = 9*Cin, tap-major): a stage of 16 channels lies inside one tap; the tap is a
     // uniform offset added to the row's pixel address, a tap outside the image an out-of-range address = a hardware zero.
@@ -117,9 +114,6 @@ __global__ __launch_bounds__(256, (TN == 1 ? 3 : 2)) void gemm_h2_kernel(const l
         const int c = tid + 256 * j, row = perm(c >> 2), piece = c & 3;
         w_voff[j] = row * (int)wrow_b + piece * 16;
         w_st[j] = (128 + row) * ROWB + piece * 16;
-#ifdef LVAE_EXP_H2_FULLLINE
-        w_voff[j] = (c >> 3) * (int)wrow_b + (c & 7) * 16;
-#endif
     }
     const int a_fr = (wave_m * 64 + li) * ROWB + 16 * lh;
     const int b_fr = (128 + wave_n * TN * 32 + li) * ROWB + 16 * lh;

@@ -20,14 +20,7 @@
 // order, then applies splitk_epilogue_store -- the operations of the parallel form + reduction in the same order, without the workspace.
 #include "gemm_common.h"
 
-#if !defined(LVAE_EXPERIMENTAL_BUILD) && (defined(H2N_EXP_CENTER) || defined(H2N_EXP_NOMFMA) || defined(H2N_EXP_NOLOAD))
-#error "H2N_EXP_* timing studies (wrong results) need -DLVAE_EXPERIMENTAL_BUILD (tools/build_exp.sh)"
-#endif
-#ifdef H2N_EXP_NOMFMA
-#define H2N_MFMA(a, b, c) (c)
-#else
 #define H2N_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#endif
 
 namespace {
 
@@ -127,18 +120,11 @@ __global__ __launch_bounds__(512, 1) void gemm_h2n_kernel(const lvae_gemm_desc d
             int vo;
             if (AMODE == LVAE_A_CONV3) {
                 const int kq = q * 16, tap = kq / d.K0, kk = kq - tap * d.K0;                 // uniform
-#ifdef H2N_EXP_CENTER        // timing study (wrong results): every tap reads the centre pixel -- what is left when the gather's re-reads hit L1
-                const int toff = kk * 4;
-#else
                 const int toff = (((tap / 3 - 1) * d.W + (tap % 3 - 1)) * d.K0 + kk) * 4;
-#endif
                 vo = ((tapok[j] >> tap) & 1) ? a_voff[j] + toff : 0x7fffffff;
             } else {
                 vo = a_voff[j] == 0x7fffffff ? a_voff[j] : a_voff[j] + q * 64;
             }
-#ifdef H2N_EXP_NOLOAD          // timing study: the A loads of the steady state go to an out-of-range address (no memory traffic)
-            if (q >= n_d<NB>()) vo = 0x7fffffff;
-#endif
             ar[slot][j] = __builtin_amdgcn_raw_buffer_load_b128(rsA, vo, 0, 0);
         }
     };

@@ -23,7 +23,6 @@
 // H: a_hi*w_hi), and the producers' split is the consumer's (exact), so every output bit equals gemm_h2_kernel's on the fp32 operand.
 #include "gemm_common.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -31,20 +30,8 @@ namespace {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #define LVAE_FENCE() __builtin_amdgcn_sched_barrier(0)
-// timing ablations (wrong results by construction; tools/build_exp.sh only): what a launch costs without its MFMAs / fragment reads / epilogue
-#if !defined(LVAE_EXPERIMENTAL_BUILD) && (defined(H2P_EXP_NOMFMA) || defined(H2P_EXP_NODSR) || defined(H2P_EXP_NOEPI) || defined(H2P_EXP_NODMA))
-#error "H2P_EXP_* ablations need -DLVAE_EXPERIMENTAL_BUILD (tools/build_exp.sh)"
-#endif
-#ifdef H2P_EXP_NODSR
-#define H2P_DSR(dst, addr, off) asm volatile("" : "=v"(dst) : "v"(addr))
-#else
 #define H2P_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#endif
-#ifdef H2P_EXP_NOMFMA
-#define H2P_MFMA(a, b, c) (c)
-#else
 #define H2P_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#endif
 
 // (the straight-line epilogue h2p_epilogue_fast lives in gemm_common.h)
 // FOLD ("serial split-K", d.ksplit = S > 1 with a_h2): ONE workgroup walks the S contiguous K slices of its tile and adds their partial sums
@@ -81,10 +68,10 @@ __global__ __launch_bounds__(128 * WM + 64 * NLOAD, (NLOAD ? 1 : (WM == 4 ? 1 : 
     const int li = lane & 31, lh = lane >> 5;
     const int nq = d.K / 32;
     const int rowb = d.K * 4;                                       // bytes of one H2K32 row (A and W alike)
-    // Phase stagger (LVAE_H2P_STAGGER, off by default).  Workgroups of one launch start together and take equally long, so the chip
+    // Phase stagger (launch_h2p passes 0: off).  Workgroups of one launch start together and take equally long, so the chip
     // alternates between main loops (matrix pipe busy, HBM nearly idle) and epilogues (every CU storing its tile, the matrix pipe idle).
     // Starting every second workgroup half a main loop late -- the second resident workgroup of a CU (told by its LDS allocation
-    // base) or, with one workgroup per CU, the odd CUs -- was measured and did NOT help (0 ... -5 %): kept as a knob for the record.
+    // base) or, with one workgroup per CU, the odd CUs -- was measured and did NOT help (0 ... -5 %).
     if (stagger > 0) {
         const bool late = WM == 4 ? ((__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (8 << 6) | 4) & 1) != 0)          // HW_ID.CU_ID bit 0
                                   : (__builtin_amdgcn_s_getreg(((8 - 1) << 11) | (0 << 6) | 6) != 0);                // LDS_ALLOC.LDS_BASE
@@ -134,11 +121,7 @@ __global__ __launch_bounds__(128 * WM + 64 * NLOAD, (NLOAD ? 1 : (WM == 4 ? 1 : 
     auto dma = [&](int i, int stage, int buf) {                     // i, buf: compile-time after unrolling; stage: uniform
         const int g = i * NWAVE + wave;
         const bool isA = g < BM / 8;                                // uniform
-#ifdef H2P_EXP_NODMA
-        const int soff = 0x7ffffff0;                                  // out of range: the DMA writes zeros, no memory traffic
-#else
         const int soff = (isA ? 8 * g : 8 * g - BM) * rowb + stage * 128;
-#endif
         __builtin_amdgcn_raw_ptr_buffer_load_lds(isA ? rsA : rsW, (__attribute__((address_space(3))) void*)((char*)smem + buf * STAGE + g * 1024),
                                                  16, dvoff, soff, 0, 0);
     };
@@ -264,10 +247,9 @@ __global__ __launch_bounds__(128 * WM + 64 * NLOAD, (NLOAD ? 1 : (WM == 4 ? 1 : 
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // trailing (redundant) DMAs have landed before LDS is reused / freed
     if constexpr (FOLD) {
-#ifndef H2P_EXP_GENERIC_EPI
         if (d.bias && n0 + BN <= d.N && !((d.ldo | d.ldres) & 3)) {          // uniform: a straight-line form of the tail below
             if (d.epi == LVAE_EPI_BIAS_GELU && d.out_h2 && !(d.ldo & 31)) {
-                h2p_epilogue_fast<TN, LVAE_EPI_BIAS_GELU, true, H2P_FULL_LINE, true>(d, tot, m0, n0, rows_a, wave_m, wave_n, li, lh);
+                h2p_epilogue_fast<TN, LVAE_EPI_BIAS_GELU, true, true, true>(d, tot, m0, n0, rows_a, wave_m, wave_n, li, lh);
                 return;
             }
             if (d.epi == LVAE_EPI_GAMMA_RES && !d.out_h2) {
@@ -279,7 +261,6 @@ __global__ __launch_bounds__(128 * WM + 64 * NLOAD, (NLOAD ? 1 : (WM == 4 ? 1 : 
                 return;
             }
         }
-#endif
         // the reduce kernel's tail on this tile: 4 consecutive columns of one row per lane (quad transpose), then its epilogue function
         const int lj = li & 3;
 #pragma unroll
@@ -303,13 +284,9 @@ __global__ __launch_bounds__(128 * WM + 64 * NLOAD, (NLOAD ? 1 : (WM == 4 ? 1 : 
         for (int b = 0; b < TN; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) accH[a][b][r] = __builtin_fmaf(accX[a][b][r], 1.0f / 2048.0f, accH[a][b][r]);
-#ifdef H2P_EXP_NOEPI
-    if (accH[0][0][0] == 123.456f) d.out[0] = accH[0][0][1] + accH[1][TN - 1][3];
-#else
-#ifndef H2P_EXP_GENERIC_EPI
     if (d.store == LVAE_ST_ROWMAJOR && n0 + BN <= d.N && !((d.ldo | d.ldres) & 3)) {          // uniform: one of the straight-line forms
         if (d.epi == LVAE_EPI_BIAS_GELU && d.out_h2 && !(d.ldo & 31)) {
-            h2p_epilogue_fast<TN, LVAE_EPI_BIAS_GELU, true, H2P_FULL_LINE>(d, accH, m0, n0, rows_a, wave_m, wave_n, li, lh);
+            h2p_epilogue_fast<TN, LVAE_EPI_BIAS_GELU, true, true>(d, accH, m0, n0, rows_a, wave_m, wave_n, li, lh);
             return;
         }
         if (d.epi == LVAE_EPI_GAMMA_RES && !d.out_h2) {
@@ -321,9 +298,7 @@ __global__ __launch_bounds__(128 * WM + 64 * NLOAD, (NLOAD ? 1 : (WM == 4 ? 1 : 
             return;
         }
     }
-#endif
     gemm_finish<C>(d, accH, m0, n0, wave_m, wave_n, li, lh, (void*)smem, t);
-#endif
 }
 
 template <int WM, int TN, int NBUF, bool FOLD = false, int NLOAD = 0>
@@ -332,36 +307,14 @@ int launch_h2p(const lvae_gemm_desc* d, hipStream_t st) {
     static LdsAttr attr;
     if (const int ae = attr.ensure((const void*)gemm_h2p_kernel<WM, TN, NBUF, FOLD, NLOAD>, LDS)) return ae;
     const int tiles_m = (d->M + BM - 1) / BM, tiles_n = (d->N + BN - 1) / BN, n_tiles = tiles_m * tiles_n;
-    static int lds_pad = 0, stagger = 0;
-#ifdef LVAE_EXPERIMENTAL_BUILD           // knobs of the round-3 studies (tools/build_exp.sh copies only; docs/MEASUREMENT_HISTORY.md 5c): extra dynamic LDS (forces
-    static bool env_read = false;        // one 128-row workgroup per CU) and the phase stagger (measured 0 ... -5 % on the model's shapes)
-    if (!env_read) {
-        const char* e = getenv("LVAE_H2P_LDSPAD"); lds_pad = e ? atoi(e) : 0;
-        e = getenv("LVAE_H2P_STAGGER"); stagger = e ? atoi(e) : 0;
-        env_read = true;
-    }
-    if (lds_pad > 0) (void)hipFuncSetAttribute((const void*)gemm_h2p_kernel<WM, TN, NBUF, FOLD, NLOAD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS + lds_pad);
-#endif
-    hipLaunchKernelGGL((gemm_h2p_kernel<WM, TN, NBUF, FOLD, NLOAD>), dim3(n_tiles), dim3(128 * WM + 64 * NLOAD), LDS + lds_pad, st, *d, tiles_n, n_tiles, stagger);
+    hipLaunchKernelGGL((gemm_h2p_kernel<WM, TN, NBUF, FOLD, NLOAD>), dim3(n_tiles), dim3(128 * WM + 64 * NLOAD), LDS, st, *d, tiles_n, n_tiles, 0);
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-// Entry point for gemm_f32.hip's dispatcher (prec 4, a_h2 = 1).  force: 0 = choose; 10 * WM + TN = that tile (tuning hook LVAE_H2P_TILE:
-// 42 = 256 x 128, 41 = 256 x 64, 22 = 128 x 128, 21 = 128 x 64).  Every choice gives the same bits.
-#ifdef LVAE_EXP_H2PP
-int lvae_gemm_h2pp_launch(const lvae_gemm_desc* d, hipStream_t st, int tn);        // gemm_h2pp.hip: the persistent-form study (force = 92 / 91)
-#endif
-
-#ifdef LVAE_EXP_H2E
-int lvae_gemm_h2e_try(const lvae_gemm_desc* d, hipStream_t st, int* rc);          // gemm_h2e.hip: the epilogue-interleaved study (force = 51)
-#endif
-
-#ifdef LVAE_EXP_H2Q
-int lvae_gemm_h2q_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc);          // gemm_h2q.hip: the loader-wave study (force = 61)
-#endif
-
+// Entry point for gemm_f32.hip's dispatcher (prec 4, a_h2 = 1).  force: 0 = choose; 10 * WM + TN = that tile (42 = 256 x 128,
+// 41 = 256 x 64, 22 = 128 x 128, 21 = 128 x 64).  Every choice gives the same bits.
 int lvae_gemm_h2p_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc) {
     if (d->prec != 4 || !d->a_h2 || d->a_mode != LVAE_A_PLAIN || d->K1 != 0 || d->K0 != d->K || (d->K & 31) || d->lda0 != d->K ||
         d->ldw != d->K || d->a_gelu || (long)256 * d->K * 4 > 0x7fffffffL)
@@ -372,33 +325,13 @@ int lvae_gemm_h2p_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* r
         // kernel's epilogue function stores), 128 x 64 tiles (the running sum lives beside two accumulator sets)
         if ((d->K / 32) % d->ksplit || d->store != LVAE_ST_ROWMAJOR || (N & 3) || (d->ldo & 3) || (d->ldres & 3)) return 0;
         // up to one workgroup per CU: eight loader waves beside the four compute waves (above); more tiles: two workgroups per CU hide
-        // each other's DMA issue as before (tuning hook of tools/r6_fold_loaders.sh: LVAE_FOLD_LOADERS=0 / 1)
-#ifdef LVAE_EXPERIMENTAL_BUILD
-        static const int force = getenv("LVAE_FOLD_LOADERS") ? atoi(getenv("LVAE_FOLD_LOADERS")) : -1;
-#else
-        constexpr int force = -1;                                   // (the product library's launch paths read no environment)
-#endif
+        // each other's DMA issue as before
         const int tiles = ((M + 127) / 128) * ((N + 63) / 64);
-        const bool loaders = force >= 0 ? force != 0 : tiles <= lvae_cu_count();
+        const bool loaders = tiles <= lvae_cu_count();
         *rc = loaders ? launch_h2p<2, 1, 3, true, 8>(d, st) : launch_h2p<2, 1, 3, true>(d, st);
         return 1;
     }
     int sel = force;
-#ifdef LVAE_EXP_H2Q
-    if (sel == 61) {
-        if (lvae_gemm_h2q_try(d, st, 1, rc)) return 1;
-        sel = 0;
-    }
-#endif
-#ifdef LVAE_EXP_H2E
-    if (sel == 51) {
-        if (lvae_gemm_h2e_try(d, st, rc)) return 1;
-        sel = 0;
-    }
-#endif
-#ifdef LVAE_EXP_H2PP
-    if ((sel == 92 || sel == 91) && d->K >= 128 && !(d->K & 63)) { *rc = lvae_gemm_h2pp_launch(d, st, sel - 90); return 1; }
-#endif
     if (sel != 42 && sel != 41 && sel != 22 && sel != 21 && sel != 23) {
         // Tile by measurement (profiles/r03_gemm_h2p_tile_sweep.txt: every MLP shape of the model at batch 4 and 8 under each tile):
         // least padded width first (N = 192: three 64-wide tiles, not two 128-wide); 64-wide: 128 x 64 everywhere; 128-wide: 128 x 64

@@ -19,7 +19,6 @@
 //    residual rows have the output's type.
 #include "gemm_common.h"
 
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -352,11 +351,7 @@ __global__ __launch_bounds__(256, (TN <= 2 && ABF ? 3 : 2)) void gemm_lp_kernel(
             }
         }
         const bool has_res = epi == LVAE_EPI_GAMMA_RES || epi == LVAE_EPI_RES;
-#ifdef LVAE_EXP_NO_RES_PREFETCH
-        const bool res_pf = false;
-#else
         const bool res_pf = has_res && store == LVAE_ST_ROWMAJOR;
-#endif
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             // residual values of this 32-row block: requested up front, back to back, from clamped (always valid) addresses -- loaded
@@ -466,14 +461,7 @@ int launch_lp_tn(const lvae_gemm_desc* d, hipStream_t st) {
     // temporaries (hipcc spills ~400 of them to scratch: measured 3x slower) and is not built.  Results do not depend on the choice.
     // fp32 A (the K = z operands of z_proj): 64-wide tiles (its wider instances would spill); N a multiple of 192: 128 x 192 tiles
     // (N = 192 is ONE column tile: A is read once instead of twice, and no half-empty 128 x 128 tile)
-    int tn = (d->N <= 64 || !ABF) ? 1 : ((d->N % 192 == 0) ? 3 : 2);
-#ifdef LVAE_EXPERIMENTAL_BUILD           // tile sweep hook (tools/build_exp.sh copies only)
-    {
-        static int force = -1;
-        if (force < 0) { const char* e = getenv("LVAE_LP_TN"); force = e ? atoi(e) : 0; }
-        if (force >= 1 && force <= 3 && ABF && d->N > 64) tn = force;
-    }
-#endif
+    const int tn = (d->N <= 64 || !ABF) ? 1 : ((d->N % 192 == 0) ? 3 : 2);
     if (tn == 1) return launch_lp<1, AMODE, ABF, OBF>(d, st);
     if constexpr (ABF) return tn == 3 ? launch_lp<3, AMODE, ABF, OBF>(d, st) : launch_lp<2, AMODE, ABF, OBF>(d, st);
     return -22;

@@ -311,7 +311,6 @@ __global__ __launch_bounds__(128 * WM, (WM == 4 ? 1 : 2)) void gemm_q8_kernel(co
     // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  Per-column ops, DPP
     // quad transpose (the lane then owns 4 consecutive COLUMNS of one row), then: out_h2 = the result re-quantised to Q8 for the next GEMM
     // (block amax over the 8 lanes that share a row and a 32-column block: ds_swizzle xor 4 / 8 / 16), else bf16 rows.
-#ifndef Q8_EXP_GENERIC_EPI
     if (n0 + BN <= d.N) {                                                   // uniform: full-width tile -> a straight-line form
         if (d.out_h2) {
             if (d.epi == LVAE_EPI_BIAS_GELU) { q8_epilogue_fast<TN, LVAE_EPI_BIAS_GELU, true>(d, acc, m0, n0, rows_a, wave_m, wave_n, li, lh); return; }
@@ -321,7 +320,6 @@ __global__ __launch_bounds__(128 * WM, (WM == 4 ? 1 : 2)) void gemm_q8_kernel(co
             if (d.epi == LVAE_EPI_RES) { q8_epilogue_fast<TN, LVAE_EPI_RES, false>(d, acc, m0, n0, rows_a, wave_m, wave_n, li, lh); return; }
         }
     }
-#endif
     const int epi = d.epi, lj = li & 3;
     const bool has_res = epi == LVAE_EPI_GAMMA_RES || epi == LVAE_EPI_RES;
     char* const outb = (char*)d.out;

@@ -23,13 +23,6 @@
 
 #include <type_traits>
 
-#ifdef LVAE_X3V2_TRACE             // tools/ubench/x3k16_trace.hip: s_memtime stamps of one wave per k16 stage
-extern "C" __device__ long* lvae_trace_buf;
-#define X3_STAMP(i) do { if (tracing) tstamp[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define X3_STAMP(i) do {} while (0)
-#endif
-
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -236,11 +229,6 @@ __global__ __launch_bounds__(256, (TN == 1 ? 3 : 2)) void gemm_x3k16_kernel(cons
     const int wave_m = wave >> 1, wave_n = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
     auto perm = [](int q) { return (q & ~7) | ((q & 3) << 1) | ((q >> 2) & 1); };        // 0,2,4,6,1,3,5,7
-#ifdef LVAE_EXP_PRIO
-    // the two workgroups of a CU get different issue priorities (told apart by their LDS allocation base), so that they drift
-    // out of phase instead of reaching their per-stage barriers together
-    if (__builtin_amdgcn_s_getreg(((8 - 1) << 11) | (0 << 6) | 6) != 0) __builtin_amdgcn_s_setprio(LVAE_EXP_PRIO);
-#endif
 
     // split-K (gridDim.y slices): this workgroup covers k16 stages [q0, q0 + nq); the slice offset goes into the buffer bases
     const int nq = d.K / 16 / (int)gridDim.y, q0 = (int)blockIdx.y * nq;
@@ -323,25 +311,15 @@ __global__ __launch_bounds__(256, (TN == 1 ? 3 : 2)) void gemm_x3k16_kernel(cons
         float x0 = __uint_as_float(ra[par][j][2 * h]), x1 = __uint_as_float(ra[par][j][2 * h + 1]);
         if (AGELU) { x0 = gelu_erf(x0); x1 = gelu_erf(x1); }
         unsigned hi, mid, lo;
-#ifdef LVAE_EXP_NOSPLIT            // experiment (wrong results): what the operand split costs inside the main loop
-        hi = ra[par][j][2 * h]; mid = ra[par][j][2 * h + 1]; lo = hi;
-#else
         split_pair(x0, x1, hi, mid, lo);
-#endif
         asm volatile("" : "+v"(hi), "+v"(mid), "+v"(lo));
         sa[0][h] = hi; sa[1][h] = mid; sa[2][h] = lo;
     };
     auto store_a = [&](char* st, int j) {
-#ifdef LVAE_EXP_NOSTORE
-        if (d.M > 0) return;
-#endif
 #pragma unroll
         for (int p = 0; p < 3; ++p) *(u32x2*)(st + a_st[j] + p * 32) = sa[p];
     };
     auto store_w = [&](char* st, int par, int j) {
-#ifdef LVAE_EXP_NOSTORE
-        if (d.M > 0) return;
-#endif
         *(u32x4*)(st + w_st[j]) = rb[par][j];
     };
     // load order of one register set: A0, W0, W1, A1, W2, W3, W4 -- the same in the prologue and in the loop (vmcnt bookkeeping)
@@ -365,29 +343,12 @@ __global__ __launch_bounds__(256, (TN == 1 ? 3 : 2)) void gemm_x3k16_kernel(cons
     __syncthreads();
 
     bf16x8 af[2][3], bf[2][3];
-#ifdef LVAE_X3V2_TRACE
-#if LVAE_X3V2_TRACE == 2           // every workgroup records: [block][8 header + 4 * 256 stamps]; header: start, end, HW_ID, XCC_ID
-    const bool tracing = tid == 0;
-    long* const tbuf = lvae_trace_buf + (long)blockIdx.x * (8 + 4 * 256);
-    if (tracing) {
-        tbuf[2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-        tbuf[3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        tbuf[4] = __builtin_amdgcn_s_getreg((31 << 11) | 6);
-    }
-#else
-    const bool tracing = blockIdx.x == (unsigned)(n_tiles / 2 + 8) && tid == 0;
-    long* const tbuf = lvae_trace_buf - 8;
-#endif
-    long tstamp[4] = {0, 0, 0, 0};
-    if (tracing) lvae_trace_buf[LVAE_X3V2_TRACE == 2 ? (long)blockIdx.x * (8 + 4 * 256) : 120] = __builtin_readcyclecounter();
-#endif
     // one k16 stage: compute on stage PAR, write tile q+1 from register set PAR^1 into the other stage, reload that set with q+3
     auto body = [&](auto par_tag, int q) {
         constexpr int PAR = decltype(par_tag)::value, OTH = PAR ^ 1;
         const int q3 = q + 3 < nq ? q + 3 : nq - 1;
         const char* cur = lds + PAR * STAGE;
         char* nxt = lds + OTH * STAGE;
-        X3_STAMP(0);
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -432,33 +393,15 @@ __global__ __launch_bounds__(256, (TN == 1 ? 3 : 2)) void gemm_x3k16_kernel(cons
                 }
                 LVAE_FENCE();
             }
-            if (g == 0) X3_STAMP(1);
         }
-        X3_STAMP(2);
         __syncthreads();
-        X3_STAMP(3);
-#ifdef LVAE_X3V2_TRACE
-        if (tracing && q < (LVAE_X3V2_TRACE == 2 ? 256 : 28)) for (int z = 0; z < 4; ++z) tbuf[8 + q * 4 + z] = tstamp[z];
-#endif
     };
     for (int q = 0; q < nq; q += 2) {
         body(std::integral_constant<int, 0>{}, q);
         body(std::integral_constant<int, 1>{}, q + 1);
     }
-#ifdef LVAE_X3V2_TRACE
-    if (tracing) lvae_trace_buf[LVAE_X3V2_TRACE == 2 ? (long)blockIdx.x * (8 + 4 * 256) + 1 : 121] = __builtin_readcyclecounter();
-#endif
     gemm_finish<C>(d, acc, m0, n0, wave_m, wave_n, li, lh, (void*)smem, t);
-#ifdef LVAE_X3V2_TRACE
-    if (tracing) lvae_trace_buf[LVAE_X3V2_TRACE == 2 ? (long)blockIdx.x * (8 + 4 * 256) + 5 : 122] = __builtin_readcyclecounter();
-#endif
 }
-
-#ifdef LVAE_X3V2_TRACE
-int g_x3v2_lds_pad = 0;            // trace harness: extra dynamic LDS to force one workgroup per CU
-#else
-constexpr int g_x3v2_lds_pad = 0;
-#endif
 
 template <int TN, bool AGELU, int AMODE>
 int launch_k16(const lvae_gemm_desc* d, hipStream_t st) {
@@ -466,7 +409,7 @@ int launch_k16(const lvae_gemm_desc* d, hipStream_t st) {
     static LdsAttr attr;
     if (const int ae = attr.ensure((const void*)gemm_x3k16_kernel<TN, AGELU, AMODE>, LDS + 64 * 1024)) return ae;
     const int tiles_m = (d->M + 127) / 128, tiles_n = (d->N + BN - 1) / BN, n_tiles = tiles_m * tiles_n;
-    hipLaunchKernelGGL((gemm_x3k16_kernel<TN, AGELU, AMODE>), dim3(n_tiles, d->ksplit > 1 ? d->ksplit : 1), dim3(256), LDS + g_x3v2_lds_pad, st, *d,
+    hipLaunchKernelGGL((gemm_x3k16_kernel<TN, AGELU, AMODE>), dim3(n_tiles, d->ksplit > 1 ? d->ksplit : 1), dim3(256), LDS, st, *d,
                        tiles_n, n_tiles);
     return (int)hipGetLastError();
 }
@@ -475,7 +418,7 @@ int launch_k16(const lvae_gemm_desc* d, hipStream_t st) {
 
 // Entry point for gemm_f32.hip's dispatcher.  Returns 1 when the problem is one these kernels take (and *rc holds the launch
 // status), 0 otherwise (the caller falls back to gemm_x3_kernel).  force: 0 = choose; 1..3 = k16 kernel with TN = force;
-// 8 = the 8-wave 256 x 128 kernel (tuning hook LVAE_X3V2_TN).  Every choice gives the same bits.
+// 8 = the 8-wave 256 x 128 kernel.  Every choice gives the same bits.
 int lvae_gemm_x3v2_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc) {
     const bool conv3 = d->a_mode == LVAE_A_CONV3;
     if (d->prec != 2 || (d->a_mode != LVAE_A_PLAIN && !conv3) || (d->K & 31) || d->ldw != d->K) return 0;

@@ -28,35 +28,14 @@
 #include <type_traits>
 #include <utility>
 
-#if !defined(LVAE_EXPERIMENTAL_BUILD) && (defined(H2C_EXP_NOGELU) || defined(H2C_EXP_NOADMA) || defined(H2C_EXP_NOWDMA) || defined(H2C_EXP_NOMFMA) || \
-    defined(H2C_EXP_NOEPI) || defined(H2C_EXP_NODSR) || defined(H2C_EXP_NOBAR) || defined(H2C_EXP_TRACE) || defined(H2C_EXP_NOARES))
-#error "H2C_EXP_* ablations (wrong results by construction: they remove work to time what is left) need -DLVAE_EXPERIMENTAL_BUILD (tools/build_exp.sh)"
-#endif
-// H2C_EXP_TRACE: in-kernel timeline (s_memtime) of wave 0 of workgroup 0 on its SECOND tile, written behind the output rows
-// (out + M * C floats; tools/microbench.py mlptrace allocates the room): slot 3P .. 3P + 2 = before the counted wait / before the barrier /
-// behind the barrier of position P; 96 + 2 ch .. = GELU phase of chunk ch begins / ends; 104 .. 106 = epilogue begins / next tile's stages
-// landed / stores issued
-#ifdef H2C_EXP_TRACE
-#define H2C_T(slot) do { if (trace_on) trace[slot] = __builtin_readcyclecounter(); } while (0)
-#else
-#define H2C_T(slot) do { } while (0)
-#endif
-#ifdef H2C_EXP_NOMFMA
-#define H2C_MFMA(a, b, c) (c)
-#else
 #define H2C_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#endif
 
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #define LVAE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#ifdef H2C_EXP_NODSR
-#define H2C_DSR(dst, addr, off) asm volatile("" : "=v"(dst) : "v"(addr))
-#else
 #define H2C_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#endif
 
 template <int N, class F, int... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -163,13 +142,8 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
     const int perm = (pp ^ ((4 * (wave & 1) + (r_in >> 1)) & 7)) << 4;
     const int dvA = r_in * (C * 4) + perm;               // A / W1 rows are C * 4 bytes (H2K32)
     const int dvW2 = r_in * (HID * 4) + perm;            // W2 rows are HID * 4 bytes
-#ifdef H2C_EXP_NOWDMA
-    const __amdgpu_buffer_rsrc_t rsW1 = __builtin_amdgcn_make_buffer_rsrc((void*)d.w1, 0, 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsW2 = __builtin_amdgcn_make_buffer_rsrc((void*)d.w2, 0, 0, 0x00020000);
-#else
     const __amdgpu_buffer_rsrc_t rsW1 = __builtin_amdgcn_make_buffer_rsrc((void*)d.w1, 0, HID * C * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW2 = __builtin_amdgcn_make_buffer_rsrc((void*)d.w2, 0, C * HID * 4, 0x00020000);
-#endif
     // issue the DMA instructions of tile-relative position P (compile time) of the tile whose A rows start at `abase` (`arows` valid rows;
     // 0 rows = nothing to fetch: every lane out of range, the slot is zero-filled -- keeps the instruction count, hence vmcnt, uniform)
     auto dma_pos = [&](auto ptag, int i, const char* abase, int arows) __attribute__((always_inline)) {
@@ -184,9 +158,6 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
                                                      (CH * S::HC + 8 * g) * (C * 4) + Q * 128, 0, 0);
         } else if constexpr (Q < KS1) {                  // F stage Q of chunk CH: A rows 0 .. BM - 1 | W1 rows CH * HC .. + HC - 1, k32 index Q
             if (i < S::NA) {
-#ifdef H2C_EXP_NOADMA
-                arows = 0;
-#endif
                 const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)abase, 0, arows * (C * 4), 0x00020000);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(slot + g * 1024), 16, dvA, 8 * g * (C * 4) + Q * 128, 0, 0);
             } else {
@@ -205,9 +176,6 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
         int wv = wave;
         asm volatile("" : "+s"(wv));
         const int ga = ia * 8 + wv;
-#ifdef H2C_EXP_NOADMA
-        arows = 0;
-#endif
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)abase, 0, arows * (C * 4), 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)((char*)smem + S::AOFF + stg * (BM * 128) + ga * 1024), 16, dvA,
                                                  8 * ga * (C * 4) + stg * 128, 0, 0);
@@ -256,15 +224,7 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
     f16x8 ca[2], cw[S::NBM][2];                                             // carried: A planes, W blocks x planes
     f32x4 rv[4][NB2];                                                        // residual rows of this tile (requested four stages early)
     bool first = true;
-#ifdef H2C_EXP_TRACE
-    unsigned long long* trace = (unsigned long long*)(d.out + (long)d.M * C);
-    int tile_no = 0;
-#endif
     for (; tile < n_tiles; tile += gridDim.x) {
-#ifdef H2C_EXP_TRACE
-        const bool trace_on = blockIdx.x == 0 && tid == 0 && tile_no == 1;
-        ++tile_no;
-#endif
         const int m0 = tile * BM;
         const int nxt = tile + gridDim.x;
         const char* ab_cur = tile_abase(tile);
@@ -299,18 +259,13 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
             // everyone's have, and everyone is done with position P - 1 -- fragment reads included (lgkmcnt: the slot of position P - 1 is
             // the target of the DMAs issued below).  Positions 0 and 1 of a tile that follows another one were waited for before that
             // tile's epilogue stores.
-            H2C_T(3 * P);
             if (P >= LA || first) {
                 constexpr int ALLOW = S::ni_between(P) + S::nextra_between(P) + ((CH == S::NCH - 1 && Q >= KS1 && Q < KS1 + LA) ? 4 * NB2 : 0);
                 asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(ALLOW) : "memory");
             } else {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
-            H2C_T(3 * P + 1);
-#ifndef H2C_EXP_NOBAR
             asm volatile("s_barrier" ::: "memory");
-#endif
-            H2C_T(3 * P + 2);
             LVAE_FENCE();
             int issued = 0;
             // (opaque: the per-slot, per-piece addresses are recomputed per stage -- a few v_add in MFMA shadows -- instead of being hoisted
@@ -383,7 +338,6 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
                 int lio = li, lho = lh;
                 asm volatile("" : "+v"(lio), "+v"(lho));
                 const int lj = lio & 3;
-                H2C_T(96 + 2 * CH);
 #pragma unroll
                 for (int b = 0; b < NBF; ++b) {
                     const int cs = NBF * wn + b;                              // hidden columns 32 NBF wn + 32 b .. + 31 of the chunk = stage cs
@@ -394,15 +348,11 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
                         float v1 = __builtin_fmaf(pX[b][4 * g + 1], 1.0f / 2048.0f, pH[b][4 * g + 1]) + b1v[CH][b];
                         float v2 = __builtin_fmaf(pX[b][4 * g + 2], 1.0f / 2048.0f, pH[b][4 * g + 2]) + b1v[CH][b];
                         float v3 = __builtin_fmaf(pX[b][4 * g + 3], 1.0f / 2048.0f, pH[b][4 * g + 3]) + b1v[CH][b];
-#ifdef H2C_EXP_NOGELU
-                        unsigned h0 = __float_as_uint(v0), l0 = __float_as_uint(v1), h1 = __float_as_uint(v2), l1 = __float_as_uint(v3);
-#else
                         gelu_erf4(v0, v1, v2, v3);
                         quad_transpose(v0, v1, v2, v3, lj);
                         unsigned h0, l0, h1, l1;
                         split_pair_h2(v0, v1, h0, l0);
                         split_pair_h2(v2, v3, h1, l1);
-#endif
                         const int m = 32 * wm + 4 * lho + 8 * g + lj;
                         const int k = (m >> 1) & 7, x = ((k << 1) & 7) | (k >> 2);
                         const unsigned base = lds0 + S::RING + cs * (BM * 128) + m * 128 + ((cc & 7) << 1);
@@ -411,7 +361,6 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
                         asm volatile("ds_write_b64 %0, %1" ::"v"(base + ((((cc >> 3) + 4) ^ x) << 4)), "v"(lo2) : "memory");
                     }
                 }
-                H2C_T(97 + 2 * CH);
                 if constexpr (CH == S::NCH - 1) {
                     // the tile's residual rows, requested now (the P accumulators are dead: their registers hold the 4 * NB2 vectors), four
                     // fc2 stages before the epilogue adds them -- their latency under load (2 - 4 us) used to be exposed once per tile
@@ -421,11 +370,7 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
                         const int rbg = (row < d.M ? row : 0) * C;            // (M * C < 2^31: checked on the host)
 #pragma unroll
                         for (int b = 0; b < NB2; ++b)
-#ifdef H2C_EXP_NOEPI
-                            rv[g][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#else
                             rv[g][b] = *(const f32x4*)(d.res + rbg + col_of(b) + (lio & ~3));
-#endif
                     }
                 }
             }
@@ -439,7 +384,6 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
             int lio = li, lho = lh;
             asm volatile("" : "+v"(lio), "+v"(lho));
             const int lj = lio & 3;
-            H2C_T(104);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
 #pragma unroll
@@ -455,7 +399,6 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
             // (residual rows long here;) next tile's positions 0 and 1 landed -- ARES: and its A stages 0 / 1; stages 2 / 3, the youngest
             // loads, may still be on their way
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ARES ? 2 * S::NA : 0) : "memory");
-            H2C_T(105);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int row = m0 + 32 * wm + 4 * lho + 8 * g + lj;       // (recomputed: the rows of the residual request, not kept in registers)
@@ -463,18 +406,13 @@ __global__ __launch_bounds__(512, 1) void mlp_h2c_kernel(const lvae_mlp_desc d, 
                 const int rbg = (rokg ? row : 0) * C;
 #pragma unroll
                 for (int b = 0; b < NB2; ++b) {
-#ifdef H2C_EXP_NOEPI
-                    if (rokg && oH[b][4 * g] == 123.456f) {
-#else
                     if (rokg) {
-#endif
                         f32x4 o = {oH[b][4 * g + 0], oH[b][4 * g + 1], oH[b][4 * g + 2], oH[b][4 * g + 3]};
                         o[0] += rv[g][b][0]; o[1] += rv[g][b][1]; o[2] += rv[g][b][2]; o[3] += rv[g][b][3];
                         *(f32x4*)(d.out + rbg + col_of(b) + (lio & ~3)) = o;
                     }
                 }
             }
-            H2C_T(106);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -500,11 +438,7 @@ int launch_h2c(const lvae_mlp_desc* d, hipStream_t st) {
 extern "C" int lvae_mlp_h2f(const lvae_mlp_desc* d, void* stream) {
     if (!d || !d->y || !d->w1 || !d->b1 || !d->w2 || !d->b2 || !d->gamma || !d->res || !d->out || d->M <= 0) return -22;
     if (d->C == 192 && d->hid == 384) return launch_h2c<192, 384, 128>(d, (hipStream_t)stream);
-#ifdef H2C_EXP_NOARES
-    if (d->C == 128 && d->hid == 192) return launch_h2c<128, 192, 64>(d, (hipStream_t)stream);
-#else
     if (d->C == 128 && d->hid == 192) return launch_h2c<128, 192, 64, 128, 1, 3, true>(d, (hipStream_t)stream);
-#endif
     if (d->C == 384 && d->hid == 768) return launch_h2c<384, 768, 128, 64, 3, 4>(d, (hipStream_t)stream);
     // (C = 256 / hidden = 448, 512 as <256, hid, 64, 128, 2, 4> was instantiated and measured: bit-identical, 30 spilled registers, 134.7 against
     //  124.3 us at M = 49152, 66.2 against 68.9 at 24576: profiles/r04_mlp_h2c_384x768.txt -- not built into the library)

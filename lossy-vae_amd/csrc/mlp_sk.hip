@@ -25,7 +25,6 @@
 // the point is the number of dependent launches, not the matrix pipe.
 #include "gemm_common.h"
 
-#include <cstdlib>
 
 int lvae_splitk_reduce_launch(const lvae_gemm_desc* d, int S, hipStream_t st);        // gemm_f32.hip
 
@@ -280,13 +279,8 @@ extern "C" int lvae_mlp_sk(const lvae_mlp_sk_desc* d, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int rc = -22;
     if (C != 512) return -22;
-    // 64-row workgroups where 32-row ones would be more than one round of the chip's CUs (tuning hook of tools/r6_mlp_sk_bench.py: LVAE_SK_NRB)
-#ifdef LVAE_EXPERIMENTAL_BUILD
-    static const int force_nrb = getenv("LVAE_SK_NRB") ? atoi(getenv("LVAE_SK_NRB")) : 0;
-#else
-    constexpr int force_nrb = 0;                                    // (the product library's launch paths read no environment)
-#endif
-    const bool two = force_nrb ? force_nrb == 2 : ((d->M + 31) / 32) * S2 > lvae_cu_count();
+    // 64-row workgroups where 32-row ones would be more than one round of the chip's CUs
+    const bool two = ((d->M + 31) / 32) * S2 > lvae_cu_count();
     if (CH == 128 && ngrp == 4) rc = two ? launch_sk<128, 4, 16, 8, 1, 2>(d, st) : launch_sk<128, 4, 16, 8, 2, 1>(d, st);
     else if (CH == 192 && ngrp == 3) rc = launch_sk<192, 3, 16, 8, 2, 1>(d, st);      // (two row blocks would be 20 waves)
     else if (CH == 256 && ngrp == 2) rc = launch_sk<256, 2, 16, 4, 1, 1>(d, st);

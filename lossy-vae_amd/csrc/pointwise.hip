@@ -12,7 +12,6 @@
 // accesses, wave64 shuffles for the per-pixel reductions, and >> 256 workgroups per launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/lvae_hip.h"
 #include "device_math.h"
@@ -180,8 +179,6 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(const void* __restrict__
     }
 }
 
-int g_dw_th = 0;       // tuning hook (LVAE_DW_TH): 1 or 2 output rows per group; 0 = heuristic
-
 template <int KS, int VPL, int LPP, int TH, bool BF = false>
 int launch_dwln_th(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
                    const float* shift, const float* scale1p, void* y, int B, int H, int W, hipStream_t st) {
@@ -202,7 +199,7 @@ int launch_dwln(const float* x, const float* wt, const float* bias, const float*
     // slower on the C >= 256 layers, where 200+ VGPRs halve the occupancy.  Same accumulation order => same bits either way.
     const long px = (long)B * H * W;
     constexpr int C = 4 * VPL * LPP;
-    int th = g_dw_th ? g_dw_th : ((KS == 7 && C <= 192 && VPL <= 3 && px >= 100000) ? 2 : 1);
+    int th = (KS == 7 && C <= 192 && VPL <= 3 && px >= 100000) ? 2 : 1;
     if (KS == 1 || VPL > 4) th = 1;          // VPL = 9 (C = 144, 288) has no registers for a second row
     if (th == 2) return launch_dwln_th<KS, VPL, LPP, (KS == 1 ? 1 : 2)>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
     return launch_dwln_th<KS, VPL, LPP, 1>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
@@ -620,13 +617,6 @@ extern "C" int lvae_dwconv_ln_f32(const float* x, const float* wt, const float* 
         int rc = 0;
         if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 0, (hipStream_t)stream, &rc)) return rc;
     }
-#ifdef LVAE_EXPERIMENTAL_BUILD           // tile-height sweep hook (tools/build_exp.sh copies only)
-    static bool env_read = false;
-    if (!env_read) {
-        const char* e = getenv("LVAE_DW_TH"); if (e) g_dw_th = atoi(e);
-        env_read = true;
-    }
-#endif
     hipStream_t st = (hipStream_t)stream;
     switch (k) {
         case 1: return dispatch_dwln_c<1>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);

@@ -1,58 +1,16 @@
 """Launch plans: a model's encode/decode for one (batch, height, width) is recorded ONCE as a flat list of native
 launches (function pointer + fully resolved arguments: device addresses of pre-allocated NHWC buffers and packed
-weights), then replayed with a tight loop -- or as a HIP graph -- on the current HIP stream.
+weights), then replayed by one native call per launch range on the current HIP stream.
 
 This is the MI355X-side replacement for the reference's eager `nn.Module.forward` dispatch (~450 leaf modules and
 ~10^3 elementwise kernels per encode: SURVEY.md 8(a) A15).  PyTorch is used only as the allocator / stream owner.
 """
 import ctypes
-import os
 
 import torch
 
 from . import _native
 from ._native import GemmDesc
-
-
-# tile configurations of lvae_gemm_f32 (index = cfg-1): (BM, BN) -- used only to prune autotune candidates
-_GEMM_TILES = [(128, 128), (128, 64), (64, 64), (256, 256), (256, 192), (256, 224), (256, 128), (128, 256), (128, 192), (128, 32),
-               (64, 64), (128, 64)]
-_TUNE_CACHE = {}
-
-
-def autotune_gemm(lib, d, stream_ptr, device):
-    """Pick the fastest tile configuration for this GEMM shape by timing the candidates on the GPU (2 timed runs each
-    after a warm-up).  Every configuration produces bit-identical results (fixed k-order), so this only affects speed."""
-    key = (d.M, d.N, d.K, d.K0, d.K1, d.a_mode, d.epi, d.store)
-    best = _TUNE_CACHE.get(key)
-    if best is not None:
-        return best
-    cands = []
-    for i, (bm, bn) in enumerate(_GEMM_TILES):
-        if bn >= 2 * d.N and bn > 32:          # more than half of the tile's columns would be padding
-            continue
-        if d.N > 4 * bn and bn <= 64:          # narrow tiles on a wide problem
-            continue
-        if bm >= 4 * d.M and bm > 64:
-            continue
-        cands.append(i + 1)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    st = torch.cuda.current_stream(device)
-    best, best_t = 0, float('inf')
-    for c in cands:
-        d.cfg = c
-        if lib.lvae_gemm_f32(ctypes.byref(d), stream_ptr) != 0:
-            continue
-        e0.record(st)
-        for _ in range(2):
-            lib.lvae_gemm_f32(ctypes.byref(d), stream_ptr)
-        e1.record(st)
-        e1.synchronize()
-        t = e0.elapsed_time(e1)
-        if t < best_t:
-            best, best_t = c, t
-    _TUNE_CACHE[key] = best
-    return best
 
 
 # Split-K policy constants.  They are part of the bitstream contract (the slice count fixes a GEMM's summation order, and encoder and
@@ -147,8 +105,6 @@ class _EventHolder:
 
 
 class Plan:
-    autotune = os.environ.get('LVAE_AUTOTUNE', '0') == '1'    # opt-in: in-situ gains were within noise (docs/MEASUREMENT_HISTORY.md 5)
-
     def __init__(self, device):
         self.lib = _native.lib()
         self.device = torch.device(device)
@@ -165,9 +121,7 @@ class Plan:
         self.w16_x3 = None     # f16x2 plans: the bf16x3 map for the GEMMs the f16x2 kernel does not take
         self.w16_k32 = None    # f16x2 plans: weights in the H2K32 plane format for the pre-split-operand GEMMs (csrc/gemm_h2p.hip)
         self.w16_q8 = None     # fp8 plans: weights in the Q8 format of the pre-quantised-operand GEMMs (csrc/gemm_q8.hip)
-        self.graphs = {}       # (lo, hi) -> torch.cuda.CUDAGraph (a hipGraph of that launch range), captured on 2nd use
         self.segments = {}     # (lo, hi, n_ops) -> (lvae_op array, n): the native form of that launch range
-        self.seen = set()
         # Independent branches on a side stream (small maps only: there the GPU is far from full and the launches of a branch are
         # pure latency): ops recorded between side_begin() / side_end() go to `side_stream`, ordered against the main stream by
         # fork (side waits for main) / join (main waits for side) events.  Results do not change -- same kernels, same inputs.
@@ -225,7 +179,7 @@ class Plan:
         self.ops.append((fn, tuple(args), label, self.on_side))
 
     def enable_side_stream(self):
-        if self.side_stream is None and not self.use_graphs:
+        if self.side_stream is None:
             self.side_stream = torch.cuda.Stream(device=self.device)
         return self.side_stream is not None
 
@@ -385,9 +339,6 @@ class Plan:
                         self.keep.append(cnt)
                     cnt = self.bufs[cname] = torch.zeros(max(4096, n_cnt), dtype=torch.int32, device=self.device)
                 d.cnt = cnt.data_ptr()
-        if self.autotune and M * N >= 64 * 64:
-            sp = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            d.cfg = autotune_gemm(self.lib, d, sp, self.device)
         self.keep.append(d)
         self.flops += 2 * M * N * K
         self.add(self.lib.lvae_gemm_f32, (ctypes.byref(d),), label)
@@ -439,7 +390,7 @@ class Plan:
     # The MLP of a small-map block (both GEMMs split-K) as fused launch + reduce (csrc/mlp_sk.hip, round 6): same bits as the split-K
     # launches whichever form runs them, so the rule may look at the batch.  Taken up to this many rows per launch (beyond, the
     # pre-split serial split-K launches fill the chip and stream each weight once per 128 rows instead of once per 32).
-    MLP_SK_MAX_ROWS = int(os.environ.get('LVAE_MLP_SK_MAX_ROWS', '1024'))
+    MLP_SK_MAX_ROWS = 1024
 
     def mlp_sk_ok(self, C, hid, k, rows_per_image, M, n_affine=1):
         """f16x2 plans: (S1, S2) when the block's MLP runs as lvae_mlp_sk, else None.  Only where the two-launch alternative is split-K
@@ -468,15 +419,9 @@ class Plan:
         self.flops += 4 * M * C * hid
 
     # ---- execution
-    # opt-in: measured +-0.5% at B=1 (the path is GPU-latency-bound, not launch-bound) and HIP's global capture mode
-    # conflicts with the two pipeline-group threads launching concurrently (hipErrorStreamCaptureInvalidated).
-    use_graphs = os.environ.get('LVAE_GRAPHS', '0') == '1'
-
     # Replay: a launch range is compiled once into a native segment (an array of lvae_op: entry point id + arguments by class) and run
     # by ONE foreign call that needs no interpreter state (csrc/plan_runtime.cpp) -- with several pipeline groups launching from their
-    # own threads, one ctypes call per launch made the interpreter lock the schedule.  LVAE_PY_REPLAY=1 keeps the per-launch Python
-    # loop (debugging: the failing launch's label comes with the error either way).
-    py_replay = os.environ.get('LVAE_PY_REPLAY', '0') == '1'
+    # own threads, one ctypes call per launch made the interpreter lock the schedule.  The failing launch's label comes with an error.
 
     def _segment(self, lo, hi):
         key = (lo, hi, len(self.ops))
@@ -512,49 +457,14 @@ class Plan:
             label = self.ops[lo + bad.value][2] if bad.value >= 0 else '?'
             raise RuntimeError(f'native launch "{label}" failed: rc={rc}')
 
-    def _run_eager(self, lo, hi, s):
-        if not self.py_replay:
-            return self._run_native(lo, hi, s)
-        sp = ctypes.c_void_p(s)
-        ss = ctypes.c_void_p(self.side_stream.cuda_stream) if self.side_stream is not None else None
-        for fn, args, label, side in self.ops[lo:hi]:
-            if fn is _ORDER:
-                rc = self.lib.lvae_stream_order(sp, ss, args[1]) if args[0] else self.lib.lvae_stream_order(ss, sp, args[1])
-            else:
-                rc = fn(*args, ss if side else sp)
-            if rc != 0:
-                raise RuntimeError(f'native launch "{label}" failed: rc={rc}')
-
     def run(self, lo=0, hi=None, stream=None):
-        """Replay ops[lo:hi] on `stream` (raw hipStream_t; default: torch's current stream).  The first use of a range
-        runs eagerly (also warms one-time kernel attributes); the second use captures it into a hipGraph (all buffers are
-        pre-allocated, so the capture contains kernel nodes only); later uses replay the graph with ONE host call instead
-        of one ctypes call per launch."""
+        """Replay ops[lo:hi] on `stream` (raw hipStream_t; default: torch's current stream) as one native call: the range's
+        segment is built on its first use and kept."""
         if torch.cuda.current_device() != self.device.index:      # launches go to the plan's GPU whatever the caller's current device
             with torch.cuda.device(self.device):
                 return self.run(lo, hi, stream)
-        cur = torch.cuda.current_stream(self.device)
-        s = stream if stream is not None else cur.cuda_stream
-        key = (lo, hi)
-        if self.use_graphs and s == cur.cuda_stream:
-            g = self.graphs.get(key)
-            if g:
-                g.replay()
-                return
-            if g is None and key in self.seen and cur.cuda_stream != 0:
-                try:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=cur):
-                        self._run_eager(lo, hi, torch.cuda.current_stream(self.device).cuda_stream)
-                    self.graphs[key] = g
-                    g.replay()
-                    return
-                except Exception as e:      # capture unsupported in this context: stay eager for this range
-                    self.graphs[key] = False
-                    import warnings
-                    warnings.warn(f'hipGraph capture failed for launch range {key}: {e}; running eagerly')
-            self.seen.add(key)
-        self._run_eager(lo, hi, s)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        self._run_native(lo, hi, s)
 
 
 def ptr(t, offset_elems=0):

@@ -243,15 +243,12 @@ class CodecBase(nn.Module):
                          type(self).__name__, self._prec, ' (package default)' if self._prec == DEFAULT_PRECISION else ' (set explicitly)')
 
     # ---- one pipeline group's decode / encode as ONE foreign call (csrc/plan_runtime.cpp: lvae_decode_blocks / lvae_encode_blocks)
-    native_group_loops = os.environ.get('LVAE_PY_GROUP_LOOP') != '1'        # debugging / A-B switch: '1' = the per-block Python loops
-    status_checks = os.environ.get('LVAE_NO_STATUS_CHECK') != '1'           # A-B switch of tools/ab_status.sh ONLY: '1' = the group loops run
-                                                                            # without the status word (what the non-finite guard costs)
+    native_group_loops = True             # False: the per-block Python loops (tests and bench.py compare the two)
 
     # The coder's arrays travel without copies (round 5): the index / quantize / dequantize launches of a group's native loops are recorded
     # with the plan's PINNED HOST arrays as their raster operands (device-mapped host memory; the kernels touch the raster in runs of 64
     # consecutive entries, csrc/pointwise.hip), so a decode has no blit launch between a segment and the coder or between the coder and the
-    # next segment, and an encode none behind its segments.  'both' | 'dec' | 'enc' | 'none' (A-B switch LVAE_ZERO_COPY: tools/r5_zero_copy.sh); the per-block Python loops and the test hooks keep the device arrays.
-    zero_copy_coder_io = os.environ.get('LVAE_ZERO_COPY', 'both')
+    # next segment, and an encode none behind its segments.  The per-block Python loops and the test hooks keep the device arrays.
 
     @staticmethod
     def _alias_host(pl, seg, n_ops):
@@ -281,7 +278,6 @@ class CodecBase(nn.Module):
         cached = getattr(pl, key, None)
         if cached is None:
             cls = _native.DecBlock if kind == 'dec' else _native.EncBlock
-            zero_copy = cls_.zero_copy_coder_io in (kind, 'both')
             arr = (cls * len(cuts))()
             segs, lo = [], 0
             for li, cut in enumerate(cuts):
@@ -293,13 +289,12 @@ class CodecBase(nn.Module):
                 b.ops, b.n_ops, b.per_image = ctypes.cast(seg, ctypes.c_void_p).value, n_ops, z * hw
                 b.idx_dev, b.idx_host = pl.idx_all.data_ptr() + o, pl.idx_host.data_ptr() + o
                 b.sym_dev, b.sym_host = pl.sym_all.data_ptr() + 4 * o, pl.sym_host.data_ptr() + 4 * o
-                if zero_copy:
-                    seg = cls_._alias_host(pl, seg, n_ops)
-                    segs[-1] = seg
-                    b.ops, b.idx_dev, b.sym_dev = ctypes.cast(seg, ctypes.c_void_p).value, None, None
+                seg = cls_._alias_host(pl, seg, n_ops)
+                segs[-1] = seg
+                b.ops, b.idx_dev, b.sym_dev = ctypes.cast(seg, ctypes.c_void_p).value, None, None
                 lo = cut
             tail, n_tail = pl._segment(lo, len(pl.ops)) if kind == 'dec' else (None, 0)
-            if zero_copy and n_tail:                       # (the last block's symbols are read by the tail's first launch)
+            if n_tail:                                     # (the last block's symbols are read by the tail's first launch)
                 tail = cls_._alias_host(pl, tail, n_tail)
             early = None
             if kind == 'dec' and len(cuts):                # the same blocks with block 0's launches taken out: _decode_group_native issues
@@ -344,7 +339,7 @@ class CodecBase(nn.Module):
         if trace is not None:
             secs[0], secs[1] = -64.0, _native.TRACE_MAGIC          # timeline request: capacity AND the magic word (include/lvae_hip.h)
         ss = pl.side_stream.cuda_stream if pl.side_stream is not None else None
-        st_dev = pl.status_ptr() if self.status_checks else None
+        st_dev = pl.status_ptr()
         with torch.cuda.device(pl.device):
             rc = _native.lib().lvae_decode_blocks(arr, nb, n, sp, sl, qcdf.ctypes.data, qcdf.shape[1], cdf_len.ctypes.data, offset.ctypes.data,
                                                   ctypes.cast(tail, ctypes.c_void_p) if n_tail else None, n_tail, st_dev, pl.status_host.data_ptr(),
@@ -383,7 +378,7 @@ class CodecBase(nn.Module):
         fb, fo = ctypes.c_int(-1), ctypes.c_int(-1)
         secs = (ctypes.c_double * 3)()
         ss = pl.side_stream.cuda_stream if pl.side_stream is not None else None
-        st_dev = pl.status_ptr() if self.status_checks else None
+        st_dev = pl.status_ptr()
         with torch.cuda.device(pl.device):
             rc = _native.lib().lvae_encode_blocks(arr, nb, n, op, oc, out_len, qcdf.ctypes.data, qcdf.shape[1], cdf_len.ctypes.data, offset.ctypes.data,
                                                   st_dev, pl.status_host.data_ptr(), ctypes.c_void_p(stream.cuda_stream),
@@ -416,8 +411,6 @@ class CodecBase(nn.Module):
         tail segment); wait for the caller's stream -- which waits for the groups' -- and raise if a NaN / inf reached a prior
         parameter or the reconstruction.  The reference's protocol synchronises right after decompress() anyway
         (scripts/speedtest-lvae.py:34-36), so this costs nothing there; the reconstruction is never handed on unchecked."""
-        if not self.status_checks:
-            return
         torch.cuda.current_stream(self._dummy.device).synchronize()
         err = None
         for g, (_start, n) in enumerate(groups):
@@ -506,14 +499,9 @@ class CodecBase(nn.Module):
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))        # lambda tables / inputs produced on the caller's stream
 
-        stagger = float(getattr(self, 'group_stagger_s', 0.0) or 0.0)       # study knob (tools/r6_stagger_groups.py): group g starts g x this later
-
         def work(g):
             st = self._streams[g]
             st.wait_event(ev)
-            if stagger > 0.0 and g:
-                import time as _t
-                _t.sleep(g * stagger)              # (sleep, not a spin: a spinning Python thread keeps the GIL from the other groups' threads)
             with torch.cuda.stream(st):
                 return fn(g, groups[g][0], groups[g][1], st)
         # the last group runs on the calling thread (no hand-over latency for it; the pool threads have theirs first)

@@ -366,7 +366,7 @@ class _EncPlan(_NetPlan):
                                              m.out_channels, model.im_shift, model.im_scale, self.status_ptr()), p + '.stem')
                 self.flops += 2 * B * h * w * m.out_channels * 48
             elif m.kind == 'down':
-                if self.side_stream is not None and (h, w) == (H // 16, W // 16) and not hoisted and (not small_side or getattr(model, 'hoist_small', True)):
+                if self.side_stream is not None and (h, w) == (H // 16, W // 16) and not hoisted:
                     self._hoist_posterior0(model, feats, hoisted, H, W)
                 h, w = h // 2, w // 2
                 nx = self.new(B * h * w * m.out_channels, self.adt)
@@ -546,8 +546,8 @@ class VariableRateLossyVAE(CodecBase):
         self._plans = {}
         self._cur_lmb = None
         self.timing = {} if os.environ.get('LVAE_TIMING') else None      # host-side phase timers (debug)
-        # independent encoder branches on a second HIP stream (see SIDE_STREAM_MAX_PIXELS, _EncPlan); LVAE_SIDE_STREAMS=0: A/B switch, same bits
-        self.side_streams = os.environ.get('LVAE_SIDE_STREAMS', '1') == '1'
+        # independent encoder branches on a second HIP stream (see SIDE_STREAM_MAX_PIXELS, _EncPlan); False gives the same bits
+        self.side_streams = True
 
     # ---- helpers
     def _dg(self) -> DiscretizedGaussian:

@@ -1,4 +1,4 @@
-"""Debug: qres34m 512x768 (seeded 'wide' weights) vs the CPU oracle, per-block flip counts.  LVAE_DW_CL=0 selects the earlier depthwise forms."""
+"""Debug: qres34m 512x768 (seeded 'wide' weights) vs the CPU oracle, per-block flip counts."""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, 'lossy-vae_amd')); sys.path.insert(0, os.path.join(REPO, 'tests'))

@@ -11,7 +11,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 
-if os.environ.get('LVAE_LIB'):            # A/B against another build of the native library (tools/r5_rans_mps.sh)
+if os.environ.get('LVAE_LIB'):            # A/B against another build of the native library
     from lvae import _native
     _native.LIB_PATH = os.path.abspath(os.environ['LVAE_LIB'])
 

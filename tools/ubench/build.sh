@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds the micro-benchmarks / in-kernel timeline harnesses next to their sources (binaries are git-ignored; they travel to the
+# Builds the micro-benchmarks next to their sources (binaries are git-ignored; they travel to the
 # GPU box with the gpurun snapshot).   bash tools/ubench/build.sh [name ...]
 cd "$(dirname "$0")"
 names=("$@"); [ ${#names[@]} -eq 0 ] && names=($(ls *.hip | sed 's/\.hip$//'))

@@ -1,6 +1,6 @@
 // lds_slot_probe.hip -- round 6: which values of HW_REG_LDS_ALLOC (id 6) the three co-resident 48 KB workgroups of a CU see, and in which
-// order the dispatcher fills the chip (is workgroup b's layer on its CU = (b / 8) / 32 ?).  Needed by the three-phase stagger study of
-// gemm_h2p (tools/r6_stagger3.sh): a workgroup must know which of its CU's slots it occupies.
+// order the dispatcher fills the chip (is workgroup b's layer on its CU = (b / 8) / 32 ?).  Needed by a three-phase stagger of gemm_h2p:
+// a workgroup must know which of its CU's slots it occupies.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

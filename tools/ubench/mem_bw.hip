@@ -1,6 +1,6 @@
 // mem_bw.hip -- what the chip sustains for plain streaming stores, loads and both at once (16 B per lane, whole 128-B lines per 8 lanes,
 // grid-stride over a buffer far larger than the 256 MB Infinity Cache), and for LDS-DMA loads from a workgroup whose other wave is
-// storing: the numbers behind "a GEMM's result stores cost their bandwidth, not their latency" (csrc/gemm_h2q.hip).
+// storing: the numbers behind "a GEMM's result stores cost their bandwidth, not their latency".
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
