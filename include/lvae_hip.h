@@ -378,6 +378,21 @@ int lvae_dequantize_f32(const int32_t* sym, const float* pm, float* zhat, int B,
 int lvae_prior_sample_f32(const float* prm, float* z, long M, int zdim, int ldz, float t, unsigned long long seed,
                           unsigned long long offset, void* stream);
 
+/* The sampler of one QRes-VAE latent block (qresvae/model.py QLatentBlockX.forward_uncond: cond_sample / uncond_sample / inpaint).
+ * Writes z rows [B*h*w][ldz] (pad columns [zdim, ldz) = 0).  Inside the box rows [r0, r1) x columns [c0, c1) of the h x w map -- and
+ * everywhere when lat == NULL -- an element is drawn exactly as lvae_prior_sample_f32 draws it (same arithmetic, counter offset +
+ * m*zdim + c): a full box equals lvae_prior_sample_f32 bit for bit.  Outside the box the given latent lat, NCHW (B, zdim, h, w), is
+ * copied verbatim: an empty box (r0 == r1) is its NHWC transpose. */
+int lvae_latent_sample_box_f32(const float* prm, const float* lat, float* z, int B, int h, int w, int zdim, int ldz, int r0, int r1,
+                               int c0, int c1, float t, unsigned long long seed, unsigned long long offset, void* stream);
+
+/* GaussianNLLOutputNet.sample (qresvae/model.py:44-57, continuous mode) + process_output of qres34m_lossless: raw as for
+ * lvae_lossless_params_f32 ([B*H*W][6], mean c0..2 | log-scale c0..2); for every (b, c, y, x) of the NCHW output, counter offset + its
+ * raster index: out = clamp(mean + (exp(ls)*t)*N(0,1), -1, 1)*0.5 + 0.5 (Philox4x32-10 variates of lvae_prior_sample_f32).  t = 0 gives
+ * clamp(mean)*0.5 + 0.5 exactly.  status (optional): LVAE_STATUS_NONFINITE_IMAGE when a sample is NaN / inf before the clamp. */
+int lvae_pixel_sample_f32(const float* raw, float* out, int B, int H, int W, float t, unsigned long long seed, unsigned long long offset,
+                          int* status, void* stream);
+
 /* GaussianNLLOutputNet coding parameters of qres34m_lossless (qresvae/model.py:69-94).  raw = the fused conv_mean | conv_scale
  * output after PixelShuffle, NHWC [B*H*W][6] (mean c0..2, log-scale c0..2), H x W = image size.  For every (b, c, y, x) in the
  * coder's NCHW raster order, with bin = 1/127.5 and the reference's fp32 operation order:
@@ -398,6 +413,11 @@ int lvae_lossless_output_f32(const int32_t* sym, const float* pm, float* out, lo
  * coder's NCHW raster order; out_nats (double[B]) must be zeroed by the caller. */
 int lvae_gaussian_nll_f32(const float* prm, const int32_t* sym, double* out_nats, float scale_bound, int B, int HW, int z,
                           int cdf_form, void* stream);
+
+/* The per-element terms of lvae_gaussian_nll_f32 (same arithmetic), stored instead of summed: out[(b*z + c)*HW + p] = -ln max(P, 1e-9)
+ * as float, NCHW -- the `kl` map of the reference's forward_get_latents (qresvae/model.py:257-282 in eval mode). */
+int lvae_gaussian_nll_map_f32(const float* prm, const int32_t* sym, float* out, float scale_bound, int B, int HW, int z, int cdf_form,
+                              void* stream);
 
 /* y = gelu_erf(x) elementwise: the exact-erf GELU used by every fused epilogue, exposed for numerics tests. */
 int lvae_gelu_f32(const float* x, float* y, long n, void* stream);

@@ -384,6 +384,28 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// Variates of counter `ctr`: a standard normal (Box-Muller on the first two words) and a U(-0.5, 0.5) (third word).  Shared by
+// every sampler, so a draw depends on (seed, counter) alone.
+__device__ __forceinline__ void philox_variates(uint64_t seed, uint64_t ctr, float& nrm, float& uni) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    const float u1 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1)
+    const float u2 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    nrm = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+    uni = ((float)(r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f) - 0.5f;
+}
+
+// One latent element drawn from the prior (qresvae/model.py forward_uncond, qarv/model.py:98-100): z = pm + pv*N(0,1)*t + U*t,
+// pv = exp(softplus(lv + 2.3) - 2.3).  Every latent sampler calls this, so they agree bit for bit on a shared counter.
+__device__ __forceinline__ float prior_draw(float mean, float lv, float t, uint64_t seed, uint64_t ctr) {
+    const float xs = lv + 2.3f;
+    const float sp = xs > 20.0f ? xs : log1pf(expf(xs));
+    const float pv = expf(sp - 2.3f);
+    float nrm, uni;
+    philox_variates(seed, ctr, nrm, uni);
+    return mean + pv * nrm * t + uni * t;
+}
+
 __global__ void prior_sample_kernel(const float* __restrict__ prm, float* __restrict__ z, long total, int zdim, int ldz, float t,
                                     uint64_t seed, uint64_t offset) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;     // e = m*ldz + c
@@ -391,19 +413,32 @@ __global__ void prior_sample_kernel(const float* __restrict__ prm, float* __rest
     const long m = e / ldz;
     const int c = (int)(e - m * ldz);
     if (c >= zdim) { z[e] = 0.f; return; }
-    const float mean = prm[m * 2 * zdim + c];
-    const float lv = prm[m * 2 * zdim + zdim + c];
-    const float xs = lv + 2.3f;
-    const float sp = xs > 20.0f ? xs : log1pf(expf(xs));
-    const float pv = expf(sp - 2.3f);
-    const uint64_t ctr = offset + (uint64_t)(m * zdim + c);
-    uint32_t r[4];
-    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const float u1 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1)
-    const float u2 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float nrm = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-    const float uni = ((float)(r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f) - 0.5f;
-    z[e] = mean + pv * nrm * t + uni * t;
+    z[e] = prior_draw(prm[m * 2 * zdim + c], prm[m * 2 * zdim + zdim + c], t, seed, offset + (uint64_t)(m * zdim + c));
+}
+
+// Pixel draw of GaussianNLLOutputNet.sample (qresvae/model.py:44-57, continuous mode) + process_output: x = mean + (exp(ls)*t)*N(0,1)
+// in the reference's operation order, then clamp(x, -1, 1)*0.5 + 0.5.  raw is the conv_mean | conv_scale map after PixelShuffle, NHWC
+// [B*HW][6]; out (and the counter, offset + e) in NCHW raster order.  t = 0 gives clamp(mean)*0.5 + 0.5 exactly.
+__global__ void pixel_sample_kernel(const float* __restrict__ raw, float* __restrict__ out, long total, int HW, float t, uint64_t seed,
+                                    uint64_t offset, int* __restrict__ status) {
+#pragma clang fp contract(off)
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;     // e = (b*3 + c)*HW + p
+    if (e >= total) return;
+    const long bc = e / HW;
+    const int p = (int)(e - bc * HW);
+    const long b = bc / 3;
+    const int c = (int)(bc - b * 3);
+    const float* r = raw + (b * HW + p) * 6;
+    float nrm, uni;
+    philox_variates(seed, offset + (uint64_t)e, nrm, uni);
+    float s = expf(r[3 + c]);
+    s = s * t;
+    float x = s * nrm;
+    x = r[c] + x;
+    if (status && !(fabsf(x) <= 3.4028234664e38f)) atomicOr(status, LVAE_STATUS_NONFINITE_IMAGE);
+    x = fminf(fmaxf(x, -1.0f), 1.0f);
+    x = x * 0.5f;
+    out[e] = x + 0.5f;
 }
 
 // ------------------------------------------------------------------------------------------------ entropy parameters
@@ -539,10 +574,63 @@ __global__ __launch_bounds__(256) void dequantize_kernel(const int32_t* __restri
     }
 }
 
+// One latent block's z rows [B*HW][ldz] for sampling (qresvae/model.py forward_uncond): inside the box rows [r0, r1) x columns
+// [c0, c1) of the h x w map -- or everywhere when no latent is given -- drawn by prior_draw with counter offset + m*zdim + c (the
+// counters of prior_sample_kernel); outside it the given latent `lat` (NCHW (B, zdim, h, w)) copied.  Pad columns [zdim, ldz) are 0.
+// The NCHW read goes through the LDS transpose of dequantize_kernel: 64 pixels x 16 channels per workgroup.
+__global__ __launch_bounds__(256) void latent_sample_box_kernel(const float* __restrict__ prm, const float* __restrict__ lat,
+                                                                float* __restrict__ zout, int HW, int w, int zdim, int ldz, int r0,
+                                                                int r1, int c0b, int c1b, float t, uint64_t seed, uint64_t offset) {
+    __shared__ float tile[CT_CH * CT_LD];
+    const int b = blockIdx.z, p0 = blockIdx.x * CT_PIX, np = (HW - p0) < CT_PIX ? (HW - p0) : CT_PIX;
+    const long m0 = (long)b * HW + p0;
+    const int c0 = blockIdx.y * CT_CH;
+    const int zc = (ldz - c0) < CT_CH ? (ldz - c0) : CT_CH;
+    if (lat) {                                                     // uniform over the launch
+        for (int j = threadIdx.x; j < zc * CT_PIX; j += 256) {
+            const int cl = j / CT_PIX, pl = j - cl * CT_PIX;
+            if (pl < np && c0 + cl < zdim) tile[cl * CT_LD + pl] = lat[((long)b * zdim + c0 + cl) * HW + p0 + pl];
+        }
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < np * zc; i += 256) {
+        const int pl = i / zc, c = c0 + (i - pl * zc);
+        const long m = m0 + pl;
+        float v = 0.f;
+        if (c < zdim) {
+            const int p = p0 + pl, y = p / w, x = p - y * w;
+            if (!lat || (y >= r0 && y < r1 && x >= c0b && x < c1b))
+                v = prior_draw(prm[m * 2 * zdim + c], prm[m * 2 * zdim + zdim + c], t, seed, offset + (uint64_t)(m * zdim + c));
+            else
+                v = tile[(c - c0) * CT_LD + pl];
+        }
+        zout[m * ldz + c] = v;
+    }
+}
+
 // Eval-mode rate estimate (qarv/model.py:95-96; CompressAI GaussianConditional._likelihood): per latent element
 // P = Phi((.5-|v|)/s) - Phi((-.5-|v|)/s), v = zhat - mean = the integer symbol, s = max(exp(softplus(x+2.3)-2.3), bound),
 // P = max(P, 1e-9); accumulates sum(-ln P) per image (nats) in fp64.  Phi in fp32 as the reference: erf form for
 // DiscretizedGaussian (underflows to exactly 0 in the tails), erfc form for stock GaussianConditional.
+// ln P of one latent element (the per-element arithmetic of gaussian_nll_kernel and gaussian_nll_map_kernel).
+__device__ __forceinline__ float gaussian_logp(float lv, int32_t sym, float bound, int cdf_form) {
+    const float xs = lv + 2.3f;
+    const float sp = xs > 20.0f ? xs : log1pf(expf(xs));
+    const float s = fmaxf(expf(sp - 2.3f), bound);
+    const float v = fabsf((float)sym);
+    const float a = (0.5f - v) / s, d = (-0.5f - v) / s;
+    float up, lo;
+    if (cdf_form == 0) {
+        up = 0.5f * (1.0f + lvae_erff(a * 0.70710678118654752440f));
+        lo = 0.5f * (1.0f + lvae_erff(d * 0.70710678118654752440f));
+    } else {
+        up = 0.5f * erfcf(-0.70710678118654752440f * a);
+        lo = 0.5f * erfcf(-0.70710678118654752440f * d);
+    }
+    const float P = fmaxf(up - lo, 1e-9f);
+    return logf(P);
+}
+
 __global__ __launch_bounds__(256) void gaussian_nll_kernel(const float* __restrict__ prm, const int32_t* __restrict__ sym,
                                                            double* __restrict__ out, float bound, long per_image, int HW,
                                                            int z, int cdf_form) {
@@ -552,22 +640,7 @@ __global__ __launch_bounds__(256) void gaussian_nll_kernel(const float* __restri
         const long p = e / z;                    // pixel within the image
         const int c = (int)(e - p * z);
         const long m = (long)b * HW + p;
-        const float lv = prm[m * 2 * z + z + c];
-        const float xs = lv + 2.3f;
-        const float sp = xs > 20.0f ? xs : log1pf(expf(xs));
-        const float s = fmaxf(expf(sp - 2.3f), bound);
-        const float v = fabsf((float)sym[((long)b * z + c) * HW + p]);
-        const float a = (0.5f - v) / s, d = (-0.5f - v) / s;
-        float up, lo;
-        if (cdf_form == 0) {
-            up = 0.5f * (1.0f + lvae_erff(a * 0.70710678118654752440f));
-            lo = 0.5f * (1.0f + lvae_erff(d * 0.70710678118654752440f));
-        } else {
-            up = 0.5f * erfcf(-0.70710678118654752440f * a);
-            lo = 0.5f * erfcf(-0.70710678118654752440f * d);
-        }
-        const float P = fmaxf(up - lo, 1e-9f);
-        acc -= (double)logf(P);
+        acc -= (double)gaussian_logp(prm[m * 2 * z + z + c], sym[((long)b * z + c) * HW + p], bound, cdf_form);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
@@ -575,6 +648,19 @@ __global__ __launch_bounds__(256) void gaussian_nll_kernel(const float* __restri
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(out + b, ws[0] + ws[1] + ws[2] + ws[3]);
+}
+
+// The same per element, stored: out[(b*z + c)*HW + p] = -ln P (NCHW, the `kl` map of the reference's forward_get_latents).
+__global__ __launch_bounds__(256) void gaussian_nll_map_kernel(const float* __restrict__ prm, const int32_t* __restrict__ sym,
+                                                               float* __restrict__ out, float bound, long total, int HW, int z,
+                                                               int cdf_form) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const long bc = e / HW;
+    const int p = (int)(e - bc * HW);
+    const long b = bc / z;
+    const int c = (int)(bc - b * z);
+    out[e] = -gaussian_logp(prm[(b * HW + p) * 2 * z + z + c], sym[e], bound, cdf_form);
 }
 
 __global__ void bias_expand_kernel(const float* __restrict__ bias, float* __restrict__ out, long total4, int C4) {
@@ -776,6 +862,15 @@ extern "C" int lvae_gaussian_nll_f32(const float* prm, const int32_t* sym, doubl
     return (int)hipGetLastError();
 }
 
+extern "C" int lvae_gaussian_nll_map_f32(const float* prm, const int32_t* sym, float* out, float scale_bound, int B, int HW, int z,
+                                         int cdf_form, void* stream) {
+    if (!prm || !sym || !out || B <= 0 || HW <= 0 || z <= 0 || (cdf_form != 0 && cdf_form != 1)) return -22;
+    const long total = (long)B * HW * z;
+    hipLaunchKernelGGL(gaussian_nll_map_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, prm, sym, out,
+                       scale_bound, total, HW, z, cdf_form);
+    return (int)hipGetLastError();
+}
+
 extern "C" int lvae_bias_expand_f32(const float* bias, float* out, long M, int C, void* stream) {
     if (!bias || !out || M <= 0 || C <= 0 || (C & 3)) return -22;
     const long total4 = M * (C / 4);
@@ -839,6 +934,25 @@ extern "C" int lvae_prior_sample_f32(const float* prm, float* z, long M, int zdi
     return (int)hipGetLastError();
 }
 
+extern "C" int lvae_latent_sample_box_f32(const float* prm, const float* lat, float* z, int B, int h, int w, int zdim, int ldz, int r0,
+                                          int r1, int c0, int c1, float t, unsigned long long seed, unsigned long long offset,
+                                          void* stream) {
+    if (!prm || !z || B <= 0 || B > 65535 || h <= 0 || w <= 0 || zdim <= 0 || ldz < zdim || (long)h * w > 0x7fffffffL) return -22;
+    const int HW = h * w;
+    hipLaunchKernelGGL(latent_sample_box_kernel, dim3((unsigned)((HW + CT_PIX - 1) / CT_PIX), (unsigned)((ldz + CT_CH - 1) / CT_CH), (unsigned)B),
+                       dim3(256), 0, (hipStream_t)stream, prm, lat, z, HW, w, zdim, ldz, r0, r1, c0, c1, t, (uint64_t)seed, (uint64_t)offset);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_pixel_sample_f32(const float* raw, float* out, int B, int H, int W, float t, unsigned long long seed,
+                                     unsigned long long offset, int* status, void* stream) {
+    if (!raw || !out || B <= 0 || H <= 0 || W <= 0 || (long)H * W > 0x7fffffffL) return -22;
+    const long total = (long)B * 3 * H * W;
+    hipLaunchKernelGGL(pixel_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, raw, out, total, H * W,
+                       t, (uint64_t)seed, (uint64_t)offset, status);
+    return (int)hipGetLastError();
+}
+
 extern "C" int lvae_lossless_params_f32(const float* raw, const float* im, float* pm, uint8_t* idx, int32_t* sym, const float* table,
                                         int n_scales, float bound, int B, int H, int W, int* status, void* stream) {
     if (!raw || !pm || !idx || !table || n_scales <= 0 || n_scales > 256 || B <= 0 || H <= 0 || W <= 0 || (im && !sym)) return -22;
@@ -869,5 +983,5 @@ extern "C" int lvae_stream_order(void* from_stream, void* to_stream, void* ev) {
     return (int)hipStreamWaitEvent((hipStream_t)to_stream, (hipEvent_t)ev, 0);
 }
 
-extern "C" int lvae_abi_version(void) { return 24; }
+extern "C" int lvae_abi_version(void) { return 25; }
 extern "C" const char* lvae_build_info(void) { return "liblvae_hip gfx950 (MI355X) fp32-MFMA; hipcc " __VERSION__; }

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblvae_hip.so')
-ABI_VERSION = 24
+ABI_VERSION = 25
 _lib = None
 
 
@@ -109,6 +109,9 @@ SIGNATURES = {
     'lvae_lossless_output_f32': (_i, [_vp, _vp, _vp, C.c_long, _vp, _vp]),
     'lvae_prior_sample_f32': (_i, [_vp, _vp, C.c_long, _i, _i, C.c_float, C.c_ulonglong, C.c_ulonglong, _vp]),
     'lvae_gaussian_nll_f32': (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    'lvae_latent_sample_box_f32': (_i, [_vp, _vp, _vp] + [_i] * 9 + [C.c_float, C.c_ulonglong, C.c_ulonglong, _vp]),
+    'lvae_pixel_sample_f32': (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_ulonglong, _vp, _vp]),
+    'lvae_gaussian_nll_map_f32': (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
     'lvae_bias_expand_f32': (_i, [_vp, _vp, _l, _i, _vp]),
     'lvae_event_create': (_vp, []),
     'lvae_event_destroy': (_i, [_vp]),

@@ -11,7 +11,13 @@ As for QARV, the module tree only owns parameters; the network runs as native HI
                                      sources), c2/c3 as A_CONV3 (or plain for k<3), GELU fused in each epilogue
   z_proj (:235-239)               -> A_CONV3/plain GEMM + GELU, then 1x1 GEMM with the residual add into the feature
   prior/posterior heads, coder    -> lvae_prior_index_f32 / lvae_quantize_f32 / lvae_dequantize_f32 + host rANS
+
+The generative surface (:578-638) replays the same plans block by block: `cond_sample` / `uncond_sample` replace each block's
+dequantize launch by lvae_latent_sample_box_f32 (prior draw, given latent, or both split by a paint box) and the lossless model's pixel
+decoder by lvae_pixel_sample_f32; `forward_get_latents` takes each block's -ln P map (lvae_gaussian_nll_map_f32) right behind its
+quantize launch; `inpaint` alternates the two.
 """
+import ctypes
 import math
 import pickle
 
@@ -25,6 +31,22 @@ from ...utils import coding
 from ..base import CodecBase, PREC_CODE, on_model_device
 from ..entropy_coding import DiscretizedGaussian, log_spaced_table, rans_decode_streams, rans_encode_streams
 from ..qarv.model import UpParams, _conv
+
+
+def box_slices(box, h, w):
+    """(r0, r1, c0, c1) of the reference's `slice(round(y1*h), round(y2*h))`, `slice(round(x1*w), round(x2*w))` on an h x w map, with
+    Python's round (ties to even) and slicing rules (negative / out-of-range bounds); an empty range gives r0 == r1 (or c0 == c1)."""
+    x1, y1, x2, y2 = box
+    rows, cols = range(h)[round(y1 * h):round(y2 * h)], range(w)[round(x1 * w):round(x2 * w)]
+    if len(rows) == 0 or len(cols) == 0:
+        return (0, 0, 0, 0)
+    return (rows.start, rows.stop, cols.start, cols.stop)
+
+
+def latent_box(box, h, w):
+    """The paint box on one latent map (QLatentBlockX.forward_uncond): None -- the given latent is kept whole -- on a map with
+    min(h, w) == 1, else box_slices."""
+    return None if min(h, w) == 1 else box_slices(box, h, w)
 
 
 # ----------------------------------------------------------------------------------------------- parameter holders
@@ -264,6 +286,7 @@ class _QresPlan(Plan):
         self.w16_k32 = pk.bf16_map('f16x2k32') if self.prec == 4 else None
         self.lat_shapes, self.idx_off, self.sym_off, self.cuts = [], [], [], []
         self.qcuts, self.prm_bufs, self.qm_bufs, self.zhat_bufs, self.zhat_ld = [], [], [], [], []   # test access (CodecBase._trace_blocks)
+        self.pm_bufs, self.lat_hw = [], []          # per latent block: prior means [B*h*w][z], map size (h, w) (the generative API)
         nH, nW = H // 64, W // 64
         # latent I/O sizes: resolution doubles at every rate-2 upsample of the top-down path
         tot, s = 0, 1
@@ -348,6 +371,7 @@ class _QresPlan(Plan):
             pm = self.new(M * z)
             ioff = sum(a * b for a, b in self.lat_shapes) * B
             self.lat_shapes.append((z, h * w)); self.idx_off.append(ioff); self.sym_off.append(ioff)
+            self.pm_bufs.append(pm); self.lat_hw.append((h, w))
             self.add(lib.lvae_prior_index_f32, (prm.data_ptr(), pm.data_ptr(), ptr(self.idx_all, ioff), pk.scale_table.data_ptr(),
                                                 pk.scale_table.numel(), pk.scale_bound, B, h * w, z, self.status_ptr()), p + '.prior_index')
             zhat = self.buf('zhat', M * zp)
@@ -387,6 +411,7 @@ class _QresPlan(Plan):
             self.px_sym_host = torch.empty(npx, dtype=torch.int32).pin_memory()
             self.px_idx_host = torch.empty(npx, dtype=torch.uint8).pin_memory()
             self.px_sym_np, self.px_idx_np = self.px_sym_host.numpy(), self.px_idx_host.numpy()
+            self.px_params_op = len(self.ops)               # sampling replays up to here and draws the pixels from px_raw instead
             self.add(lib.lvae_lossless_params_f32, (raw.data_ptr(), self.im.data_ptr() if encode else None, self.px_pm.data_ptr(),
                                                     self.px_idx.data_ptr(), self.px_sym.data_ptr() if encode else None,
                                                     pk.out_scale_table.data_ptr(), pk.out_scale_table.numel(), pk.out_scale_bound,
@@ -466,6 +491,7 @@ class HierarchicalVAE(CodecBase):
         self.max_stride = config['max_stride']
         self.register_buffer('_dummy', torch.zeros(1), persistent=False)
         self.compressing = False
+        self.num_latents = sum(1 for b in self.decoder.dec_blocks if b.kind == 'qlb')
         self._packed, self._plans = None, {}
         self._init_codec_base()
 
@@ -708,32 +734,146 @@ class HierarchicalVAE(CodecBase):
         return [dict(symbols=sym[o:o + B * z * hw].reshape(B, z, hw).copy(), indexes=idx[o:o + B * z * hw].reshape(B, z, hw).copy())
                 for o, (z, hw) in zip(pl.sym_off, pl.lat_shapes)]
 
+    # ---- the generative API (reference qresvae/model.py:578-638): sampling, latents, inpainting.  Latents and pixels are drawn by the
+    # device Philox stream (lvae_latent_sample_box_f32 / lvae_pixel_sample_f32), not by torch's RNG: a call is reproducible by its
+    # `seed`, and at temperature 0 (no noise) its result is the reference's.
     @torch.no_grad()
     @on_model_device
-    def cond_sample(self, latents, nhw_repeat=None, temprature=1.0, paint_box=None):
-        """Decoder output for GIVEN latents (reference qresvae/model.py:591-603 with every latent supplied: forward_with_latents
-        :403-417 uses them verbatim): latents[i] is a (B, z_i, h_i, w_i) tensor, e.g. what the encoder quantised.  Sampling the
-        missing latents of a partial list (temprature, paint_box) belongs to the reference's generation demos, not to the
-        compress / decompress path, and is not offered."""
-        assert paint_box is None and all(z is not None for z in latents), 'cond_sample: every latent must be given'
-        B, _, nH, nW = latents[0].shape
+    def cond_sample(self, latents, nhw_repeat=None, temprature=1.0, paint_box=None, *, seed=None, return_latents=False):
+        """Decoder output for a list of latents (:591-603, forward_with_latents :403-417, QLatentBlockX.forward_uncond :284-315).
+        latents[i] is a (B, z_i, h_i, w_i) tensor (e.g. a `forward_get_latents` z) or None:
+          None                    -> the block is drawn from the prior, z = pm + pv*t*N(0,1) + t*U(-1/2, 1/2);
+          given, paint_box None   -> used verbatim;
+          given, paint_box        -> drawn inside the box (x1, y1, x2, y2) in [0, 1] units, rows round(y1*h):round(y2*h) and columns
+                                     round(x1*w):round(x2*w) of the block's map, kept outside it; a map with min(h, w) == 1 is kept whole.
+        nhw_repeat = (B, h, w) of the top latent map; None takes it from latents[0].  The lossless model draws its pixels too
+        (GaussianNLLOutputNet.sample, continuous mode).  seed: the Philox key (default: a fresh one from torch's CPU generator, so
+        torch.manual_seed makes calls reproducible).  return_latents=True (not in the reference) also returns the latents used.
+        With nothing drawn, or t = 0, a NaN / inf raises NonFiniteError; otherwise the sample is returned whatever it holds."""
+        if nhw_repeat is None:
+            assert latents[0] is not None, 'nhw_repeat should be provided when latents[0] is None'
+            B, _, nH, nW = latents[0].shape
+        else:
+            B, nH, nW = nhw_repeat
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self._ensure_tables()
         self._prepare()
         pl = self._plan('dec', B, nH * 64, nW * 64)
-        assert len(latents) == len(pl.lat_shapes)
-        lo = 0
-        for li, cut in enumerate(pl.cuts[:len(pl.lat_shapes)]):
+        return self._sample(pl, latents, float(temprature), paint_box, int(seed), 0, return_latents)
+
+    @torch.no_grad()
+    def uncond_sample(self, nhw_repeat, temprature=1.0, *, seed=None, return_latents=False):
+        """Generate new images from the prior alone (:578-589); nhw_repeat = (B, h, w) of the top latent map (images of 64h x 64w)."""
+        return self.cond_sample([None] * self.num_latents, nhw_repeat, temprature, seed=seed, return_latents=return_latents)
+
+    def _ensure_tables(self):
+        """The plans' prior heads index into the scale table, which compress_mode() builds (a fixed log-spaced table, no weights
+        involved); the reference's generative calls do not need it, so they build it here when it is missing."""
+        if self._dg().scale_table.numel() == 0:
+            self.compress_mode()
+
+    def _sample(self, pl, latents, t, paint_box, seed, salt, return_latents):
+        """Replay the decode plan block by block; each block's dequantize launch (at `cuts[li]`) is replaced by the box sampler writing
+        the same z buffer.  Counters: latent block li at li << 40, the lossless model's pixels at L << 40, plus `salt`."""
+        L, B = len(pl.lat_shapes), pl.B
+        assert len(latents) == L, f'{len(latents)} latents for {L} latent blocks'
+        st = ctypes.c_void_p(torch.cuda.current_stream(pl.device).cuda_stream)
+        lo, used, drawn, keep = 0, [], False, []
+        for li in range(L):
+            cut = pl.cuts[li]
             pl.run(lo, cut)
             z, hw = pl.lat_shapes[li]
-            ld, M = pl.zhat_ld[li], B * hw
-            assert tuple(latents[li].shape[:2]) == (B, z) and latents[li][0, 0].numel() == hw, f'latent {li}: {tuple(latents[li].shape)}'
-            zt = latents[li].to(pl.device, torch.float32).reshape(B, z, hw).permute(0, 2, 1).reshape(M, z)
-            zh = pl.zhat_bufs[li][:M * ld].view(M, ld)
-            zh.zero_()
-            zh[:, :z].copy_(zt)
-            lo = cut + 1                                 # the launch at `cut` is this block's dequantize: skipped
-        assert not pl.lossless, 'cond_sample: lossy models only (the lossless output net codes pixels, not a latent)'
-        pl.run(lo, None)
+            h, w = pl.lat_hw[li]
+            lat = latents[li]
+            if lat is None:
+                box, lat_ptr = (0, h, 0, w), None
+            else:
+                assert tuple(lat.shape) == (B, z, h, w), f'latent {li}: shape {tuple(lat.shape)}, expected {(B, z, h, w)}'
+                lat = lat.to(pl.device, torch.float32).contiguous()
+                keep.append(lat)
+                box = latent_box(paint_box, h, w) if paint_box is not None else None
+                box, lat_ptr = (box or (0, 0, 0, 0)), lat.data_ptr()
+            drawn = drawn or (box[1] > box[0] and box[3] > box[2])
+            rc = pl.lib.lvae_latent_sample_box_f32(pl.prm_bufs[li].data_ptr(), lat_ptr, pl.zhat_bufs[li].data_ptr(), B, h, w, z,
+                                                   pl.zhat_ld[li], *box, t, seed, (li << 40) + salt, st)
+            _native.check(rc, 'lvae_latent_sample_box_f32')
+            lo = cut + 1
+            if return_latents:
+                ld = pl.zhat_ld[li]
+                zs = pl.zhat_bufs[li][:B * hw * ld].view(B, hw, ld)[:, :, :z]
+                used.append(zs.permute(0, 2, 1).reshape(B, z, h, w).clone())
+        if pl.lossless:
+            H, W = pl.out.shape[2:]
+            pl.run(lo, pl.px_params_op)
+            rc = pl.lib.lvae_pixel_sample_f32(pl.px_raw.data_ptr(), pl.out.data_ptr(), B, H, W, t, seed, (L << 40) + salt,
+                                              pl.status_ptr(), st)
+            _native.check(rc, 'lvae_pixel_sample_f32')
+            drawn = True
+        else:
+            pl.run(lo, None)
         pl.fetch_status()
         torch.cuda.current_stream(pl.device).synchronize()
-        pl.raise_if_flagged(where='in cond_sample()')
-        return pl.out.clone()
+        if drawn and t != 0.0:
+            # random numbers of the model's own scale (with untrained weights the deeper blocks' prior scales are astronomically large):
+            # whatever they lead to is the sample, as in the reference -- clear the word, no error
+            pl.status.zero_(); pl.status_host.zero_()
+        else:
+            pl.raise_if_flagged(where='in cond_sample()')
+        out = pl.out.clone()
+        return (out, used) if return_latents else out
+
+    @torch.no_grad()
+    @on_model_device
+    def forward_get_latents(self, im):
+        """The eval-mode forward pass of the reference (:605-611, QLatentBlockX.forward_train :257-282): per latent block
+        dict(z=(B, z, h, w) quantised latent symbols + pm, kl=(B, z, h, w) -ln P of each element under the prior, CompressAI
+        GaussianConditional likelihood: scale bound 0.11, erfc form, P >= 1e-9).  Runs the encode plan up to the last latent."""
+        B, _, H, W = im.shape
+        assert H % self.max_stride == 0 and W % self.max_stride == 0, f'{im.shape=}'
+        self._ensure_tables()
+        pk = self._prepare()
+        pl = self._plan('enc', B, H, W)
+        pl.im.view(B, 3, H, W).copy_(im)
+        st = ctypes.c_void_p(torch.cuda.current_stream(pl.device).cuda_stream)
+        kls, lo = [], 0
+        for li, cut in enumerate(pl.qcuts):
+            pl.run(lo, cut)
+            lo = cut
+            # prm is scratch shared by every block: the block's kl map is taken right behind its quantize launch
+            z, hw = pl.lat_shapes[li]
+            kl = torch.empty(B, z, *pl.lat_hw[li], device=pl.device)
+            rc = pl.lib.lvae_gaussian_nll_map_f32(pl.prm_bufs[li].data_ptr(), ptr(pl.sym_all, pl.sym_off[li]), kl.data_ptr(),
+                                                  pk.scale_bound, B, hw, z, 1, st)
+            _native.check(rc, 'lvae_gaussian_nll_map_f32')
+            kls.append(kl)
+        pl.fetch_status()
+        torch.cuda.current_stream(pl.device).synchronize()
+        pl.raise_if_flagged(where='in forward_get_latents()')
+        out = []
+        for li, (z, hw) in enumerate(pl.lat_shapes):
+            o = pl.sym_off[li]
+            sym = pl.sym_all[o:o + B * z * hw].view(B, z, hw).float()
+            pm = pl.pm_bufs[li].view(B, hw, z).permute(0, 2, 1)
+            out.append(dict(z=(sym + pm).reshape(B, z, *pl.lat_hw[li]), kl=kls[li]))
+        return out
+
+    @torch.no_grad()
+    @on_model_device
+    def inpaint(self, im, paint_box, steps=1, temprature=1.0, *, seed=None):
+        """Inpainting (:613-638): `steps` rounds of forward_get_latents -> cond_sample(paint_box) on the image with the box replaced by
+        the previous round's clamped sample.  Returns the last whole sample (not a composite).  Round s draws at counter salt s << 48."""
+        _, _, H, W = im.shape
+        r0, r1, c0, c1 = box_slices(paint_box, H, W)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        im = im.to(self._dummy.device)
+        im_input = im.clone()
+        for s in range(steps):
+            latents = [st['z'] for st in self.forward_get_latents(im_input)]
+            pl = self._plan('dec', im.shape[0], H, W)
+            im_sample = self._sample(pl, latents, float(temprature), paint_box, int(seed), s << 48, False)
+            im_sample.clamp_(min=0, max=1)
+            im_input = im.clone()
+            im_input[:, :, r0:r1, c0:c1] = im_sample[:, :, r0:r1, c0:c1]
+        return im_sample
