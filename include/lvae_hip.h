@@ -237,7 +237,8 @@ int lvae_gemm_num_configs(void);      /* number of selectable tile configuration
 enum {
     LVAE_OP_GEMM = 1, LVAE_OP_DWCONV_LN_F32, LVAE_OP_DWCONV_LN_H2, LVAE_OP_DWCONV_LN_BF16, LVAE_OP_DWCONV_LN_Q8, LVAE_OP_STEM_F32, LVAE_OP_STEM_BF16,
     LVAE_OP_BIAS_EXPAND_F32, LVAE_OP_BIAS_EXPAND_BF16, LVAE_OP_PRIOR_INDEX, LVAE_OP_QUANTIZE, LVAE_OP_DEQUANTIZE, LVAE_OP_GAUSSIAN_NLL,
-    LVAE_OP_LOSSLESS_PARAMS, LVAE_OP_LOSSLESS_OUTPUT, LVAE_OP_MLP_H2F, LVAE_OP_MLP_SK, LVAE_OP_PRIOR_INDEX_SK, LVAE_OP_QUANTIZE_SK, LVAE_OP_ORDER
+    LVAE_OP_LOSSLESS_PARAMS, LVAE_OP_LOSSLESS_OUTPUT, LVAE_OP_MLP_H2F, LVAE_OP_MLP_SK, LVAE_OP_PRIOR_INDEX_SK, LVAE_OP_QUANTIZE_SK,
+    LVAE_OP_GAUSSIAN_NLL_CHAN, LVAE_OP_RD_IMAGE, LVAE_OP_PIXEL_NLL, LVAE_OP_ORDER
 };
 typedef struct { int kind; int side; void* p[8]; long i[6]; double f[2]; } lvae_op;
 #define LVAE_TRACE_MAGIC 1985229328.0      /* lvae_decode_blocks: seconds[1] of a timeline request */
@@ -418,6 +419,34 @@ int lvae_gaussian_nll_f32(const float* prm, const int32_t* sym, double* out_nats
  * as float, NCHW -- the `kl` map of the reference's forward_get_latents (qresvae/model.py:257-282 in eval mode). */
 int lvae_gaussian_nll_map_f32(const float* prm, const int32_t* sym, float* out, float scale_bound, int B, int HW, int z, int cdf_form,
                               void* stream);
+
+/* ---- eval-mode statistics of model.forward (ABI 26).  Deterministic: no float atomics, every sum in a fixed order (fp64 per thread,
+ * fixed xor tree per wave, waves in order), so two calls on the same input return the same bits.  Each output is overwritten.
+ * The two image entry points split each image into LVAE_EVAL_CHUNKS pixel ranges fixed by H*W alone (one workgroup each, all images at
+ * once), write per-chunk fp64 partials to the caller's `ws` (double[B][LVAE_EVAL_CHUNKS][2], scratch) and add them in chunk order in a
+ * second launch. */
+#define LVAE_EVAL_CHUNKS 256
+
+/* Per-channel latent rate: out[b*z + c] = sum over the h*w map of -ln max(P, 1e-9), each term the float lvae_gaussian_nll_map_f32 stores
+ * (same arithmetic), added in fp64.  prm NHWC [B*HW][2z] as for lvae_gaussian_nll_f32, sym NCHW (the coder's raster order).  The sum over
+ * c is the image's rate in nats; the per-channel values are the reference's `_stats_log['*_channels']` before the bits conversion. */
+int lvae_gaussian_nll_chan_f32(const float* prm, const int32_t* sym, double* out, float scale_bound, int B, int HW, int z, int cdf_form,
+                               void* stream);
+
+/* Lossy reconstruction and distortion.  raw = the decoder's final conv output BEFORE the clamp, NHWC [B*H*W][3]; im NCHW in [0, 1].
+ * im_hat (NCHW) = fminf(fmaxf(v, -1), 1)*0.5f + 0.5f -- the expression of the ST_IMAGE store, so it equals the codec's output bit for
+ * bit.  sums[2b] = sum (v - (im - 0.5)*2)^2 (the reference's unclamped mse_loss(x_hat, x_target)), sums[2b + 1] = sum (im_hat - im)^2
+ * (for PSNR).  status (optional): LVAE_STATUS_NONFINITE_IMAGE when a v is NaN / inf. */
+int lvae_rd_image_f32(const float* raw, const float* im, float* im_hat, double* sums, double* ws, int B, int H, int W, int* status,
+                      void* stream);
+
+/* Lossless pixel likelihood: GaussianNLLOutputNet.forward_loss (qresvae/model.py:24-38) with gaussian_log_prob_mass (entropy_coding.py:
+ * 18-49) in fp32: logscale = softplus(l + 16) - 16, s = exp(logscale), bin 1/127.5, x = (im - 0.5)*2, P = Phi((x + bin/2 - m)/s) -
+ * Phi((x - bin/2 - m)/s); log P = log(max(P, 1e-8)) where P > 1e-6, else the Gaussian log-density + log(bin).  The mean m is NOT rounded.
+ * raw6 as for lvae_lossless_params_f32 ([B*H*W][6], mean c0..2 | log-scale c0..2).  im_hat = clamp(m, -1, 1)*0.5 + 0.5 (NCHW);
+ * sums[2b] = sum -log P, sums[2b + 1] = sum (im_hat - im)^2.  status (optional): LVAE_STATUS_NONFINITE_IMAGE for a NaN / inf mean or term. */
+int lvae_pixel_nll_f32(const float* raw6, const float* im, float* im_hat, double* sums, double* ws, int B, int H, int W, int* status,
+                       void* stream);
 
 /* y = gelu_erf(x) elementwise: the exact-erf GELU used by every fused epilogue, exposed for numerics tests. */
 int lvae_gelu_f32(const float* x, float* y, long n, void* stream);

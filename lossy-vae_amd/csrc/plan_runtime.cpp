@@ -80,6 +80,18 @@ extern "C" int lvae_run_ops(const lvae_op* ops, int n, void* stream, void* side_
                 rc = lvae_quantize_sk_f32((const float*)p[0], (int)i[0], (const float*)p[1], (float*)p[2], (const float*)p[3], (int32_t*)p[4], (float*)p[5],
                                           (int)i[1], (int)i[2], (int)i[3], (int)i[4], (int*)p[6], st);
                 break;
+            case LVAE_OP_GAUSSIAN_NLL_CHAN:
+                rc = lvae_gaussian_nll_chan_f32((const float*)p[0], (const int32_t*)p[1], (double*)p[2], (float)f[0], (int)i[0], (int)i[1], (int)i[2],
+                                                (int)i[3], st);
+                break;
+            case LVAE_OP_RD_IMAGE:
+                rc = lvae_rd_image_f32((const float*)p[0], (const float*)p[1], (float*)p[2], (double*)p[3], (double*)p[4], (int)i[0], (int)i[1], (int)i[2],
+                                       (int*)p[5], st);
+                break;
+            case LVAE_OP_PIXEL_NLL:
+                rc = lvae_pixel_nll_f32((const float*)p[0], (const float*)p[1], (float*)p[2], (double*)p[3], (double*)p[4], (int)i[0], (int)i[1], (int)i[2],
+                                        (int*)p[5], st);
+                break;
             case LVAE_OP_ORDER:      // i[0] != 0: the side stream waits for the main stream (fork); else the main stream for the side stream (join)
                 rc = i[0] ? lvae_stream_order(stream, side_stream, p[0]) : lvae_stream_order(side_stream, stream, p[0]);
                 break;

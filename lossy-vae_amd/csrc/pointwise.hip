@@ -663,6 +663,185 @@ __global__ __launch_bounds__(256) void gaussian_nll_map_kernel(const float* __re
     out[e] = -gaussian_logp(prm[(b * HW + p) * 2 * z + z + c], sym[e], bound, cdf_form);
 }
 
+// ------------------------------------------------------------------------------------------------ eval-mode statistics (model.forward)
+// Deterministic reductions: every element goes to a fixed thread, every thread adds its elements in a fixed order in fp64, a wave adds its
+// lanes by a fixed xor tree, and one thread adds the waves' partials in wave order.  No float atomics: the bits depend on the launch shape alone.
+
+// Fixed-order sum of one fp64 value per thread of a workgroup of NT threads; the result is valid in thread 0.
+template <int NT>
+__device__ __forceinline__ double wg_sum_f64(double v, double* ws /* [NT / 64] */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < NT / 64; ++w) s += ws[w];
+    return s;
+}
+
+// Per (image, channel) sum of -ln P over the latent map (gaussian_logp: the value lvae_gaussian_nll_map_f32 stores, element for element).
+// One workgroup of NT threads per (channel, image); thread t takes pixels t, t + NT, ...: the NCHW symbols are read along pixels
+// (coalesced), the NHWC log-scale parameters as a gather of one float per pixel row.  Not the LDS (pixel, channel) tile of
+// lvae_latent_sample_box_f32: a tile walks the map in pieces, and a fixed-order sum over pieces needs either one workgroup per channel
+// group looping over the whole map (16 channels per workgroup: ~1500 serial elements per thread on the stride-4 maps of a 512 x 768
+// batch, 25 % of a qres34m forward when measured) or a partials buffer this entry point does not take.  The gathered lines are shared by
+// the z workgroups of an image through L2 (the latent maps are <= 0.4 MB per image).  NT = 256 on maps up to 8192 pixels, 1024 above
+// (a rule in HW alone, so the sum order does not depend on the batch).
+template <int NT>
+__global__ __launch_bounds__(NT) void gaussian_nll_chan_kernel(const float* __restrict__ prm, const int32_t* __restrict__ sym,
+                                                               double* __restrict__ out, float bound, int HW, int z, int cdf_form) {
+    __shared__ double ws[NT / 64];
+    const int c = blockIdx.x, b = blockIdx.y;
+    const int32_t* sc = sym + ((long)b * z + c) * HW;
+    const float* lv = prm + (long)b * HW * 2 * z + z + c;
+    double acc = 0.0;
+    for (int p = threadIdx.x; p < HW; p += NT) acc += (double)(-gaussian_logp(lv[(long)p * 2 * z], sc[p], bound, cdf_form));
+    acc = wg_sum_f64<NT>(acc, ws);
+    if (threadIdx.x == 0) out[(long)b * z + c] = acc;
+}
+
+// The two image kernels below: grid (LVAE_EVAL_CHUNKS, B) of EV_WG threads.  Chunk k of an image covers pixels [k*cs, min((k+1)*cs, HW)),
+// cs = ceil(HW / LVAE_EVAL_CHUNKS) -- a map fixed by HW alone -- and writes its two fp64 partial sums to ws[(b*CHUNKS + k)*2 + {0, 1}];
+// eval_sums_kernel then adds an image's partials in chunk order (lane j: chunks j, j + 64, ..., then the fixed xor tree).
+constexpr int EV_WG = 256;
+
+__device__ __forceinline__ void eval_chunk(int HW, int& p_lo, int& p_hi) {
+    const int cs = (HW + LVAE_EVAL_CHUNKS - 1) / LVAE_EVAL_CHUNKS;
+    p_lo = blockIdx.x * cs;
+    p_hi = (HW - p_lo) < cs ? HW : p_lo + cs;
+}
+
+__global__ __launch_bounds__(64) void eval_sums_kernel(const double* __restrict__ ws, double* __restrict__ sums) {
+    const int b = blockIdx.x;
+    const double* w = ws + (long)b * LVAE_EVAL_CHUNKS * 2;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        double s = 0.0;
+        for (int k = threadIdx.x; k < LVAE_EVAL_CHUNKS; k += 64) s += w[2 * k + q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (threadIdx.x == 0) sums[2 * b + q] = s;
+    }
+}
+
+// Lossy models: raw = the decoder's final conv output before the clamp, NHWC [B*HW][3].  im_hat (NCHW) = clamp(raw)*0.5 + 0.5 -- the
+// ST_IMAGE store's expression -- and the fp64 partial sums of (raw - x)^2, x = (im - 0.5)*2 (the reference's mse_loss(x_hat, x_target)),
+// and of (im_hat - im)^2.
+__global__ __launch_bounds__(EV_WG) void rd_image_kernel(const float* __restrict__ raw, const float* __restrict__ im,
+                                                         float* __restrict__ im_hat, double* __restrict__ part, int HW,
+                                                         int* __restrict__ status) {
+    __shared__ double ws[EV_WG / 64];
+    const int b = blockIdx.y;
+    int p_lo, p_hi;
+    eval_chunk(HW, p_lo, p_hi);
+    const float* r = raw + (long)b * HW * 3;
+    const float* x = im + (long)b * 3 * HW;
+    float* o = im_hat + (long)b * 3 * HW;
+    double se = 0.0, sq = 0.0;
+    bool bad = false;
+    for (int p0 = p_lo + threadIdx.x; p0 < p_hi; p0 += 4 * EV_WG) {       // four pixels per step: their twelve loads in flight together
+        float vv[4][3], tt[4][3];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int p = p0 + u * EV_WG;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                vv[u][c] = p < p_hi ? r[(long)p * 3 + c] : 0.0f;
+                tt[u][c] = p < p_hi ? x[(long)c * HW + p] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int p = p0 + u * EV_WG;
+            if (p >= p_hi) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = vv[u][c], t = tt[u][c];
+                bad |= !(fabsf(v) <= 3.4028234664e38f);
+                const float h = fminf(fmaxf(v, -1.0f), 1.0f) * 0.5f + 0.5f;
+                o[(long)c * HW + p] = h;
+                const float d = v - (t - 0.5f) * 2.0f, e = h - t;
+                se += (double)d * (double)d;
+                sq += (double)e * (double)e;
+            }
+        }
+    }
+    if (status && bad) atomicOr(status, LVAE_STATUS_NONFINITE_IMAGE);
+    se = wg_sum_f64<EV_WG>(se, ws);
+    __syncthreads();
+    sq = wg_sum_f64<EV_WG>(sq, ws);
+    if (threadIdx.x == 0) {
+        double* w = part + ((long)b * LVAE_EVAL_CHUNKS + blockIdx.x) * 2;
+        w[0] = se;
+        w[1] = sq;
+    }
+}
+
+// Lossless model: GaussianNLLOutputNet.forward_loss (qresvae/model.py:24-38, entropy_coding.py:18-49) in fp32 with torch's operation
+// order: logscale = softplus(l + 16) - 16 (threshold 20), s = exp(logscale), x = (im - 0.5)*2, bin b = 1/127.5,
+// P = Phi((x + b/2 - m)/s) - Phi((x - b/2 - m)/s) with Phi(v) = 0.5*(1 + erf((v - m)*(1/s)/sqrt 2));
+// log P = P > 1e-6 ? log(max(P, 1e-8)) : -(x - m)^2/(2 s^2) - log s - log sqrt(2 pi) + log b.  The mean is not rounded (that belongs to
+// the coder).  raw6 = px_raw, NHWC [B*HW][6] (mean c0..2 | log-scale c0..2).  im_hat = clamp(m)*0.5 + 0.5 and the fp64 partial sums
+// of -log P and of (im_hat - im)^2.
+__global__ __launch_bounds__(EV_WG) void pixel_nll_kernel(const float* __restrict__ raw, const float* __restrict__ im,
+                                                          float* __restrict__ im_hat, double* __restrict__ part, int HW,
+                                                          int* __restrict__ status) {
+#pragma clang fp contract(off)
+    __shared__ double ws[EV_WG / 64];
+    const int b = blockIdx.y;
+    int p_lo, p_hi;
+    eval_chunk(HW, p_lo, p_hi);
+    const float* r6 = raw + (long)b * HW * 6;
+    const float* xi = im + (long)b * 3 * HW;
+    float* o = im_hat + (long)b * 3 * HW;
+    const float hb = (float)(0.5 * (1.0 / 127.5));
+    const float log_bin = (float)-4.848116364598481;                      // math.log(1/127.5)
+    const float log_sqrt_2pi = (float)0.9189385332046727;                 // math.log(math.sqrt(2 * math.pi))
+    const float sqrt2 = 1.41421356237309504880f;                           // math.sqrt(2), the divisor of torch's Normal.cdf
+    double nll = 0.0, sq = 0.0;
+    bool bad = false;
+    for (int p = p_lo + threadIdx.x; p < p_hi; p += EV_WG) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float m = r6[(long)p * 6 + c];
+            float ls = r6[(long)p * 6 + 3 + c] + 16.0f;
+            ls = ls > 20.0f ? ls : log1pf(expf(ls));
+            ls = ls - 16.0f;
+            const float s = expf(ls);
+            const float inv = 1.0f / s;
+            const float t = xi[(long)c * HW + p];
+            const float x = (t - 0.5f) * 2.0f;
+            const float up = 0.5f * (1.0f + erff((((x + hb) - m) * inv) / sqrt2));
+            const float lo = 0.5f * (1.0f + erff((((x - hb) - m) * inv) / sqrt2));
+            const float P = up - lo;
+            float lp;
+            if (P > 1e-6f) {
+                lp = logf(fmaxf(P, 1e-8f));
+            } else {
+                const float d = x - m;
+                lp = -(d * d) / (2.0f * (s * s)) - logf(s) - log_sqrt_2pi;
+                lp = lp + log_bin;
+            }
+            bad |= !(fabsf(m) <= 3.4028234664e38f) || !(fabsf(lp) <= 3.4028234664e38f);
+            const float h = fminf(fmaxf(m, -1.0f), 1.0f) * 0.5f + 0.5f;
+            o[(long)c * HW + p] = h;
+            const float e = h - t;
+            nll -= (double)lp;
+            sq += (double)e * (double)e;
+        }
+    }
+    if (status && bad) atomicOr(status, LVAE_STATUS_NONFINITE_IMAGE);
+    nll = wg_sum_f64<EV_WG>(nll, ws);
+    __syncthreads();
+    sq = wg_sum_f64<EV_WG>(sq, ws);
+    if (threadIdx.x == 0) {
+        double* w = part + ((long)b * LVAE_EVAL_CHUNKS + blockIdx.x) * 2;
+        w[0] = nll;
+        w[1] = sq;
+    }
+}
+
 __global__ void bias_expand_kernel(const float* __restrict__ bias, float* __restrict__ out, long total4, int C4) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total4) return;
@@ -871,6 +1050,36 @@ extern "C" int lvae_gaussian_nll_map_f32(const float* prm, const int32_t* sym, f
     return (int)hipGetLastError();
 }
 
+extern "C" int lvae_gaussian_nll_chan_f32(const float* prm, const int32_t* sym, double* out, float scale_bound, int B, int HW, int z,
+                                          int cdf_form, void* stream) {
+    if (!prm || !sym || !out || B <= 0 || B > 65535 || HW <= 0 || z <= 0 || (cdf_form != 0 && cdf_form != 1)) return -22;
+    if (HW <= 8192)
+        hipLaunchKernelGGL(gaussian_nll_chan_kernel<256>, dim3((unsigned)z, (unsigned)B), dim3(256), 0, (hipStream_t)stream, prm, sym, out,
+                           scale_bound, HW, z, cdf_form);
+    else
+        hipLaunchKernelGGL(gaussian_nll_chan_kernel<1024>, dim3((unsigned)z, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, prm, sym, out,
+                           scale_bound, HW, z, cdf_form);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_rd_image_f32(const float* raw, const float* im, float* im_hat, double* sums, double* ws, int B, int H, int W, int* status,
+                                 void* stream) {
+    if (!raw || !im || !im_hat || !sums || !ws || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long)H * W * 6 > 0x7fffffffL) return -22;
+    hipLaunchKernelGGL(rd_image_kernel, dim3(LVAE_EVAL_CHUNKS, (unsigned)B), dim3(EV_WG), 0, (hipStream_t)stream, raw, im, im_hat, ws, H * W,
+                       status);
+    hipLaunchKernelGGL(eval_sums_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, ws, sums);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_pixel_nll_f32(const float* raw6, const float* im, float* im_hat, double* sums, double* ws, int B, int H, int W, int* status,
+                                  void* stream) {
+    if (!raw6 || !im || !im_hat || !sums || !ws || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long)H * W * 6 > 0x7fffffffL) return -22;
+    hipLaunchKernelGGL(pixel_nll_kernel, dim3(LVAE_EVAL_CHUNKS, (unsigned)B), dim3(EV_WG), 0, (hipStream_t)stream, raw6, im, im_hat, ws, H * W,
+                       status);
+    hipLaunchKernelGGL(eval_sums_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, ws, sums);
+    return (int)hipGetLastError();
+}
+
 extern "C" int lvae_bias_expand_f32(const float* bias, float* out, long M, int C, void* stream) {
     if (!bias || !out || M <= 0 || C <= 0 || (C & 3)) return -22;
     const long total4 = M * (C / 4);
@@ -983,5 +1192,5 @@ extern "C" int lvae_stream_order(void* from_stream, void* to_stream, void* ev) {
     return (int)hipStreamWaitEvent((hipStream_t)to_stream, (hipEvent_t)ev, 0);
 }
 
-extern "C" int lvae_abi_version(void) { return 25; }
+extern "C" int lvae_abi_version(void) { return 26; }
 extern "C" const char* lvae_build_info(void) { return "liblvae_hip gfx950 (MI355X) fp32-MFMA; hipcc " __VERSION__; }

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblvae_hip.so')
-ABI_VERSION = 25
+ABI_VERSION = 26
 _lib = None
 
 
@@ -64,7 +64,8 @@ class EncBlock(C.Structure):
 OP_KINDS = {name: k + 1 for k, name in enumerate([
     'lvae_gemm_f32', 'lvae_dwconv_ln_f32', 'lvae_dwconv_ln_h2', 'lvae_dwconv_ln_bf16', 'lvae_dwconv_ln_q8', 'lvae_stem_f32', 'lvae_stem_bf16',
     'lvae_bias_expand_f32', 'lvae_bias_expand_bf16', 'lvae_prior_index_f32', 'lvae_quantize_f32', 'lvae_dequantize_f32',
-    'lvae_gaussian_nll_f32', 'lvae_lossless_params_f32', 'lvae_lossless_output_f32', 'lvae_mlp_h2f', 'lvae_mlp_sk', 'lvae_prior_index_sk_f32', 'lvae_quantize_sk_f32'])}
+    'lvae_gaussian_nll_f32', 'lvae_lossless_params_f32', 'lvae_lossless_output_f32', 'lvae_mlp_h2f', 'lvae_mlp_sk', 'lvae_prior_index_sk_f32', 'lvae_quantize_sk_f32',
+    'lvae_gaussian_nll_chan_f32', 'lvae_rd_image_f32', 'lvae_pixel_nll_f32'])}
 OP_ORDER = len(OP_KINDS) + 1
 
 TRACE_MAGIC = 1985229328.0       # LVAE_TRACE_MAGIC
@@ -72,6 +73,7 @@ A_PLAIN, A_PATCH2, A_CONV3 = 0, 1, 2
 STATUS_RANGE, STATUS_NONFINITE_PRIOR, STATUS_NONFINITE_LATENT, STATUS_NONFINITE_IMAGE = 1, 2, 4, 8      # LVAE_STATUS_* (status word)
 EPI_BIAS, EPI_BIAS_GELU, EPI_GAMMA_RES, EPI_RES = 0, 1, 2, 3
 ST_ROWMAJOR, ST_SHUFFLE, ST_IMAGE = 0, 2, 3
+EVAL_CHUNKS = 256                # LVAE_EVAL_CHUNKS: lvae_rd_image_f32 / lvae_pixel_nll_f32 take ws = double[B][EVAL_CHUNKS][2]
 
 _vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
 SIGNATURES = {
@@ -112,6 +114,9 @@ SIGNATURES = {
     'lvae_latent_sample_box_f32': (_i, [_vp, _vp, _vp] + [_i] * 9 + [C.c_float, C.c_ulonglong, C.c_ulonglong, _vp]),
     'lvae_pixel_sample_f32': (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_ulonglong, _vp, _vp]),
     'lvae_gaussian_nll_map_f32': (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    'lvae_gaussian_nll_chan_f32': (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    'lvae_rd_image_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'lvae_pixel_nll_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'lvae_bias_expand_f32': (_i, [_vp, _vp, _l, _i, _vp]),
     'lvae_event_create': (_vp, []),
     'lvae_event_destroy': (_i, [_vp]),

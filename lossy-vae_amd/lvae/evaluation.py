@@ -13,7 +13,7 @@ from tempfile import gettempdir
 import torch
 
 from .paths import known_datasets
-from .utils.coding import pil_to_tensor01
+from .utils.coding import crop_divisible_by, pil_to_tensor01
 
 
 def _list_images(dataset):
@@ -76,6 +76,47 @@ def imcoding_evaluate(model, dataset, progress=False):
         for k, v in stats.items():      # timm AverageMeter: running sum / count
             sums[k] += v
     return {k: v / n for k, v in sums.items()}
+
+
+class AverageMeter:
+    """timm.utils.AverageMeter: running sum / count of the values it is updated with (tensors stay tensors)."""
+
+    def __init__(self):
+        self.val, self.sum, self.count, self.avg = 0, 0, 0, 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+@torch.no_grad()
+def image_self_evaluate(model, dataset, progress=True):
+    """The reference's validation loop (evaluation.py:70-107): for every image of sorted(rglob('*.*')) -- center-cropped to multiples of
+    model.max_stride when the model has one (crop_divisible_by) -- call model(im) and average each returned statistic over the
+    images (AverageMeter).  No entropy coding: the statistics are the model's forward() ones."""
+    from PIL import Image
+    device = next(model.parameters()).device
+    img_paths = _list_images(dataset)
+    pbar = img_paths
+    if progress:
+        from tqdm import tqdm
+        pbar = tqdm(img_paths, ascii=True)
+    all_image_stats = defaultdict(AverageMeter)
+    for impath in pbar:
+        img = Image.open(impath)
+        if hasattr(model, 'max_stride'):
+            img = crop_divisible_by(img, div=model.max_stride)
+        im = pil_to_tensor01(img).unsqueeze_(0).to(device=device)
+        stats = model(im)
+        assert isinstance(stats, dict), f'{type(stats)=}. expected a dict.'
+        for k, v in stats.items():
+            all_image_stats[k].update(v)
+        if progress:
+            msg = ', '.join([f'{k}={v:.3f}' for k, v in stats.items()])
+            pbar.set_description(f'image {impath.stem}: {msg}')
+    return {k: meter.avg for k, meter in all_image_stats.items()}
 
 
 def shard_paths(img_paths, rank, world):

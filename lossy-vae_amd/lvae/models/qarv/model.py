@@ -16,6 +16,7 @@ import math
 import os
 import struct
 import time
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -166,10 +167,13 @@ class _Packed:
             elif m.kind == 'up':
                 w = m[0].weight.reshape(m.cout * m.rate ** 2, m.cin)
                 b = m[0].bias
+                r2 = m.rate ** 2
                 if m.cout > 3:      # NHWC pixel-shuffle store wants columns ordered (i, j, c)
-                    r2 = m.rate ** 2
                     w = w.reshape(m.cout, r2, m.cin).permute(1, 0, 2).reshape(r2 * m.cout, m.cin)
                     b = b.reshape(m.cout, r2).t().reshape(-1)
+                else:               # the eval decode plan's raw NHWC store of the final conv: the same rows in that order (same bits per element)
+                    put(p + '.w_raw', w.reshape(m.cout, r2, m.cin).permute(1, 0, 2).reshape(r2 * m.cout, m.cin))
+                    put(p + '.b_raw', b.reshape(m.cout, r2).t().reshape(-1))
                 put(p + '.w', w); put(p + '.b', b)
             elif m.kind == 'vrlv':
                 for sub in ('resnet_front', 'resnet_end', 'posterior0', 'posterior1', 'posterior2'):
@@ -272,10 +276,16 @@ class _NetPlan(Plan):
         self.gemm(A0=h.data_ptr(), K0=hid, M=M, N=C, Wt=pk.p(p + '.fc2_w'), bias=pk.p(p + '.fc2_b'),
                   gamma=pk.p(p + '.gamma'), res=x, ldres=C, out=out, epi=_native.EPI_GAMMA_RES, a_h2=pre2, ksplit=S2, label=p + '.fc2')
 
-    def upsample(self, p, m, x, out, H, W):
+    def upsample(self, p, m, x, out, H, W, raw=False):
+        """raw (final conv only): the launch of the ST_IMAGE store with the raw NHWC fp32 store of the pre-clamp output instead."""
         pk = self.pk
         M = self.B * H * W
         final = m.cout <= 3
+        if raw:
+            assert final
+            self.gemm(A0=x, K0=m.cin, M=M, N=m.cout * m.rate ** 2, Wt=pk.p(p + '.w_raw'), bias=pk.p(p + '.b_raw'), out=out,
+                      store=_native.ST_SHUFFLE, r=m.rate, H=H, W=W, out_bf16=0, label=p + '.up_raw')
+            return
         self.gemm(A0=x, K0=m.cin, M=M, N=m.cout * m.rate ** 2, Wt=pk.p(p + '.w'), bias=pk.p(p + '.b'), out=out,
                   store=_native.ST_IMAGE if final else _native.ST_SHUFFLE, r=m.rate, H=H, W=W, label=p + '.up')
 
@@ -316,7 +326,8 @@ class _NetPlan(Plan):
                   ldres=m.width, out=f, epi=_native.EPI_RES, a_bf16=0, label=p + '.z_proj')
         self.cnx(p + '.resnet_end', m.resnet_end, f, f, H, W)
 
-    def alloc_latent_io(self, nH, nW):
+    def alloc_latent_io(self, nH, nW, host=True):
+        """Device symbol / index buffers of every latent block; host=True adds the coder's pinned host copies."""
         B = self.B
         total, s = 0, 1
         # latent resolution per block follows the top-down path: starts at (nH,nW), doubles at each upsample
@@ -330,15 +341,18 @@ class _NetPlan(Plan):
         self.n_sym = total * B
         self.sym_all = self.new(self.n_sym, torch.int32)
         self.idx_all = self.new(self.n_sym, torch.uint8)
-        self.sym_host = torch.empty(self.n_sym, dtype=torch.int32).pin_memory()
-        self.idx_host = torch.empty(self.n_sym, dtype=torch.uint8).pin_memory()
-        self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
+        if host:
+            self.sym_host = torch.empty(self.n_sym, dtype=torch.int32).pin_memory()
+            self.idx_host = torch.empty(self.n_sym, dtype=torch.uint8).pin_memory()
+            self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
 
 
 class _EncPlan(_NetPlan):
     """forward_end2end(mode='compress') (qarv/model.py:294-315) for B images of size HxW."""
 
-    def __init__(self, model, pk, B, H, W, with_bits=False):
+    def __init__(self, model, pk, B, H, W, with_bits=False, chan_bits=False):
+        """with_bits ('encb'): each block's rate per image in `nats` ([block][image], accumulated); chan_bits ('ence', the encoder half of
+        forward()): per image and channel in `kl_chan` (fp64 [L][B][z_l] at chan_off[l], lvae_gaussian_nll_chan_f32: deterministic)."""
         super().__init__(model, pk, B)
         lib = self.lib
         self.im = self.new(B * 3 * H * W)
@@ -351,8 +365,11 @@ class _EncPlan(_NetPlan):
         # path leaves stride 16 and runs on the side stream under the stride-32 / 64 stages of both paths, whose launches (M = 96 ... 384
         # rows per image) leave the chip almost empty (round 5; same kernels, same inputs, same bits)
         hoisted = {}                                    # dec_blocks index -> buffer holding posterior0's output
-        self.alloc_latent_io(H // 64, W // 64)
+        self.alloc_latent_io(H // 64, W // 64, host=not chan_bits)         # forward()'s symbols never leave the device
         self.nats = self.new(model.num_latents * B, torch.float64) if with_bits else None   # [block][image] sum(-ln P)
+        if chan_bits:
+            self.kl_chan = self.new(B * sum(m.zdim for m in model.dec_blocks if m.kind == 'vrlv'), torch.float64)
+            self.chan_off = []
         feats = {}
         tapped = set()
         h, w = H, W
@@ -436,6 +453,11 @@ class _EncPlan(_NetPlan):
                     li = len(self.sym_off) - 1
                     self.add(lib.lvae_gaussian_nll_f32, (self.bufs['prm'].data_ptr(), ptr(self.sym_all, ioff), ptr(self.nats, li * B),
                                                          pk.scale_bound, B, h * w, z, 0), p + '.nll')
+                if chan_bits:
+                    co = B * sum(zz for zz, _ in self.lat_shapes[:-1])
+                    self.chan_off.append(co)
+                    self.add(lib.lvae_gaussian_nll_chan_f32, (self.bufs['prm'].data_ptr(), ptr(self.sym_all, ioff), ptr(self.kl_chan, co),
+                                                              pk.scale_bound, B, h * w, z, 0), p + '.nll_chan')
                 self.fuse_and_end(p, m, f.data_ptr(), zhat.data_ptr(), h, w)
             elif m.kind == 'cnx':
                 self.cnx(p, m, f.data_ptr(), f.data_ptr(), h, w)
@@ -470,12 +492,14 @@ class _EncPlan(_NetPlan):
 
 
 class _DecPlan(_NetPlan):
-    """decompress() (qarv/model.py:531-557): 9 GPU segments separated by host rANS decodes."""
+    """decompress() (qarv/model.py:531-557): 9 GPU segments separated by host rANS decodes.  evaluate ('evald', the decoder half of
+    forward()): the final conv stored raw (NHWC fp32 [B*H*W][3], `x_raw`) and lvae_rd_image_f32 against `im` -> `out` (im_hat), `rd_sums`
+    (fp64 [B][2]: sum (x_hat - x_target)^2, sum (im_hat - im)^2)."""
 
-    def __init__(self, model, pk, B, nH, nW):
+    def __init__(self, model, pk, B, nH, nW, evaluate=False):
         super().__init__(model, pk, B)
         lib = self.lib
-        self.alloc_latent_io_full(nH, nW)
+        self.alloc_latent_io_full(nH, nW, host=not evaluate)
         h, w = nH, nW
         width = model.dec_blocks[0].width
         f = self.new(B * h * w * width, self.adt)
@@ -502,15 +526,23 @@ class _DecPlan(_NetPlan):
             elif m.kind == 'up':
                 final = m.cout <= 3
                 nf = self.new(B * h * w * m.rate ** 2 * m.cout, torch.float32 if final else self.adt)
-                self.upsample(p, m, f.data_ptr(), nf.data_ptr(), h, w)
+                self.upsample(p, m, f.data_ptr(), nf.data_ptr(), h, w, raw=final and evaluate)
                 f = nf
                 h, w = h * m.rate, w * m.rate
-                if final:
+                if final and evaluate:
+                    self.x_raw, self.im, self.rd_sums = nf, self.new(B * 3 * h * w), self.new(B * 2, torch.float64)
+                    self.rd_ws = self.new(B * _native.EVAL_CHUNKS * 2, torch.float64)     # per-chunk partials of lvae_rd_image_f32
+                    im_hat = self.new(B * 3 * h * w)
+                    self.add(lib.lvae_rd_image_f32, (nf.data_ptr(), self.im.data_ptr(), im_hat.data_ptr(), self.rd_sums.data_ptr(),
+                                                     self.rd_ws.data_ptr(), B, h, w,
+                                                     self.status_ptr()), 'rd_image')
+                    self.out = im_hat.view(B, m.cout, h, w)
+                elif final:
                     self.out = nf.view(B, m.cout, h, w)
         assert self.out is not None
 
-    def alloc_latent_io_full(self, nH, nW):
-        self.alloc_latent_io(nH, nW)
+    def alloc_latent_io_full(self, nH, nW, host=True):
+        self.alloc_latent_io(nH, nW, host)
 
 
 # ----------------------------------------------------------------------------------------------- the model
@@ -615,6 +647,10 @@ class VariableRateLossyVAE(CodecBase):
                 pl = _EncPlan(self, pk, B, a, b)
             elif kind == 'encb':
                 pl = _EncPlan(self, pk, B, a, b, with_bits=True)
+            elif kind == 'ence':
+                pl = _EncPlan(self, pk, B, a, b, chan_bits=True)
+            elif kind == 'evald':
+                pl = _DecPlan(self, pk, B, a, b, evaluate=True)
             else:
                 pl = _DecPlan(self, pk, B, a, b)
             self._plans[key] = pl
@@ -865,6 +901,88 @@ class VariableRateLossyVAE(CodecBase):
                 bodies.append(f.read())
         out = self.decompress_batch(bodies)
         return [out[i:i + 1, :, :h, :w] for i, (h, w) in enumerate(heads)]
+
+    # ---- the eval-mode forward pass (reference qarv/model.py:258-363)
+    def sample_lmb(self, n):
+        """(:258-264) n lambdas drawn uniformly in lmb^(1/3) over lmb_range, with torch's RNG on the model device."""
+        low, high = self.lmb_range
+        p = 3.0
+        low, high = math.pow(low, 1 / p), math.pow(high, 1 / p)
+        transformed_lmb = low + (high - low) * torch.rand(n, device=self._dummy.device)
+        return torch.pow(transformed_lmb, exponent=p)
+
+    def expand_to_tensor(self, input_, n):
+        """(:266-273) a float / int / one-element tensor -> an (n,) tensor on the model device; an (n,) tensor as it is."""
+        assert isinstance(input_, (torch.Tensor, float, int)), f'{type(input_)=}'
+        if isinstance(input_, torch.Tensor) and (input_.numel() == 1):
+            input_ = input_.item()
+        if isinstance(input_, (float, int)):
+            input_ = torch.full(size=(n,), fill_value=float(input_), device=self._dummy.device)
+        assert input_.shape == (n,), f'{input_=}, {input_.shape=}'
+        return input_
+
+    @torch.no_grad()
+    @on_model_device
+    def forward(self, batch, lmb=None, return_rec=False):
+        """The reference's `model(batch, lmb)` (:317-363) without entropy coding: batch = a (B, 3, H, W) tensor or an (im, label) pair;
+        lmb = None (sample_lmb(B)), a float or a (B,) tensor.  Returns an OrderedDict: loss (0-d tensor on the model device,
+        mean of kl + lmb * mse), bppix, mse (mean((x_hat - x_target)^2) on the UNCLAMPED reconstruction, batch mean), psnr (from the
+        batch-mean MSE of im_hat) and im_hat (B, 3, H, W) when return_rec.
+        The plans take one lambda each: images that share a lambda run as one sub-batch ('ence' encode plan with the per-channel rate,
+        then the 'evald' decode plan fed with its symbols, the final conv stored raw + lvae_rd_image_f32), distinct lambdas as separate
+        sub-batches, and the results are put back in input order -- a batch with per-image lambdas gives the bits of per-image calls.
+        Eval-mode (quantised) statistics only: model.train() adds no training noise.  Deterministic: two calls on the same input (and
+        lambdas) return the same bits.  A NaN / inf raises NonFiniteError, an input outside [0, 1] AssertionError."""
+        im = batch[0] if isinstance(batch, (tuple, list)) else batch
+        im = im.to(self._dummy.device)
+        assert im.dim() == 4 and im.shape[1] == 3 and not im.requires_grad, f'{im.shape=}'
+        nB, imC, imH, imW = im.shape
+        assert (imH % self.max_stride == 0) and (imW % self.max_stride == 0), f'{im.shape=}'
+        if lmb is None:
+            lmb = self.sample_lmb(n=nB)
+        lmb = self.expand_to_tensor(lmb, n=nB)
+        self._prepare()
+        lv = [float(np.float32(v)) for v in lmb.tolist()]          # the plans' embedding is built from the fp32 value (_set_lmb)
+        groups = {}
+        for i, v in enumerate(lv):
+            groups.setdefault(v, []).append(i)
+        ndims = imC * imH * imW
+        kl = torch.empty(nB, dtype=torch.float64)
+        rd = torch.empty(nB, 2, dtype=torch.float64)
+        im_hat = torch.empty(nB, 3, imH, imW, device=self._dummy.device) if return_rec else None
+        for v, idx in groups.items():
+            n = len(idx)
+            sub = im if n == nB else im[torch.tensor(idx, device=im.device)]
+            self._set_lmb(v)
+            enc = self._plan('ence', n, imH, imW)
+            dec = self._plan('evald', n, imH // self.max_stride, imW // self.max_stride)
+            enc.im.view(n, 3, imH, imW).copy_(sub)
+            dec.im.view(n, 3, imH, imW).copy_(sub)
+            enc.run()
+            enc.fetch_status()
+            torch.cuda.current_stream(enc.device).synchronize()
+            enc.raise_if_flagged(where='in forward() (encoder)')
+            dec.sym_all.copy_(enc.sym_all)                          # the encoder stops at CompresionStopFlag: decode its symbols
+            dec.run()
+            dec.fetch_status()
+            torch.cuda.current_stream(dec.device).synchronize()
+            dec.raise_if_flagged(where='in forward() (decoder)')
+            kl_chan = enc.kl_chan.cpu()
+            nats = sum(kl_chan[o:o + n * z].view(n, z).sum(1) for o, (z, _) in zip(enc.chan_off, enc.lat_shapes))
+            kl[idx] = nats / ndims
+            rd[idx] = dec.rd_sums.view(n, 2).cpu()
+            if return_rec:
+                im_hat[idx] = dec.out
+        distortion = rd[:, 0] / ndims
+        lmb64 = torch.tensor(lv, dtype=torch.float64)
+        stats = OrderedDict()
+        stats['loss'] = (kl + lmb64 * distortion).mean(0).to(device=self._dummy.device, dtype=torch.float32)
+        stats['bppix'] = float(kl.mean(0)) * self.log2_e * imC
+        stats['mse'] = float(distortion.mean(0))
+        stats['psnr'] = -10 * math.log10(float(rd[:, 1].sum()) / (nB * ndims))
+        if return_rec:
+            stats['im_hat'] = im_hat
+        return stats
 
     # ---- coder-free paths (SURVEY.md 8(f) rows 1 and 3)
     @torch.no_grad()

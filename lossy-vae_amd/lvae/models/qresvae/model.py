@@ -20,6 +20,7 @@ quantize launch; `inpaint` alternates the two.
 import ctypes
 import math
 import pickle
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -215,6 +216,12 @@ class _Packed:
                     r2 = m.rate ** 2
                     w = w.reshape(m.cout, r2, m.cin).permute(1, 0, 2).reshape(r2 * m.cout, m.cin)
                     b = b.reshape(m.cout, r2).t().reshape(-1)
+                else:
+                    # the eval plan stores the final conv raw (before the clamp) as an NHWC map: the pixel-shuffle column order (i, j, c)
+                    # of the same rows -- every output element is the same dot product, so the same bits as the ST_IMAGE store
+                    r2 = m.rate ** 2
+                    put(p + '.w_raw', w.reshape(m.cout, r2, m.cin).permute(1, 0, 2).reshape(r2 * m.cout, m.cin))
+                    put(p + '.b_raw', b.reshape(m.cout, r2).t().reshape(-1))
                 put(p + '.w', w); put(p + '.b', b)
             elif m.kind == 'deconv':
                 # stride-2 transposed conv as ONE 3x3-gather GEMM with a PixelShuffle store: output pixel (2a+py, 2b+px) reads the
@@ -274,8 +281,13 @@ class _Packed:
 
 
 class _QresPlan(Plan):
-    def __init__(self, model, pk, B, H, W, encode):
+    def __init__(self, model, pk, B, H, W, encode, evaluate=False):
+        """encode: the encode plan ('enc'); evaluate (with encode): the eval plan of forward() ('eval') -- the encode plan with each
+        block's per-channel rate behind its quantize launch (kl_chan, fp64 [L][B][z_l] at chan_off[l]), and the distortion in place of
+        the coder's sinks: the lossy models' final conv stored raw + lvae_rd_image_f32, the lossless model's lvae_pixel_nll_f32 on the
+        out-net map (rd_sums, fp64 [B][2]; `out` = im_hat)."""
         super().__init__(pk.device)
+        evaluate = bool(evaluate and encode)
         lib, self.pk, self.B = self.lib, pk, B
         if model._prec == 'fp8':
             raise NotImplementedError("the 'fp8' mode (bf16 activation storage + MX-fp8 GEMMs, BASELINE config 5) is built for qarv_base")
@@ -296,10 +308,17 @@ class _QresPlan(Plan):
             elif not (m.kind == 'up' and m.cout <= 3):
                 s *= m.rate
         self.n_sym = tot * B
+        self.evaluate = evaluate
+        if evaluate:
+            self.kl_chan = self.new(B * sum(m.zdim for m in model.decoder.dec_blocks if m.kind == 'qlb'), torch.float64)
+            self.rd_sums = self.new(B * 2, torch.float64)
+            self.rd_ws = self.new(B * _native.EVAL_CHUNKS * 2, torch.float64)     # per-chunk partials of the distortion kernel
+            self.chan_off = []
         self.sym_all, self.idx_all = self.new(self.n_sym, torch.int32), self.new(self.n_sym, torch.uint8)
-        self.sym_host = torch.empty(self.n_sym, dtype=torch.int32).pin_memory()
-        self.idx_host = torch.empty(self.n_sym, dtype=torch.uint8).pin_memory()
-        self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
+        if not evaluate:            # the coder's host copies (the eval plan's symbols never leave the device)
+            self.sym_host = torch.empty(self.n_sym, dtype=torch.int32).pin_memory()
+            self.idx_host = torch.empty(self.n_sym, dtype=torch.uint8).pin_memory()
+            self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
         feats = {}
         if encode:
             self.im = self.new(B * 3 * H * W)
@@ -357,6 +376,18 @@ class _QresPlan(Plan):
             if m.kind == 'up':
                 nf = self.new(B * h * w * m.rate ** 2 * m.cout)
                 final = m.cout <= 3
+                if final and evaluate:
+                    # the ST_IMAGE launch below with the raw NHWC store (same tile and kernel: the choice depends on the shape alone)
+                    self.gemm(A0=f.data_ptr(), K0=m.cin, M=B * h * w, N=m.cout * m.rate ** 2, Wt=pk.p(p + '.w_raw'), bias=pk.p(p + '.b_raw'),
+                              out=nf.data_ptr(), store=_native.ST_SHUFFLE, r=m.rate, H=h, W=w, label=p + '.up_raw')
+                    h, w = h * m.rate, w * m.rate
+                    self.x_raw = nf                             # test access: the reconstruction before the clamp, NHWC [B*H*W][3]
+                    im_hat = self.new(B * 3 * h * w)
+                    self.add(lib.lvae_rd_image_f32, (nf.data_ptr(), self.im.data_ptr(), im_hat.data_ptr(), self.rd_sums.data_ptr(),
+                                                     self.rd_ws.data_ptr(), B, h, w,
+                                                     self.status_ptr()), 'rd_image')
+                    self.out = im_hat.view(B, 3, h, w)
+                    continue
                 self.gemm(A0=f.data_ptr(), K0=m.cin, M=B * h * w, N=m.cout * m.rate ** 2, Wt=pk.p(p + '.w'), bias=pk.p(p + '.b'),
                           out=nf.data_ptr(), store=_native.ST_IMAGE if final else _native.ST_SHUFFLE, r=m.rate, H=h, W=w, label=p + '.up')
                 f, h, w = nf, h * m.rate, w * m.rate
@@ -383,6 +414,11 @@ class _QresPlan(Plan):
                          p + '.quantize')
                 self.qm_bufs.append(qm)
                 self.qcuts.append(len(self.ops))
+                if evaluate:            # prm still holds this block's prior (scratch shared by every block)
+                    co = B * sum(zz for zz, _ in self.lat_shapes[:-1])
+                    self.chan_off.append(co)
+                    self.add(lib.lvae_gaussian_nll_chan_f32, (prm.data_ptr(), ptr(self.sym_all, ioff), ptr(self.kl_chan, co), pk.scale_bound,
+                                                              B, h * w, z, 1), p + '.nll_chan')
             else:
                 self.cuts.append(len(self.ops))
                 self.add(lib.lvae_dequantize_f32, (ptr(self.sym_all, ioff), pm.data_ptr(), zhat.data_ptr(), B, h * w, z, zp), p + '.dequantize')
@@ -405,6 +441,13 @@ class _QresPlan(Plan):
             self.px_raw = raw                               # test access: conv_mean | conv_scale after PixelShuffle, NHWC [B*H*W][6]
             self.gemm(A0=f.data_ptr(), K0=on.cin, M=B * h * w, N=6 * on.rate ** 2, Wt=pk.p('out_net.w'), bias=pk.p('out_net.b'),
                       out=raw.data_ptr(), store=_native.ST_SHUFFLE, r=on.rate, H=h, W=w, label='out_net.conv')
+            if evaluate:                # forward_loss: the pixel likelihood of the unrounded mean, no coder parameters
+                im_hat = self.new(B * 3 * H * W)
+                self.add(lib.lvae_pixel_nll_f32, (raw.data_ptr(), self.im.data_ptr(), im_hat.data_ptr(), self.rd_sums.data_ptr(),
+                                                  self.rd_ws.data_ptr(), B, H, W,
+                                                  self.status_ptr()), 'out_net.nll')
+                self.out = im_hat.view(B, 3, H, W)
+                return
             npx = B * 3 * H * W
             self.px_pm = self.new(npx)
             self.px_sym, self.px_idx = self.new(npx, torch.int32), self.new(npx, torch.uint8)
@@ -492,6 +535,7 @@ class HierarchicalVAE(CodecBase):
         self.register_buffer('_dummy', torch.zeros(1), persistent=False)
         self.compressing = False
         self.num_latents = sum(1 for b in self.decoder.dec_blocks if b.kind == 'qlb')
+        self._stats_log = dict()
         self._packed, self._plans = None, {}
         self._init_codec_base()
 
@@ -532,7 +576,7 @@ class HierarchicalVAE(CodecBase):
         key = (kind, B, H, W, group, self._prec)
         pl = self._plans.get(key)
         if pl is None:
-            pl = _QresPlan(self, self._prepare(), B, H, W, encode=(kind == 'enc'))
+            pl = _QresPlan(self, self._prepare(), B, H, W, encode=(kind in ('enc', 'eval')), evaluate=(kind == 'eval'))
             self._plans[key] = pl
         return pl
 
@@ -733,6 +777,64 @@ class HierarchicalVAE(CodecBase):
         sym, idx = pl.sym_all.cpu().numpy(), pl.idx_all.cpu().numpy()
         return [dict(symbols=sym[o:o + B * z * hw].reshape(B, z, hw).copy(), indexes=idx[o:o + B * z * hw].reshape(B, z, hw).copy())
                 for o, (z, hw) in zip(pl.sym_off, pl.lat_shapes)]
+
+    # ---- the eval-mode forward pass (reference qresvae/model.py:517-576): rate and distortion without entropy coding
+    @torch.no_grad()
+    @on_model_device
+    def forward(self, im, return_rec=False):
+        """The reference's `model(im)`: one run of the eval plan (the encode plan with each block's per-channel rate,
+        lvae_gaussian_nll_chan_f32, and the distortion kernel in place of the coder's sinks).  Returns an OrderedDict
+          loss   0-d tensor on the model device, (kl + out_loss).mean(0)
+          kl     nats per dimension, batch mean
+          mse    (lossy models) the out net's loss: mean((x_hat - x_target)^2) * mse_lmb on the UNCLAMPED reconstruction, batch mean
+          nll    (lossless model) -log P per dimension of the pixels under the out net's discretised Gaussian, batch mean
+          bppix, psnr (from the batch-mean MSE of im_hat), and im_hat (B, 3, H, W) when return_rec
+        and fills self._stats_log['{train|eval}_bpdim' / '_bppix' / '_channels'].  The statistics are always the eval-mode (quantised)
+        ones: the package has no training path, and model.train() adds no training noise -- it only changes the _stats_log key.
+        Deterministic: two calls on the same input return the same bits.  A NaN / inf raises NonFiniteError."""
+        im = im.to(self._dummy.device)
+        assert im.dim() == 4 and im.shape[1] == 3 and not im.requires_grad, f'{im.shape=}'
+        B, imC, imH, imW = im.shape
+        assert imH % self.max_stride == 0 and imW % self.max_stride == 0, f'{im.shape=}'
+        self._ensure_tables()
+        self._prepare()
+        pl = self._plan('eval', B, imH, imW)
+        pl.im.view(B, 3, imH, imW).copy_(im)
+        pl.run()
+        pl.fetch_status()
+        torch.cuda.current_stream(pl.device).synchronize()
+        pl.raise_if_flagged(where='in forward()')       # out-of-range input: AssertionError, as the reference's preprocess_input
+        kl_chan, rd = pl.kl_chan.cpu(), pl.rd_sums.view(B, 2).cpu()
+        ndims = imC * imH * imW
+        chans = [kl_chan[o:o + B * z].view(B, z) for o, (z, _) in zip(pl.chan_off, pl.lat_shapes)]     # nats per (image, channel)
+        kl_divergences = [c.sum(1) for c in chans]
+        kl = sum(kl_divergences) / ndims
+        if pl.lossless:
+            out_loss, loss_name = rd[:, 0] / ndims, 'nll'
+        else:
+            out_loss, loss_name = rd[:, 0] / ndims * self.mse_lmb, 'mse'
+        im_mse = float(rd[:, 1].sum()) / (B * ndims)
+        nats_per_dim = float(kl.mean(0))
+        kls = torch.stack([k.mean(0) / ndims for k in kl_divergences])
+        bpdim = kls * self.log2_e
+        mode = 'train' if self.training else 'eval'
+        self._stats_log[f'{mode}_bpdim'] = bpdim.tolist()
+        self._stats_log[f'{mode}_bppix'] = (bpdim * imC).tolist()
+        self._stats_log[f'{mode}_channels'] = [(c.mean(0) / (imH * imW) * self.log2_e).tolist() for c in chans]
+        stats = OrderedDict()
+        stats['loss'] = (kl + out_loss).mean(0).to(device=self._dummy.device, dtype=torch.float32)
+        stats['kl'] = nats_per_dim
+        stats[loss_name] = float(out_loss.mean(0))
+        stats['bppix'] = nats_per_dim * self.log2_e * imC
+        stats['psnr'] = -10 * math.log10(im_mse)
+        if return_rec:
+            stats['im_hat'] = pl.out.clone()
+        return stats
+
+    @torch.no_grad()
+    def forward_eval(self, *args, **kwargs):
+        """(:572-576) = forward."""
+        return self.forward(*args, **kwargs)
 
     # ---- the generative API (reference qresvae/model.py:578-638): sampling, latents, inpainting.  Latents and pixels are drawn by the
     # device Philox stream (lvae_latent_sample_box_f32 / lvae_pixel_sample_f32), not by torch's RNG: a call is reproducible by its

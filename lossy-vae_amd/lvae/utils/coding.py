@@ -37,6 +37,17 @@ def pad_divisible_by(img, div=64):
     return Image.fromarray(np.pad(a, pw, mode='edge'))
 
 
+def crop_divisible_by(img, div=64):
+    """Center-crop a PIL image so both sides are multiples of `div` (coding.py:94-110).  The offsets are torchvision's center_crop:
+    top = int(round((h - h_new) / 2)), left = int(round((w - w_new) / 2)) (Python's round: ties to even)."""
+    h_old, w_old = img.height, img.width
+    if h_old % div == 0 and w_old % div == 0:
+        return img
+    h_new, w_new = div * (h_old // div), div * (w_old // div)
+    top, left = int(round((h_old - h_new) / 2.0)), int(round((w_old - w_new) / 2.0))
+    return img.crop((left, top, left + w_new, top + h_new))
+
+
 def pil_to_tensor01(img):
     """torchvision.transforms.functional.to_tensor for uint8 PIL images: HWC uint8 -> CHW float32 / 255."""
     import torch
