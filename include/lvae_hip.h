@@ -238,7 +238,8 @@ enum {
     LVAE_OP_GEMM = 1, LVAE_OP_DWCONV_LN_F32, LVAE_OP_DWCONV_LN_H2, LVAE_OP_DWCONV_LN_BF16, LVAE_OP_DWCONV_LN_Q8, LVAE_OP_STEM_F32, LVAE_OP_STEM_BF16,
     LVAE_OP_BIAS_EXPAND_F32, LVAE_OP_BIAS_EXPAND_BF16, LVAE_OP_PRIOR_INDEX, LVAE_OP_QUANTIZE, LVAE_OP_DEQUANTIZE, LVAE_OP_GAUSSIAN_NLL,
     LVAE_OP_LOSSLESS_PARAMS, LVAE_OP_LOSSLESS_OUTPUT, LVAE_OP_MLP_H2F, LVAE_OP_MLP_SK, LVAE_OP_PRIOR_INDEX_SK, LVAE_OP_QUANTIZE_SK,
-    LVAE_OP_GAUSSIAN_NLL_CHAN, LVAE_OP_RD_IMAGE, LVAE_OP_PIXEL_NLL, LVAE_OP_ORDER
+    LVAE_OP_GAUSSIAN_NLL_CHAN, LVAE_OP_RD_IMAGE, LVAE_OP_PIXEL_NLL,
+    LVAE_OP_DWCONV_LN_F32_V, LVAE_OP_DWCONV_LN_H2_V, LVAE_OP_DWCONV_LN_BF16_V, LVAE_OP_DWCONV_LN_Q8_V, LVAE_OP_ORDER
 };
 typedef struct { int kind; int side; void* p[8]; long i[6]; double f[2]; } lvae_op;
 #define LVAE_TRACE_MAGIC 1985229328.0      /* lvae_decode_blocks: seconds[1] of a timeline request */
@@ -325,6 +326,20 @@ int lvae_dwconv_ln_q8(const void* x, const float* wt, const float* bias, const f
 int lvae_dwconv_ln_bf16(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
                         const float* shift, const float* scale1p, void* y,
                         int B, int H, int W, int C, int k, void* stream);
+
+/* Per-image AdaLN vectors (a batch whose images are coded at different lambdas): the four forms above with an element stride between
+ * consecutive images' vectors -- image b is modulated by shift[b * vstride + c] and scale1p[b * vstride + c] (vstride >= 0; 0 = one
+ * pair for the batch).  No LayerNorm affine.  Image b's output is, bit for bit, what the form without the stride gives for that image
+ * alone with that image's vectors.  C in {128,192,256,384,512}, k in {1,3,5,7} (the csrc/dwconv_cl.hip instances); -22 otherwise --
+ * also for _f32_v / _bf16_v, whose shapes outside that set would run another kernel family. */
+int lvae_dwconv_ln_f32_v(const float* x, const float* wt, const float* bias, const float* shift, const float* scale1p, float* y,
+                         int B, int H, int W, int C, int k, long vstride, void* stream);
+int lvae_dwconv_ln_h2_v(const float* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
+                        int B, int H, int W, int C, int k, long vstride, void* stream);
+int lvae_dwconv_ln_bf16_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
+                          int B, int H, int W, int C, int k, long vstride, void* stream);
+int lvae_dwconv_ln_q8_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
+                        int B, int H, int W, int C, int k, long vstride, void* stream);
 int lvae_stem_bf16(const float* im, const float* wt, const float* bias, void* out,
                    int B, int H, int W, int Cout, float im_shift, float im_scale, int* range_flag, void* stream);
 int lvae_bias_expand_bf16(const float* bias, void* out, long M, int C, void* stream);
@@ -343,6 +358,11 @@ int lvae_range_flag_f32(const float* x, long n, float lo, float hi, int* flag, v
  * MLP (qarv/model.py:206-210) and all AdaLN `embedding_layer`s (common.py:123-127) as one concatenated GEMV. */
 int lvae_gemv_f32(const float* Wt, const float* b, const float* x, float* y, int N, int K,
                   int gelu_in, int gelu_out, void* stream);
+/* The same for nvec input vectors: x is [nvec][K], y is [nvec][N] (dense rows).  Every weight row is read from memory once and
+ * applied to all nvec inputs (K <= 1024: the row is held in registers; a longer row is re-fetched once per 8 inputs); row i of y
+ * equals lvae_gemv_f32 on row i of x bit for bit (same product order, reduction, bias, GELU). */
+int lvae_gemv_batch_f32(const float* Wt, const float* b, const float* x, float* y, int N, int K, int nvec,
+                        int gelu_in, int gelu_out, void* stream);
 
 /* Prior epilogue (qarv/model.py:51-53 + GaussianConditional.build_indexes, :106,112): prm is the `prior` conv
  * output [M][2z] (NHWC rows; first z = mean, last z = log-scale).  Writes pm [M][z] and, per image b, the scale

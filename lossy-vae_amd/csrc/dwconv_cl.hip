@@ -141,7 +141,7 @@ template <int KS, int NW, int TH, bool BF> constexpr int cl_waves() {
 template <int KS, int NW, int TH, bool BF, int OF = 0>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(cl_waves<KS, NW, TH, BF>(), cl_waves<KS, NW, TH, BF>()))) void dwconv_ln_cl_kernel(
     const void* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ bias, const float* __restrict__ aw,
-    const float* __restrict__ ab, void* __restrict__ y, int H, int W, int n_sx, int n_sy, int tpw, long mtot) {
+    const float* __restrict__ ab, void* __restrict__ y, int H, int W, int n_sx, int n_sy, int tpw, long mtot, long vstride) {
     using G = ClGeom<KS, BF>;
     constexpr bool H2 = OF == 1, Q8 = OF == 2;
     static_assert(!(H2 && BF) && !(Q8 && !BF), "H2 planes come from fp32 maps, Q8 from bf16 maps");
@@ -199,8 +199,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(cl_wave
     }
     if (PACKW && KK % 2) wp[KK / 2][1] = 0.f;
     const float bias1 = bias[c0];
-    prm[tid] = aw ? aw[tid] : 1.f;                     // blockDim.x == C
-    prm[C + tid] = ab ? ab[tid] : 0.f;
+    // image b's affine vectors start b * vstride elements behind aw / ab (0: one pair for the whole batch); b is wave-uniform, so the
+    // base moves in scalar registers and the copy below is the only place that sees it
+    prm[tid] = aw ? aw[b * vstride + tid] : 1.f;       // blockDim.x == C
+    prm[C + tid] = ab ? ab[b * vstride + tid] : 0.f;
     const int chA = 64 * wave + 4 * blk, chB = chA + 32;
 
     f32x2 acc[TH][SW / 2];
@@ -396,18 +398,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(cl_wave
 
 template <int KS, int NW, int TH, bool BF, int OF>
 int launch_cl_th(const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y, int B, int H, int W,
-                 int tpw, hipStream_t st) {
+                 int tpw, long vs, hipStream_t st) {
     const int n_sx = (W + CL_SW - 1) / CL_SW, n_ty = (H + TH - 1) / TH, n_sy = (n_ty + tpw - 1) / tpw;
     const long grid = (long)B * n_sx * n_sy;
     if (grid > 0x7fffffffL || (long)H * W * 64 * NW * (BF ? 2 : 4) > 0x7fffffffL) return -22;
     hipLaunchKernelGGL((dwconv_ln_cl_kernel<KS, NW, TH, BF, OF>), dim3((unsigned)grid), dim3(64 * NW), 0, st, x, wt, bias, aw, ab, y, H, W,
-                       n_sx, n_sy, tpw, (long)B * H * W);
+                       n_sx, n_sy, tpw, (long)B * H * W, vs);
     return (int)hipGetLastError();
 }
 
 template <int KS, int NW, bool BF, int OF>
 int launch_cl(const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y, int B, int H, int W,
-              hipStream_t st) {
+              long vs, hipStream_t st) {
     // Output rows per tile (TH) and tiles per workgroup (tpw): the pair with the least estimated time.  A workgroup costs ~3 row
     // steps for its weights plus, per tile, TH + k - 1 row steps and ~2 for the first rows' latency; the chip runs `slots`
     // workgroups at a time (3 / 4 waves per SIMD -- the register budgets -- and 160 KB of LDS per CU), in whole rounds.
@@ -432,21 +434,21 @@ int launch_cl(const void* x, const float* wt, const float* bias, const float* aw
     }
     const int TH = best_th, tpw = best_tpw;
     if constexpr (KS > 1) {
-        if (TH == 8) return launch_cl_th<KS, NW, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, st);
-        if (TH >= 2) return launch_cl_th<KS, NW, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, st);
+        if (TH == 8) return launch_cl_th<KS, NW, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
+        if (TH >= 2) return launch_cl_th<KS, NW, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
     }
-    return launch_cl_th<KS, NW, 1, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, st);
+    return launch_cl_th<KS, NW, 1, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
 }
 
 template <int KS, bool BF, int OF = 0>
 int launch_cl_c(int C, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y, int B, int H,
-                int W, hipStream_t st) {
+                int W, long vs, hipStream_t st) {
     switch (C) {
-        case 128: return launch_cl<KS, 2, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, st);
-        case 192: return launch_cl<KS, 3, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, st);
-        case 256: return launch_cl<KS, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, st);
-        case 384: return launch_cl<KS, 6, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, st);
-        case 512: return launch_cl<KS, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, st);
+        case 128: return launch_cl<KS, 2, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 192: return launch_cl<KS, 3, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 256: return launch_cl<KS, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 384: return launch_cl<KS, 6, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 512: return launch_cl<KS, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
     }
     return -22;
 }
@@ -459,50 +461,52 @@ int launch_cl_c(int C, const void* x, const float* wt, const float* bias, const 
 // instances take minutes otherwise.
 #if defined(LVAE_CL_Q8_TU)
 int lvae_dwln_cl_launch_q8(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, hipStream_t st) {
+                           int B, int H, int W, long vs, hipStream_t st) {
     switch (k) {
-        case 1: return launch_cl_c<1, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 3: return launch_cl_c<3, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 5: return launch_cl_c<5, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 7: return launch_cl_c<7, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, st);
+        case 1: return launch_cl_c<1, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 3: return launch_cl_c<3, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 5: return launch_cl_c<5, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 7: return launch_cl_c<7, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
     }
     return -22;
 }
 #elif defined(LVAE_CL_H2_TU)
 int lvae_dwln_cl_launch_h2(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, hipStream_t st) {
+                           int B, int H, int W, long vs, hipStream_t st) {
     switch (k) {
-        case 1: return launch_cl_c<1, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 3: return launch_cl_c<3, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 5: return launch_cl_c<5, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 7: return launch_cl_c<7, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, st);
+        case 1: return launch_cl_c<1, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 3: return launch_cl_c<3, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 5: return launch_cl_c<5, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 7: return launch_cl_c<7, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
     }
     return -22;
 }
 #elif defined(LVAE_CL_BF16_TU)
 int lvae_dwln_cl_launch_bf16(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                             int B, int H, int W, hipStream_t st) {
+                             int B, int H, int W, long vs, hipStream_t st) {
     switch (k) {
-        case 1: return launch_cl_c<1, true>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 3: return launch_cl_c<3, true>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 5: return launch_cl_c<5, true>(C, x, wt, bias, aw, ab, y, B, H, W, st);
-        case 7: return launch_cl_c<7, true>(C, x, wt, bias, aw, ab, y, B, H, W, st);
+        case 1: return launch_cl_c<1, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 3: return launch_cl_c<3, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 5: return launch_cl_c<5, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 7: return launch_cl_c<7, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
     }
     return -22;
 }
 #else
 int lvae_dwln_cl_launch_bf16(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                             int B, int H, int W, hipStream_t st);
+                             int B, int H, int W, long vs, hipStream_t st);
 int lvae_dwln_cl_launch_h2(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, hipStream_t st);
+                           int B, int H, int W, long vs, hipStream_t st);
 int lvae_dwln_cl_launch_q8(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, hipStream_t st);
+                           int B, int H, int W, long vs, hipStream_t st);
 
 // Entry point for pointwise.hip's dispatchers.  Returns 1 when this kernel takes the problem (*rc = launch status), 0 otherwise.
 // Taken for C in {128, 192, 256, 384, 512}, k in {1, 3, 5, 7} and at most ONE per-channel affine after the normalisation -- a rule
 // in (C, k, which pointers are given) only, because this kernel's LayerNorm association differs from the other forms'.
+// vs: element stride between consecutive images' affine vectors (0: one pair for the batch -- the lvae_dwconv_ln_* entry points; > 0:
+// the lvae_dwconv_ln_*_v ones, image b reads shift + b * vs / scale1p + b * vs).
 int lvae_dwln_cl_try(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b, const float* shift,
-                     const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, hipStream_t st, int* rc) {
+                     const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, long vs, hipStream_t st, int* rc) {
     const int bf16 = fmt == 1 || fmt == 3;                              // fmt: 0 fp32 maps, 1 bf16 maps, 2 fp32 in / f16x2 planes out, 3 bf16 in / MX-fp8 out
     if (ln_w && shift) return 0;
     if (!(C == 128 || C == 192 || C == 256 || C == 384 || C == 512) || !(k == 1 || k == 3 || k == 5 || k == 7)) return 0;
@@ -511,14 +515,14 @@ int lvae_dwln_cl_try(const void* x, const float* wt, const float* bias, const fl
     if ((long)H * W * C * (bf16 ? 2 : 4) > 0x7fffffffL) { *rc = -22; return 1; }
     const float* aw = ln_w ? ln_w : scale1p;
     const float* ab = ln_w ? ln_b : shift;
-    if (fmt == 3) { *rc = lvae_dwln_cl_launch_q8(C, k, x, wt, bias, aw, ab, y, B, H, W, st); return 1; }
-    if (bf16) { *rc = lvae_dwln_cl_launch_bf16(C, k, x, wt, bias, aw, ab, y, B, H, W, st); return 1; }
-    if (fmt == 2) { *rc = lvae_dwln_cl_launch_h2(C, k, x, wt, bias, aw, ab, y, B, H, W, st); return 1; }
+    if (fmt == 3) { *rc = lvae_dwln_cl_launch_q8(C, k, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1; }
+    if (bf16) { *rc = lvae_dwln_cl_launch_bf16(C, k, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1; }
+    if (fmt == 2) { *rc = lvae_dwln_cl_launch_h2(C, k, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1; }
     switch (k) {
-        case 1: *rc = launch_cl_c<1, false>(C, x, wt, bias, aw, ab, y, B, H, W, st); return 1;
-        case 3: *rc = launch_cl_c<3, false>(C, x, wt, bias, aw, ab, y, B, H, W, st); return 1;
-        case 5: *rc = launch_cl_c<5, false>(C, x, wt, bias, aw, ab, y, B, H, W, st); return 1;
-        case 7: *rc = launch_cl_c<7, false>(C, x, wt, bias, aw, ab, y, B, H, W, st); return 1;
+        case 1: *rc = launch_cl_c<1, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
+        case 3: *rc = launch_cl_c<3, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
+        case 5: *rc = launch_cl_c<5, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
+        case 7: *rc = launch_cl_c<7, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
     }
     return 0;
 }

@@ -92,6 +92,22 @@ extern "C" int lvae_run_ops(const lvae_op* ops, int n, void* stream, void* side_
                 rc = lvae_pixel_nll_f32((const float*)p[0], (const float*)p[1], (float*)p[2], (double*)p[3], (double*)p[4], (int)i[0], (int)i[1], (int)i[2],
                                         (int*)p[5], st);
                 break;
+            case LVAE_OP_DWCONV_LN_F32_V:
+                rc = lvae_dwconv_ln_f32_v((const float*)p[0], (const float*)p[1], (const float*)p[2], (const float*)p[3], (const float*)p[4], (float*)p[5],
+                                          (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], i[5], st);
+                break;
+            case LVAE_OP_DWCONV_LN_H2_V:
+                rc = lvae_dwconv_ln_h2_v((const float*)p[0], (const float*)p[1], (const float*)p[2], (const float*)p[3], (const float*)p[4], p[5],
+                                         (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], i[5], st);
+                break;
+            case LVAE_OP_DWCONV_LN_BF16_V:
+                rc = lvae_dwconv_ln_bf16_v(p[0], (const float*)p[1], (const float*)p[2], (const float*)p[3], (const float*)p[4], p[5],
+                                           (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], i[5], st);
+                break;
+            case LVAE_OP_DWCONV_LN_Q8_V:
+                rc = lvae_dwconv_ln_q8_v(p[0], (const float*)p[1], (const float*)p[2], (const float*)p[3], (const float*)p[4], p[5],
+                                         (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], i[5], st);
+                break;
             case LVAE_OP_ORDER:      // i[0] != 0: the side stream waits for the main stream (fork); else the main stream for the side stream (join)
                 rc = i[0] ? lvae_stream_order(stream, side_stream, p[0]) : lvae_stream_order(side_stream, stream, p[0]);
                 break;

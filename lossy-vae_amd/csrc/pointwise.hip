@@ -320,6 +320,64 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ Wt,
     }
 }
 
+// The same product for nvec input vectors (row i of x: x + i * K -> row i of y: y + i * N).  A wave still owns ONE output column; its
+// weight row is read from memory ONCE, into registers (one f32x4 per lane and 256 columns: K <= 256 * GEMV_KR, which covers the
+// embedding's K = 256; a longer row -- WREG = false -- is re-fetched once per GEMV_NB inputs), and applied to the inputs in passes of
+// GEMV_NB with one accumulator per input.  Per output element nothing differs from gemv_kernel: products in ascending k with the same
+// fmaf chain per lane, the same xor butterfly, bias, then GELU -- row i is bit for bit the single-vector launch on input i (the
+// encoder and the decoder of a stream may derive their AdaLN vectors one from a batch, the other alone).
+constexpr int GEMV_NB = 8, GEMV_KR = 4;
+template <bool WREG>
+__global__ __launch_bounds__(256) void gemv_batch_kernel(const float* __restrict__ Wt, const float* __restrict__ b,
+                                                         const float* __restrict__ x, float* __restrict__ y, int N, int K, int nvec,
+                                                         int gelu_in, int gelu_out) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    f32x4 wr[GEMV_KR];
+    if constexpr (WREG) {
+#pragma unroll
+        for (int t = 0; t < GEMV_KR; ++t) {
+            const int k = lane * 4 + 256 * t;
+            wr[t] = k < K ? *(const f32x4*)(Wt + (long)n * K + k) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    for (int i0 = 0; i0 < nvec; i0 += GEMV_NB) {
+        float s[GEMV_NB];
+#pragma unroll
+        for (int i = 0; i < GEMV_NB; ++i) s[i] = 0.f;
+        auto step = [&](const f32x4 wv, int k) {
+#pragma unroll
+            for (int i = 0; i < GEMV_NB; ++i) {
+                if (i0 + i < nvec) {
+                    f32x4 xv = *(const f32x4*)(x + (long)(i0 + i) * K + k);
+                    if (gelu_in) { xv[0] = gelu_erf(xv[0]); xv[1] = gelu_erf(xv[1]); xv[2] = gelu_erf(xv[2]); xv[3] = gelu_erf(xv[3]); }
+                    s[i] = fmaf(wv[0], xv[0], s[i]); s[i] = fmaf(wv[1], xv[1], s[i]); s[i] = fmaf(wv[2], xv[2], s[i]); s[i] = fmaf(wv[3], xv[3], s[i]);
+                }
+            }
+        };
+        if constexpr (WREG) {
+#pragma unroll
+            for (int t = 0; t < GEMV_KR; ++t) {
+                const int k = lane * 4 + 256 * t;
+                if (k < K) step(wr[t], k);
+            }
+        } else {
+            for (int k = lane * 4; k < K; k += 256) step(*(const f32x4*)(Wt + (long)n * K + k), k);
+        }
+#pragma unroll
+        for (int i = 0; i < GEMV_NB; ++i) {
+            float t = s[i];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+            if (lane == 0 && i0 + i < nvec) {
+                t += b[n];
+                y[(long)(i0 + i) * N + n] = gelu_out ? gelu_erf(t) : t;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ lossless output net
 __global__ void lossless_params_kernel(const float* __restrict__ raw, const float* __restrict__ im, float* __restrict__ pm,
                                        uint8_t* __restrict__ idx, int32_t* __restrict__ sym, const float* __restrict__ table,
@@ -871,7 +929,7 @@ __global__ __launch_bounds__(256) void sqerr_kernel(const float* __restrict__ a,
 // dwconv_cl.hip: the channel-per-lane form (weights in registers, LDS-DMA row buffers) takes the problem by (C, k) alone; what follows
 // here is the sliding-window kernel for the other channel counts (qres17m: C = 144 / 288) and the two-affine case
 int lvae_dwln_cl_try(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b, const float* shift,
-                     const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, hipStream_t st, int* rc);
+                     const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, long vs, hipStream_t st, int* rc);
 
 extern "C" int lvae_dwconv_ln_f32(const float* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
                                   const float* shift, const float* scale1p, float* y, int B, int H, int W, int C, int k,
@@ -880,7 +938,7 @@ extern "C" int lvae_dwconv_ln_f32(const float* x, const float* wt, const float* 
     if ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr)) return -22;
     {
         int rc = 0;
-        if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 0, (hipStream_t)stream, &rc)) return rc;
+        if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 0, 0, (hipStream_t)stream, &rc)) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     switch (k) {
@@ -897,7 +955,7 @@ extern "C" int lvae_dwconv_ln_h2(const float* x, const float* wt, const float* b
     if (!x || !wt || !bias || !y || B <= 0 || H <= 0 || W <= 0) return -22;
     if ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr)) return -22;
     int rc = 0;
-    return lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 2, (hipStream_t)stream, &rc) ? rc : -22;
+    return lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 2, 0, (hipStream_t)stream, &rc) ? rc : -22;
 }
 
 extern "C" int lvae_dwconv_ln_q8(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
@@ -905,7 +963,7 @@ extern "C" int lvae_dwconv_ln_q8(const void* x, const float* wt, const float* bi
     if (!x || !wt || !bias || !y || B <= 0 || H <= 0 || W <= 0) return -22;
     if ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr)) return -22;
     int rc = 0;
-    return lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 3, (hipStream_t)stream, &rc) ? rc : -22;
+    return lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 3, 0, (hipStream_t)stream, &rc) ? rc : -22;
 }
 
 extern "C" int lvae_stem_f32(const float* im, const float* wt, const float* bias, float* out, int B, int H, int W,
@@ -934,7 +992,7 @@ extern "C" int lvae_dwconv_ln_bf16(const void* x, const float* wt, const float* 
     hipStream_t st = (hipStream_t)stream;
     {
         int rc = 0;
-        if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 1, st, &rc)) return rc;
+        if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 1, 0, st, &rc)) return rc;
     }
     switch (k) {
         case 1: return dispatch_dwln_bf16<1>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
@@ -943,6 +1001,31 @@ extern "C" int lvae_dwconv_ln_bf16(const void* x, const float* wt, const float* 
         case 7: return dispatch_dwln_bf16<7>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
     }
     return -22;
+}
+
+// Per-image AdaLN vectors: image b of the batch is modulated by shift + b * vstride / scale1p + b * vstride (elements).  Only the
+// channel-per-lane kernel has this form; every other shape is an argument error (-22), never another kernel.
+static int dwln_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y, int B, int H, int W,
+                  int C, int k, long vstride, int fmt, void* stream) {
+    if (!x || !wt || !bias || !y || !shift || !scale1p || B <= 0 || H <= 0 || W <= 0 || vstride < 0) return -22;
+    int rc = 0;
+    return lvae_dwln_cl_try(x, wt, bias, nullptr, nullptr, shift, scale1p, y, B, H, W, C, k, fmt, vstride, (hipStream_t)stream, &rc) ? rc : -22;
+}
+extern "C" int lvae_dwconv_ln_f32_v(const float* x, const float* wt, const float* bias, const float* shift, const float* scale1p, float* y,
+                                    int B, int H, int W, int C, int k, long vstride, void* stream) {
+    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 0, stream);
+}
+extern "C" int lvae_dwconv_ln_bf16_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
+                                     int B, int H, int W, int C, int k, long vstride, void* stream) {
+    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 1, stream);
+}
+extern "C" int lvae_dwconv_ln_h2_v(const float* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
+                                   int B, int H, int W, int C, int k, long vstride, void* stream) {
+    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 2, stream);
+}
+extern "C" int lvae_dwconv_ln_q8_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
+                                   int B, int H, int W, int C, int k, long vstride, void* stream) {
+    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 3, stream);
 }
 
 namespace {
@@ -987,6 +1070,18 @@ extern "C" int lvae_gemv_f32(const float* Wt, const float* b, const float* x, fl
     if (!Wt || !b || !x || !y || N <= 0 || K <= 0 || (K & 3)) return -22;
     hipLaunchKernelGGL(gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, Wt, b, x, y, N, K, gelu_in,
                        gelu_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_gemv_batch_f32(const float* Wt, const float* b, const float* x, float* y, int N, int K, int nvec, int gelu_in,
+                                   int gelu_out, void* stream) {
+    if (!Wt || !b || !x || !y || N <= 0 || K <= 0 || (K & 3) || nvec <= 0) return -22;
+    if (K <= 256 * GEMV_KR)
+        hipLaunchKernelGGL(gemv_batch_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, Wt, b, x, y, N, K, nvec, gelu_in,
+                           gelu_out);
+    else
+        hipLaunchKernelGGL(gemv_batch_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, Wt, b, x, y, N, K, nvec, gelu_in,
+                           gelu_out);
     return (int)hipGetLastError();
 }
 

@@ -65,7 +65,8 @@ OP_KINDS = {name: k + 1 for k, name in enumerate([
     'lvae_gemm_f32', 'lvae_dwconv_ln_f32', 'lvae_dwconv_ln_h2', 'lvae_dwconv_ln_bf16', 'lvae_dwconv_ln_q8', 'lvae_stem_f32', 'lvae_stem_bf16',
     'lvae_bias_expand_f32', 'lvae_bias_expand_bf16', 'lvae_prior_index_f32', 'lvae_quantize_f32', 'lvae_dequantize_f32',
     'lvae_gaussian_nll_f32', 'lvae_lossless_params_f32', 'lvae_lossless_output_f32', 'lvae_mlp_h2f', 'lvae_mlp_sk', 'lvae_prior_index_sk_f32', 'lvae_quantize_sk_f32',
-    'lvae_gaussian_nll_chan_f32', 'lvae_rd_image_f32', 'lvae_pixel_nll_f32'])}
+    'lvae_gaussian_nll_chan_f32', 'lvae_rd_image_f32', 'lvae_pixel_nll_f32',
+    'lvae_dwconv_ln_f32_v', 'lvae_dwconv_ln_h2_v', 'lvae_dwconv_ln_bf16_v', 'lvae_dwconv_ln_q8_v'])}
 OP_ORDER = len(OP_KINDS) + 1
 
 TRACE_MAGIC = 1985229328.0       # LVAE_TRACE_MAGIC
@@ -99,9 +100,14 @@ SIGNATURES = {
     'lvae_stem_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     'lvae_range_flag_f32': (_i, [_vp, _l, _f, _f, _vp, _vp]),
     'lvae_dwconv_ln_bf16': (_i, [_vp] * 8 + [_i] * 5 + [_vp]),
+    'lvae_dwconv_ln_f32_v': (_i, [_vp] * 6 + [_i] * 5 + [_l, _vp]),
+    'lvae_dwconv_ln_h2_v': (_i, [_vp] * 6 + [_i] * 5 + [_l, _vp]),
+    'lvae_dwconv_ln_bf16_v': (_i, [_vp] * 6 + [_i] * 5 + [_l, _vp]),
+    'lvae_dwconv_ln_q8_v': (_i, [_vp] * 6 + [_i] * 5 + [_l, _vp]),
     'lvae_stem_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     'lvae_bias_expand_bf16': (_i, [_vp, _vp, _l, _i, _vp]),
     'lvae_gemv_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'lvae_gemv_batch_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'lvae_prior_index_f32': (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _i, _i, _vp, _vp]),
     'lvae_prior_index_sk_f32': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _i, _vp, _vp]),
     'lvae_quantize_sk_f32': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

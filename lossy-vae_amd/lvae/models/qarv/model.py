@@ -192,6 +192,7 @@ class _Packed:
         self.emb_in = torch.zeros(EMBED_DIM, **f32)
         self.emb_h = torch.zeros(EMBED_DIM, **f32)
         self.emb = torch.zeros(EMBED_DIM, **f32)
+        self.tab_cap, self.adaln_tab = 0, None          # per-image lambdas: [tab_cap][adaln_total] table (model._set_lmb with a sequence)
         self.scale_table = model._dg().scale_table.detach().to(**f32).contiguous()
         self.scale_bound = float(model._dg().lower_bound_scale.bound.item())
 
@@ -215,9 +216,14 @@ class _Packed:
 class _NetPlan(Plan):
     """Shared recording helpers for the encode and decode plans."""
 
-    def __init__(self, model, pk, B):
+    def __init__(self, model, pk, B, vec=False):
         super().__init__(pk.adaln.device)
         self.model, self.pk, self.B = model, pk, B
+        # vec: one lambda PER IMAGE.  The depthwise launches then read image b's (shift | 1+scale) vectors from row b of a slab this plan
+        # owns ([B][adaln_total], filled by load_lmb before a run) instead of the model-wide pk.adaln.  The slab is the plan's own because
+        # plans are cached with their addresses baked in while a pipeline group's first image index is not part of the cache key
+        self.vec = bool(vec)
+        self.adaln_slab = torch.zeros(B * pk.adaln_total, dtype=torch.float32, device=pk.adaln.device) if vec else None
         self.prec = PREC_CODE[model._prec]
         self.prec_name = model._prec
         self.w16 = pk.bf16_map(model._prec) if self.prec else None
@@ -234,6 +240,23 @@ class _NetPlan(Plan):
         self.prm_bufs, self.qm_bufs, self.zhat_ld = [], [], []      # test access (CodecBase._trace_blocks): tensors behind those launches
         self.lat_shapes = []                    # (z, HW)
 
+    def load_lmb(self, table, start):
+        """vec plans: rows start .. start + B of the model's per-image table -> this plan's slab, on the current stream (the stream the
+        plan is about to run on: ordered behind the table's GEMVs by the caller, and behind this plan's previous run)."""
+        n = self.pk.adaln_total
+        self.adaln_slab.copy_(table[start * n:(start + self.B) * n], non_blocking=True)
+
+    def dwln_add(self, fn, p, x, y, H, W, C, k):
+        """Record the depthwise + LayerNorm + AdaLN launch of block p: `fn` with the model-wide vectors, its _v form with the slab's."""
+        pk = self.pk
+        off = pk.adaln_off[p]
+        if self.vec:
+            self.add(getattr(self.lib, fn.lvae_name + '_v'), (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), ptr(self.adaln_slab, off),
+                                                             ptr(self.adaln_slab, off + C), y, self.B, H, W, C, k, pk.adaln_total), p + '.dwln')
+        else:
+            self.add(fn, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), None, None, ptr(pk.adaln, off), ptr(pk.adaln, off + C), y, self.B, H, W, C, k),
+                     p + '.dwln')
+
     def scratch(self, M, C, hid):
         y = self.buf(self.sname('y'), M * C, self.adt)
         h = self.buf(self.sname('hid'), M * hid, self.adt)
@@ -245,23 +268,20 @@ class _NetPlan(Plan):
         C, k, hid = m.dim, m.kernel_size, m.hidden
         M = self.B * H * W
         y, h = self.scratch(M, C, hid)
-        off = pk.adaln_off[p]
         # f16x2 plans: y and the hidden map have one consumer each (fc1 / fc2), so their producers store them pre-split (hi / lo' fp16
         # planes, 4 bytes per element like fp32) and the two GEMMs stream both operands by LDS-DMA with no conversion in the main loop
         # (reduced-precision plans: the same idea with MX-fp8 -- the producers quantise, csrc/gemm_q8.hip streams)
         # (small maps: the split-K layers -- pre-split + serial split-K where the batch makes that the faster form, same bits: engine.mlp_pipeline)
         if self.mlp_fused_ok(C, hid, k, M=M, rows_per_image=H * W):
             # C = 128 / hidden = 192 (the decoder's stride-4 blocks): fc1 -> GELU -> fc2 as one launch, the hidden tile never leaves the CU
-            self.add(lib.lvae_dwconv_ln_h2, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), None, None, ptr(pk.adaln, off), ptr(pk.adaln, off + C),
-                                             y.data_ptr(), self.B, H, W, C, k), p + '.dwln')
+            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y.data_ptr(), H, W, C, k)
             self.mlp_fused(y=y.data_ptr(), M=M, C=C, hid=hid, w1=pk.p(p + '.fc1_w'), b1=pk.p(p + '.fc1_b'), w2=pk.p(p + '.fc2_w'),
                            b2=pk.p(p + '.fc2_b'), gamma=pk.p(p + '.gamma'), res=x, out=out, label=p + '.mlp')
             return
         sk = self.mlp_sk_ok(C, hid, k, H * W, M)
         if sk is not None:
             # stride-32 / 64 maps (both GEMMs split-K): fc1 -> GELU -> fc2's partial sums as one launch, then the reduce launch (csrc/mlp_sk.hip)
-            self.add(lib.lvae_dwconv_ln_h2, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), None, None, ptr(pk.adaln, off), ptr(pk.adaln, off + C),
-                                             y.data_ptr(), self.B, H, W, C, k), p + '.dwln')
+            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y.data_ptr(), H, W, C, k)
             self.mlp_sk(y=y.data_ptr(), M=M, C=C, hid=hid, S1=sk[0], S2=sk[1], w1=pk.p(p + '.fc1_w'), b1=pk.p(p + '.fc1_b'), w2=pk.p(p + '.fc2_w'),
                         b2=pk.p(p + '.fc2_b'), gamma=pk.p(p + '.gamma'), res=x, out=out, label=p + '.mlp')
             return
@@ -269,8 +289,7 @@ class _NetPlan(Plan):
             pre1, pre2, S1, S2 = True, True, None, None
         else:
             pre1, pre2, S1, S2 = self.mlp_pipeline(C, hid, k, H * W)
-        self.add((lib.lvae_dwconv_ln_q8 if self.lp else lib.lvae_dwconv_ln_h2) if pre1 else self.dwln, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), None, None, ptr(pk.adaln, off),
-                                                               ptr(pk.adaln, off + C), y.data_ptr(), self.B, H, W, C, k), p + '.dwln')
+        self.dwln_add((lib.lvae_dwconv_ln_q8 if self.lp else lib.lvae_dwconv_ln_h2) if pre1 else self.dwln, p, x, y.data_ptr(), H, W, C, k)
         self.gemm(A0=y.data_ptr(), K0=C, M=M, N=hid, Wt=pk.p(p + '.fc1_w'), bias=pk.p(p + '.fc1_b'), out=h.data_ptr(),
                   epi=_native.EPI_BIAS_GELU, a_h2=pre1, out_h2=pre2, ksplit=S1, label=p + '.fc1')
         self.gemm(A0=h.data_ptr(), K0=hid, M=M, N=C, Wt=pk.p(p + '.fc2_w'), bias=pk.p(p + '.fc2_b'),
@@ -350,10 +369,10 @@ class _NetPlan(Plan):
 class _EncPlan(_NetPlan):
     """forward_end2end(mode='compress') (qarv/model.py:294-315) for B images of size HxW."""
 
-    def __init__(self, model, pk, B, H, W, with_bits=False, chan_bits=False):
+    def __init__(self, model, pk, B, H, W, with_bits=False, chan_bits=False, vec=False):
         """with_bits ('encb'): each block's rate per image in `nats` ([block][image], accumulated); chan_bits ('ence', the encoder half of
         forward()): per image and channel in `kl_chan` (fp64 [L][B][z_l] at chan_off[l], lvae_gaussian_nll_chan_f32: deterministic)."""
-        super().__init__(model, pk, B)
+        super().__init__(model, pk, B, vec)
         lib = self.lib
         self.im = self.new(B * 3 * H * W)
         if getattr(model, 'side_streams', False):
@@ -496,8 +515,8 @@ class _DecPlan(_NetPlan):
     forward()): the final conv stored raw (NHWC fp32 [B*H*W][3], `x_raw`) and lvae_rd_image_f32 against `im` -> `out` (im_hat), `rd_sums`
     (fp64 [B][2]: sum (x_hat - x_target)^2, sum (im_hat - im)^2)."""
 
-    def __init__(self, model, pk, B, nH, nW, evaluate=False):
-        super().__init__(model, pk, B)
+    def __init__(self, model, pk, B, nH, nW, evaluate=False, vec=False):
+        super().__init__(model, pk, B, vec)
         lib = self.lib
         self.alloc_latent_io_full(nH, nW, host=not evaluate)
         h, w = nH, nW
@@ -577,6 +596,7 @@ class VariableRateLossyVAE(CodecBase):
         self._packed_key = None
         self._plans = {}
         self._cur_lmb = None
+        self._cur_lmbs = None             # tuple of fp32 lambdas whose vectors the per-image table holds
         self.timing = {} if os.environ.get('LVAE_TIMING') else None      # host-side phase timers (debug)
         # independent encoder branches on a second HIP stream (see SIDE_STREAM_MAX_PIXELS, _EncPlan); False gives the same bits
         self.side_streams = True
@@ -597,7 +617,7 @@ class VariableRateLossyVAE(CodecBase):
         return super().load_state_dict(*a, **k)
 
     def _invalidate(self):
-        self._packed, self._plans, self._cur_lmb = None, {}, None
+        self._packed, self._plans, self._cur_lmb, self._cur_lmbs = None, {}, None, None
 
     def _prepare(self):
         dev = self._dummy.device
@@ -608,51 +628,97 @@ class VariableRateLossyVAE(CodecBase):
             _native.lib()
             with torch.no_grad():
                 self._packed = _Packed(self, dev)
-            self._plans, self._cur_lmb = {}, None
+            self._plans, self._cur_lmb, self._cur_lmbs = {}, None, None
         return self._packed
 
-    def _set_lmb(self, lmb):
-        """_get_lmb_embedding (qarv/model.py:266-287) + every block's AdaLN embedding_layer (common.py:150-151), once
-        per lambda: sinusoidal features on the host (128 cos + 128 sin), then three GEMV launches."""
-        pk = self._prepare()
-        lmb = float(np.float32(lmb))
-        if self._cur_lmb == lmb:
-            return
-        if torch.cuda.current_device() != pk.adaln.device.index:   # raw launches below: make the model's GPU the current one
-            with torch.cuda.device(pk.adaln.device):
-                return self._set_lmb(lmb)
+    def _lmb_features(self, lmb):
+        """Sinusoidal features of one lambda (qarv/model.py:266-287) on the host, fp32: 128 cos + 128 sin."""
         s = np.log(np.float32(lmb)) * np.float32(self._sin_period) / np.float32(math.log(self.MAX_LMB))
         dim = self.lmb_embed_dim[0]
         expo = np.linspace(0, 1, dim // 2, dtype=np.float32)
         freqs = np.power(np.float32(self._sin_period), -expo).astype(np.float32)
         args = (np.float32(s) * freqs).astype(np.float32)
-        e = np.concatenate([np.cos(args), np.sin(args)]).astype(np.float32)
-        pk.emb_in.copy_(torch.from_numpy(e))
+        return np.concatenate([np.cos(args), np.sin(args)]).astype(np.float32)
+
+    def _lmb_arg(self, lmb, B, default=True):
+        """The `lmb` argument of the batch interfaces -> a float (one lambda for the call: None, a number, a one-element tensor, or B
+        equal values) or a list of B fp32-valued floats (one per image).  default=False (lambdas read from stream headers): values pass
+        through as written, a zero is not replaced by default_lmb."""
+        if lmb is None:
+            return self.default_lmb
+        if isinstance(lmb, torch.Tensor):
+            lmb = lmb.item() if lmb.numel() == 1 and lmb.dim() == 0 else lmb.detach().cpu().reshape(-1).tolist()
+        elif isinstance(lmb, np.ndarray):
+            lmb = lmb.reshape(-1).tolist()
+        if isinstance(lmb, (list, tuple)):
+            assert len(lmb) == B, f'{len(lmb)} lambdas for a batch of {B}'
+            vals = [float(np.float32(v)) for v in lmb]
+            if all(v == vals[0] for v in vals):
+                return (vals[0] or self.default_lmb) if default else vals[0]
+            return vals
+        return (lmb or self.default_lmb) if default else lmb
+
+    def _set_lmb(self, lmb):
+        """_get_lmb_embedding (qarv/model.py:266-287) + every block's AdaLN embedding_layer (common.py:150-151), once
+        per lambda: sinusoidal features on the host (128 cos + 128 sin), then three GEMV launches.  A list / tuple of lambdas fills
+        row i of the per-image table pk.adaln_tab with lambda i's vectors instead (three batched launches; row i has the bits the
+        single-lambda launches give for lambda i, so streams coded from the table decode against pk.adaln and the other way round)."""
+        pk = self._prepare()
+        many = isinstance(lmb, (list, tuple))
+        key = tuple(float(np.float32(v)) for v in lmb) if many else float(np.float32(lmb))
+        if (self._cur_lmbs if many else self._cur_lmb) == key:
+            return
+        if torch.cuda.current_device() != pk.adaln.device.index:   # raw launches below: make the model's GPU the current one
+            with torch.cuda.device(pk.adaln.device):
+                return self._set_lmb(lmb)
+        dim, hid = self.lmb_embed_dim
         lib = _native.lib()
         st = torch.cuda.current_stream(pk.adaln.device).cuda_stream
+        if many:
+            n = len(key)
+            if n > pk.tab_cap:
+                cap = max(8, n)
+                f32 = dict(device=pk.adaln.device, dtype=torch.float32)
+                pk.tab_in, pk.tab_h, pk.tab_emb = torch.zeros(cap * dim, **f32), torch.zeros(cap * hid, **f32), torch.zeros(cap * hid, **f32)
+                pk.adaln_tab, pk.tab_cap = torch.zeros(cap * pk.adaln_total, **f32), cap
+            pk.tab_in[:n * dim].copy_(torch.from_numpy(np.concatenate([self._lmb_features(v) for v in key])))
+            _native.check(lib.lvae_gemv_batch_f32(pk.p('lmb.0.w'), pk.p('lmb.0.b'), pk.tab_in.data_ptr(), pk.tab_h.data_ptr(), hid, dim, n, 0, 1, st),
+                          'gemv lmb.0')
+            _native.check(lib.lvae_gemv_batch_f32(pk.p('lmb.2.w'), pk.p('lmb.2.b'), pk.tab_h.data_ptr(), pk.tab_emb.data_ptr(), hid, hid, n, 0, 0, st),
+                          'gemv lmb.2')
+            _native.check(lib.lvae_gemv_batch_f32(pk.p('adaln.w'), pk.p('adaln.b'), pk.tab_emb.data_ptr(), pk.adaln_tab.data_ptr(), pk.adaln_total,
+                                                  hid, n, 1, 0, st), 'gemv adaln')
+            self._cur_lmbs = key
+            return
+        pk.emb_in.copy_(torch.from_numpy(self._lmb_features(key)))
         _native.check(lib.lvae_gemv_f32(pk.p('lmb.0.w'), pk.p('lmb.0.b'), pk.emb_in.data_ptr(), pk.emb_h.data_ptr(),
-                                        self.lmb_embed_dim[1], dim, 0, 1, st), 'gemv lmb.0')
+                                        hid, dim, 0, 1, st), 'gemv lmb.0')
         _native.check(lib.lvae_gemv_f32(pk.p('lmb.2.w'), pk.p('lmb.2.b'), pk.emb_h.data_ptr(), pk.emb.data_ptr(),
-                                        self.lmb_embed_dim[1], self.lmb_embed_dim[1], 0, 0, st), 'gemv lmb.2')
+                                        hid, hid, 0, 0, st), 'gemv lmb.2')
         _native.check(lib.lvae_gemv_f32(pk.p('adaln.w'), pk.p('adaln.b'), pk.emb.data_ptr(), pk.adaln.data_ptr(),
-                                        pk.adaln_total, self.lmb_embed_dim[1], 1, 0, st), 'gemv adaln')
-        self._cur_lmb = lmb
+                                        pk.adaln_total, hid, 1, 0, st), 'gemv adaln')
+        self._cur_lmb = key
 
-    def _plan(self, kind, B, a, b, group=0):
-        key = (kind, B, a, b, group, bool(getattr(self, 'side_streams', False)) and kind != 'dec', self._prec)
+    def _use_lmb(self, pl, start=0):
+        """Before a plan runs on the current stream: a plan with per-image lambdas gets rows start .. start + B of the table."""
+        if pl.vec:
+            pl.load_lmb(self._packed.adaln_tab, start)
+
+    def _plan(self, kind, B, a, b, group=0, vec=False):
+        key = (kind, B, a, b, group, bool(getattr(self, 'side_streams', False)) and kind != 'dec', self._prec) + (('vec',) if vec else ())
         pl = self._plans.get(key)
         if pl is None:
             pk = self._prepare()
             if kind == 'enc':
-                pl = _EncPlan(self, pk, B, a, b)
+                pl = _EncPlan(self, pk, B, a, b, vec=vec)
             elif kind == 'encb':
-                pl = _EncPlan(self, pk, B, a, b, with_bits=True)
+                pl = _EncPlan(self, pk, B, a, b, with_bits=True, vec=vec)
             elif kind == 'ence':
-                pl = _EncPlan(self, pk, B, a, b, chan_bits=True)
+                pl = _EncPlan(self, pk, B, a, b, chan_bits=True, vec=vec)
             elif kind == 'evald':
-                pl = _DecPlan(self, pk, B, a, b, evaluate=True)
+                pl = _DecPlan(self, pk, B, a, b, evaluate=True, vec=vec)
             else:
-                pl = _DecPlan(self, pk, B, a, b)
+                pl = _DecPlan(self, pk, B, a, b, vec=vec)
             self._plans[key] = pl
         return pl
 
@@ -676,23 +742,27 @@ class VariableRateLossyVAE(CodecBase):
     @torch.no_grad()
     @on_model_device
     def compress_batch(self, im, lmb=None):
-        """Encode a (B,3,H,W) batch -> list of B byte strings (each identical to `compress(im[b:b+1])`)."""
-        lmb = lmb or self.default_lmb
+        """Encode a (B,3,H,W) batch -> list of B byte strings.  lmb: None (default_lmb), a number, or a sequence / 1-D tensor of B
+        lambdas, one per image; string b is identical to `compress(im[b:b+1], lmb[b])` and carries its own lambda in its header."""
         assert im.dim() == 4 and im.shape[1] == 3 and not im.requires_grad
         B, _, H, W = im.shape
         assert (H % self.max_stride == 0) and (W % self.max_stride == 0), f'{im.shape=}'
+        lmb = self._lmb_arg(lmb, B)
+        vec = isinstance(lmb, list)
         self._prepare()
         self._set_lmb(lmb)
         tables = self._dg().host_tables()
-        header = struct.pack('f', lmb) + struct.pack('3H', 1, H // self.max_stride, W // self.max_stride)
+        shape_str = struct.pack('3H', 1, H // self.max_stride, W // self.max_stride)
+        headers = [struct.pack('f', v) + shape_str for v in (lmb if vec else [lmb] * B)]
         groups = self._groups(B, 'enc')
         nthreads = self._coder_threads_per_group(len(groups))
         T = self.timing
 
         def encode_group(g, start, n, stream):
-            pl = self._plan('enc', n, H, W, g)
+            pl = self._plan('enc', n, H, W, g, vec=vec)
             t0 = time.time()
             pl.im.view(n, 3, H, W).copy_(im[start:start + n])
+            self._use_lmb(pl, start)
             if self.native_group_loops:
                 # the loop below as ONE foreign call (csrc/plan_runtime.cpp::lvae_encode_blocks): no interpreter between the launches,
                 # the event waits and the coder calls, and no interpreter lock shared with the other group's thread
@@ -700,7 +770,7 @@ class VariableRateLossyVAE(CodecBase):
                 nl = len(pl.lat_shapes)
                 assert nl == self.num_latents
                 strings = [per_block[li][b] for b in range(n) for li in range(nl)]
-                res = [header + coding.pack_byte_strings(strings[b * nl:(b + 1) * nl]) for b in range(n)]
+                res = [headers[start + b] + coding.pack_byte_strings(strings[b * nl:(b + 1) * nl]) for b in range(n)]
                 if T is not None:
                     T['enc_group_total'] = T.get('enc_group_total', 0) + time.time() - t0
                 return res
@@ -742,7 +812,7 @@ class VariableRateLossyVAE(CodecBase):
             strings = [per_block[li][b] for b in range(n) for li in range(nl)]
             t_gpu_done = time.time()
             assert nl == self.num_latents
-            res = [header + coding.pack_byte_strings(strings[b * nl:(b + 1) * nl]) for b in range(n)]
+            res = [headers[start + b] + coding.pack_byte_strings(strings[b * nl:(b + 1) * nl]) for b in range(n)]
             if T is not None:
                 t3 = time.time()
                 T['enc_launch'] = T.get('enc_launch', 0) + t1 - t0
@@ -767,12 +837,15 @@ class VariableRateLossyVAE(CodecBase):
     @torch.no_grad()
     @on_model_device
     def decompress_batch(self, strings):
-        """Decode a list of byte strings that share lambda and latent shape -> (B,3,H,W) tensor in [0,1]."""
+        """Decode a list of byte strings that share the latent shape (their lambdas may differ) -> (B,3,H,W) tensor in [0,1]; row b
+        equals `decompress(strings[b])`."""
         t_entry = time.time()
         B = len(strings)
         heads = [struct.unpack('f', s[:4]) + struct.unpack('3H', s[4:10]) for s in strings]
-        lmb, nB, nH, nW = heads[0]
-        assert nB == 1 and all(h == heads[0] for h in heads), 'batch must share lambda and shape'
+        _, nB, nH, nW = heads[0]
+        assert nB == 1 and all(h[1:] == heads[0][1:] for h in heads), 'batch must share the latent shape'
+        lmb = self._lmb_arg([h[0] for h in heads], B, default=False)
+        vec = isinstance(lmb, list)
         if not all(isinstance(s, bytes) for s in strings):
             strings = [bytes(s) for s in strings]
         lv = None if self.native_group_loops else [coding.unpack_byte_string(s[10:]) for s in strings]
@@ -810,7 +883,8 @@ class VariableRateLossyVAE(CodecBase):
         def decode_group(g, start, n, stream):
             if T is not None:
                 T['dec_head_thread'] = T.get('dec_head_thread', 0) + time.time() - t_b          # submit -> the group's thread runs
-            pl = self._plan('dec', n, nH, nW, g)
+            pl = self._plan('dec', n, nH, nW, g, vec=vec)
+            self._use_lmb(pl, start)
             lo = 0
             if T is not None:
                 T['dec_head'] = T.get('dec_head', 0) + time.time() - t_entry                    # entry -> this group's first launch
@@ -845,7 +919,7 @@ class VariableRateLossyVAE(CodecBase):
         if T is not None:
             t_g = time.time()
         self._run_groups(decode_group, groups)
-        self._check_decoded(groups, lambda g, n: self._plan('dec', n, nH, nW, g))
+        self._check_decoded(groups, lambda g, n: self._plan('dec', n, nH, nW, g, vec=vec))
         if T is not None:
             T['dec_groups_total'] = T.get('dec_groups_total', 0) + time.time() - t_g
             T['dec_calls'] = T.get('dec_calls', 0) + 1
@@ -881,7 +955,8 @@ class VariableRateLossyVAE(CodecBase):
     @torch.no_grad()
     def compress_files(self, img_paths, output_paths, lmb=None, images=None):
         """Batched compress_file: images whose PADDED sizes agree are coded by one compress_batch call (GPU work batched, the B x 9
-        rANS streams coded in parallel); every output file is byte-identical to what compress_file writes for that image."""
+        rANS streams coded in parallel); every output file is byte-identical to what compress_file writes for that image.  lmb: one
+        lambda, or one per file (a sequence)."""
         from PIL import Image
         imgs = images if images is not None else [Image.open(p) for p in img_paths]      # `images`: already decoded PIL images
         ims = [coding.pil_to_tensor01(coding.pad_divisible_by(img, div=self.max_stride)) for img in imgs]
@@ -893,7 +968,7 @@ class VariableRateLossyVAE(CodecBase):
 
     @torch.no_grad()
     def decompress_files(self, bits_paths):
-        """Batched decompress_file for files of one latent shape and lambda -> list of (1,3,h,w) tensors (cropped)."""
+        """Batched decompress_file for files of one latent shape (any lambdas) -> list of (1,3,h,w) tensors (cropped)."""
         heads, bodies = [], []
         for p in bits_paths:
             with open(p, 'rb') as f:
@@ -901,6 +976,32 @@ class VariableRateLossyVAE(CodecBase):
                 bodies.append(f.read())
         out = self.decompress_batch(bodies)
         return [out[i:i + 1, :, :h, :w] for i, (h, w) in enumerate(heads)]
+
+    @torch.no_grad()
+    def compress_to_target(self, im, target_bytes, n_probe=8, max_rounds=50, tol=1, verbose=False):
+        """Rate targeting for ONE image (1,3,H,W): a multi-section search over lambda in log space (lvae/utils/rate_search.py).  Each
+        round encodes n_probe copies of the image in ONE compress_batch call at n_probe log-evenly spaced lambdas strictly inside the
+        current bracket (first: lmb_range) and narrows the bracket to the two neighbouring probes that enclose the target, so the
+        bracket shrinks by n_probe + 1 per round (a bisection: by 2, one encode per round).  It stops when a probe is within `tol` bytes
+        of the target, when the bracket's ends are adjacent fp32 values, or after max_rounds rounds.
+        The size counted is what compress_file would write: the stream plus the 4-byte '2H' prefix (image height, width).
+        Returns (string, lmb, n_rounds): the largest stream seen that is <= target_bytes (if none was, the smallest seen), the fp32
+        lambda it was coded at -- string == compress(im, lmb) -- and the number of rounds (= compress_batch calls)."""
+        from ...utils.rate_search import multisection_search
+        assert im.dim() == 4 and im.shape[0] == 1, f'a single image, got {im.shape=}'
+        rep = im.expand(n_probe, -1, -1, -1)
+        coded = []
+
+        def sizes_of(lmbs):
+            strings = self.compress_batch(rep[:len(lmbs)], lmbs)
+            sizes = [len(x) + 4 for x in strings]
+            coded.extend(strings)
+            if verbose:
+                print(f'round {len(coded) // len(lmbs) - 1}: ' + ', '.join(f'lmb={v:.3f} -> {n}B' for v, n in zip(lmbs, sizes)) + f', target={target_bytes}B')
+            return sizes
+        best, history, rounds = multisection_search(sizes_of, self.lmb_range[0], self.lmb_range[1], target_bytes, n_probe=n_probe,
+                                                    max_rounds=max_rounds, tol=tol)
+        return coded[best], float(np.float32(history[best][0])), rounds
 
     # ---- the eval-mode forward pass (reference qarv/model.py:258-363)
     def sample_lmb(self, n):
@@ -928,9 +1029,9 @@ class VariableRateLossyVAE(CodecBase):
         lmb = None (sample_lmb(B)), a float or a (B,) tensor.  Returns an OrderedDict: loss (0-d tensor on the model device,
         mean of kl + lmb * mse), bppix, mse (mean((x_hat - x_target)^2) on the UNCLAMPED reconstruction, batch mean), psnr (from the
         batch-mean MSE of im_hat) and im_hat (B, 3, H, W) when return_rec.
-        The plans take one lambda each: images that share a lambda run as one sub-batch ('ence' encode plan with the per-channel rate,
-        then the 'evald' decode plan fed with its symbols, the final conv stored raw + lvae_rd_image_f32), distinct lambdas as separate
-        sub-batches, and the results are put back in input order -- a batch with per-image lambdas gives the bits of per-image calls.
+        The whole batch is ONE run of the 'ence' encode plan (with the per-channel rate) and one of the 'evald' decode plan fed with its
+        symbols (the final conv stored raw + lvae_rd_image_f32), whatever the lambdas are: with distinct lambdas the plans read one AdaLN
+        vector pair per image (_NetPlan.vec) -- a batch with per-image lambdas gives the bits of per-image calls.
         Eval-mode (quantised) statistics only: model.train() adds no training noise.  Deterministic: two calls on the same input (and
         lambdas) return the same bits.  A NaN / inf raises NonFiniteError, an input outside [0, 1] AssertionError."""
         im = batch[0] if isinstance(batch, (tuple, list)) else batch
@@ -943,36 +1044,29 @@ class VariableRateLossyVAE(CodecBase):
         lmb = self.expand_to_tensor(lmb, n=nB)
         self._prepare()
         lv = [float(np.float32(v)) for v in lmb.tolist()]          # the plans' embedding is built from the fp32 value (_set_lmb)
-        groups = {}
-        for i, v in enumerate(lv):
-            groups.setdefault(v, []).append(i)
+        arg = self._lmb_arg(lv, nB)
+        vec = isinstance(arg, list)
         ndims = imC * imH * imW
-        kl = torch.empty(nB, dtype=torch.float64)
-        rd = torch.empty(nB, 2, dtype=torch.float64)
-        im_hat = torch.empty(nB, 3, imH, imW, device=self._dummy.device) if return_rec else None
-        for v, idx in groups.items():
-            n = len(idx)
-            sub = im if n == nB else im[torch.tensor(idx, device=im.device)]
-            self._set_lmb(v)
-            enc = self._plan('ence', n, imH, imW)
-            dec = self._plan('evald', n, imH // self.max_stride, imW // self.max_stride)
-            enc.im.view(n, 3, imH, imW).copy_(sub)
-            dec.im.view(n, 3, imH, imW).copy_(sub)
-            enc.run()
-            enc.fetch_status()
-            torch.cuda.current_stream(enc.device).synchronize()
-            enc.raise_if_flagged(where='in forward() (encoder)')
-            dec.sym_all.copy_(enc.sym_all)                          # the encoder stops at CompresionStopFlag: decode its symbols
-            dec.run()
-            dec.fetch_status()
-            torch.cuda.current_stream(dec.device).synchronize()
-            dec.raise_if_flagged(where='in forward() (decoder)')
-            kl_chan = enc.kl_chan.cpu()
-            nats = sum(kl_chan[o:o + n * z].view(n, z).sum(1) for o, (z, _) in zip(enc.chan_off, enc.lat_shapes))
-            kl[idx] = nats / ndims
-            rd[idx] = dec.rd_sums.view(n, 2).cpu()
-            if return_rec:
-                im_hat[idx] = dec.out
+        self._set_lmb(arg)
+        enc = self._plan('ence', nB, imH, imW, vec=vec)
+        dec = self._plan('evald', nB, imH // self.max_stride, imW // self.max_stride, vec=vec)
+        enc.im.view(nB, 3, imH, imW).copy_(im)
+        dec.im.view(nB, 3, imH, imW).copy_(im)
+        self._use_lmb(enc)
+        enc.run()
+        enc.fetch_status()
+        torch.cuda.current_stream(enc.device).synchronize()
+        enc.raise_if_flagged(where='in forward() (encoder)')
+        dec.sym_all.copy_(enc.sym_all)                              # the encoder stops at CompresionStopFlag: decode its symbols
+        self._use_lmb(dec)
+        dec.run()
+        dec.fetch_status()
+        torch.cuda.current_stream(dec.device).synchronize()
+        dec.raise_if_flagged(where='in forward() (decoder)')
+        kl_chan = enc.kl_chan.cpu()
+        kl = sum(kl_chan[o:o + nB * z].view(nB, z).sum(1) for o, (z, _) in zip(enc.chan_off, enc.lat_shapes)) / ndims
+        rd = dec.rd_sums.view(nB, 2).cpu()
+        im_hat = dec.out.clone() if return_rec else None
         distortion = rd[:, 0] / ndims
         lmb64 = torch.tensor(lv, dtype=torch.float64)
         stats = OrderedDict()
@@ -989,21 +1083,24 @@ class VariableRateLossyVAE(CodecBase):
     @on_model_device
     def estimate(self, im, lmb=None):
         """Eval-mode forward (forward_end2end in eval mode, qarv/model.py:94-97,294-315) without entropy coding:
-        returns (im_hat (B,3,H,W) in [0,1], nats (num_latents, B) float64 = sum(-ln P) per latent block and image)."""
-        lmb = lmb or self.default_lmb
+        returns (im_hat (B,3,H,W) in [0,1], nats (num_latents, B) float64 = sum(-ln P) per latent block and image).  lmb: one lambda or B."""
         B, _, H, W = im.shape
+        lmb = self._lmb_arg(lmb, B)
+        vec = isinstance(lmb, list)
         assert (H % self.max_stride == 0) and (W % self.max_stride == 0)
         self._prepare(); self._set_lmb(lmb)
-        enc = self._plan('encb', B, H, W)
-        dec = self._plan('dec', B, H // self.max_stride, W // self.max_stride)
+        enc = self._plan('encb', B, H, W, vec=vec)
+        dec = self._plan('dec', B, H // self.max_stride, W // self.max_stride, vec=vec)
         enc.im.view(B, 3, H, W).copy_(im)
         enc.nats.zero_()
+        self._use_lmb(enc)
         enc.run()
         enc.fetch_status()
         torch.cuda.current_stream(enc.device).synchronize()
         enc.raise_if_flagged(where='in estimate() (encoder)')
         # the encoder stops at CompresionStopFlag; reconstruct by feeding its symbols to the decode plan (same latent layout)
         dec.sym_all.copy_(enc.sym_all)
+        self._use_lmb(dec)
         dec.run()
         dec.fetch_status()
         torch.cuda.current_stream(dec.device).synchronize()
@@ -1028,8 +1125,11 @@ class VariableRateLossyVAE(CodecBase):
             B, _, nH, nW = latents[0].shape
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self._prepare(); self._set_lmb(float(lmb))
-        pl = self._plan('dec', B, nH, nW)
+        lmb = self._lmb_arg(lmb, B)                                  # one lambda, or one per image
+        vec = isinstance(lmb, list)
+        self._prepare(); self._set_lmb(lmb if vec else float(lmb))
+        pl = self._plan('dec', B, nH, nW, vec=vec)
+        self._use_lmb(pl)
         st = ctypes.c_void_p(torch.cuda.current_stream(pl.device).cuda_stream)
         lo, used = 0, []
         for li, cut in enumerate(pl.cuts):
@@ -1078,10 +1178,10 @@ class VariableRateLossyVAE(CodecBase):
         """What scripts/qarv/robust-decoding.py reads from forward_end2end(..., get_latent=True) in eval mode
         (qarv/model.py:94-97,294-315): per latent block the quantized latent z = symbols + prior mean as a (B, z, h, w) tensor and
         its rate in nats per image, (num_latents, B)."""
-        lmb = lmb or self.default_lmb
         B, _, H, W = im.shape
+        lmb = self._lmb_arg(lmb, B)
         _, nats = self.estimate(im, lmb)
-        dec = self._plan('dec', B, H // self.max_stride, W // self.max_stride)
+        dec = self._plan('dec', B, H // self.max_stride, W // self.max_stride, vec=isinstance(lmb, list))
         zs = []
         for li, (zdim, hw) in enumerate(dec.lat_shapes):
             o = dec.sym_off[li]
@@ -1091,23 +1191,64 @@ class VariableRateLossyVAE(CodecBase):
         return zs, nats
 
     @torch.no_grad()
-    def _self_evaluate(self, img_paths, lmb: float):
-        """qarv/model.py:427-473 (per-image loop; estimated bpp from the likelihoods, PSNR on the cropped reconstruction)."""
+    @on_model_device
+    def _estimate_chan(self, im, lmb):
+        """estimate() with a reproducible rate: (im_hat (B,3,H,W) in [0,1], nats (B,) float64 = sum(-ln P) per image).  The rate comes
+        from the per-channel kernel of forward() (lvae_gaussian_nll_chan_f32: fixed summation order per image and channel, no atomics)
+        instead of estimate's per-block atomic sums, and the channels of an image are added in a fixed order on the host, so an image's
+        value does not depend on the batch it is in or on the run."""
+        B, _, H, W = im.shape
+        lmb = self._lmb_arg(lmb, B)
+        vec = isinstance(lmb, list)
+        assert (H % self.max_stride == 0) and (W % self.max_stride == 0)
+        self._prepare(); self._set_lmb(lmb)
+        enc = self._plan('ence', B, H, W, vec=vec)
+        dec = self._plan('dec', B, H // self.max_stride, W // self.max_stride, vec=vec)
+        enc.im.view(B, 3, H, W).copy_(im)
+        self._use_lmb(enc)
+        enc.run()
+        enc.fetch_status()
+        torch.cuda.current_stream(enc.device).synchronize()
+        enc.raise_if_flagged(where='in self_evaluate() (encoder)')
+        dec.sym_all.copy_(enc.sym_all)
+        self._use_lmb(dec)
+        dec.run()
+        dec.fetch_status()
+        torch.cuda.current_stream(dec.device).synchronize()
+        dec.raise_if_flagged(where='in self_evaluate() (decoder)')
+        kl_chan = enc.kl_chan.cpu()
+        nats = torch.zeros(B, dtype=torch.float64)
+        for b in range(B):                      # blocks in order, each block's z channels as one 1-D sum: the same operations for any B
+            for o, (z, _) in zip(enc.chan_off, enc.lat_shapes):
+                nats[b] += kl_chan[o + b * z:o + (b + 1) * z].sum()
+        return dec.out.clone(), nats
+
+    @torch.no_grad()
+    def _evaluate_image(self, impath, lmbs):
+        """One image of self_evaluate at every lambda of `lmbs`, as ONE batch (the padded image replicated): [(kl, mse)] per lambda --
+        kl in nats per dimension of the original image, mse of the cropped, clamped reconstruction (qarv/model.py:427-473)."""
         from PIL import Image
+        img = Image.open(impath)
+        h, w = img.height, img.width
+        im = coding.pil_to_tensor01(coding.pad_divisible_by(img, div=self.max_stride)).unsqueeze_(0).to(self._dummy.device)
+        im_hat, nats = self._estimate_chan(im.expand(len(lmbs), -1, -1, -1), list(lmbs))
+        real = coding.pil_to_tensor01(img).to(im_hat.device)
+        return [(float(nats[j]) / (3 * h * w), float((real - im_hat[j, :, :h, :w]).square().mean())) for j in range(len(lmbs))]
+
+    @staticmethod
+    def _add_image_stats(tot, kl, mse, lmb, log2_e):
+        distortion = 4.0 * mse      # mse between (x_hat, x_target) in (-1,1) units; uses the CLAMPED reconstruction
+        tot['loss'] += kl + lmb * distortion
+        tot['bpp'] += kl * log2_e * 3
+        tot['psnr'] += -10 * math.log10(mse)
+
+    @torch.no_grad()
+    def _self_evaluate(self, img_paths, lmb: float):
+        """qarv/model.py:427-473 (per-image loop at one lambda; estimated bpp from the likelihoods, PSNR on the cropped reconstruction)."""
         tot = {'loss': 0.0, 'bpp': 0.0, 'psnr': 0.0}
         for impath in img_paths:
-            img = Image.open(impath)
-            h, w = img.height, img.width
-            im = coding.pil_to_tensor01(coding.pad_divisible_by(img, div=self.max_stride)).unsqueeze_(0).to(self._dummy.device)
-            im_hat, nats = self.estimate(im, lmb)
-            kl = float(nats.sum()) / (3 * h * w)                                   # nats per (original) dimension
-            real = coding.pil_to_tensor01(img).to(im_hat.device)
-            fake = im_hat[0, :, :h, :w]
-            mse = float((real - fake).square().mean())
-            distortion = 4.0 * mse      # mse between (x_hat, x_target) in (-1,1) units; uses the CLAMPED reconstruction
-            tot['loss'] += kl + lmb * distortion
-            tot['bpp'] += kl * self.log2_e * 3
-            tot['psnr'] += -10 * math.log10(mse)
+            (kl, mse), = self._evaluate_image(impath, [lmb])
+            self._add_image_stats(tot, kl, mse, lmb, self.log2_e)
         n = len(img_paths)
         out = {k: v / n for k, v in tot.items()}
         out['lambda'] = lmb
@@ -1115,16 +1256,25 @@ class VariableRateLossyVAE(CodecBase):
 
     @torch.no_grad()
     def self_evaluate(self, img_dir, lmb_range=None, steps=8, log_dir=None):
-        """qarv/model.py:491-507: estimated-rate RD sweep over `steps` lambdas log-spaced in lmb_range."""
+        """qarv/model.py:491-507: estimated-rate RD sweep over `steps` lambdas log-spaced in lmb_range.  Each image runs ONCE, as a batch
+        of `steps` copies with one lambda each; per lambda the images are accumulated in path order, so the result equals the
+        reference's loop (`_self_evaluate` per lambda) float for float.  The plans of an image size hold `steps` copies of its feature
+        maps at once: for multi-megapixel sets lower `steps` if memory is short."""
         from collections import defaultdict
         from pathlib import Path
         img_paths = sorted(Path(img_dir).rglob('*.*'))
         start, end = self.lmb_range if (lmb_range is None) else lmb_range
         lambdas = torch.linspace(math.log(start), math.log(end), steps=steps).exp().tolist()
+        tots = [{'loss': 0.0, 'bpp': 0.0, 'psnr': 0.0} for _ in lambdas]
+        for impath in img_paths:
+            for tot, lmb, (kl, mse) in zip(tots, lambdas, self._evaluate_image(impath, lambdas)):
+                self._add_image_stats(tot, kl, mse, lmb, self.log2_e)
         stats = defaultdict(list)
-        for lmb in lambdas:
-            for k, v in self._self_evaluate(img_paths, lmb).items():
-                stats[k].append(v)
+        n = len(img_paths)
+        for tot, lmb in zip(tots, lambdas):
+            for k, v in tot.items():
+                stats[k].append(v / n)
+            stats['lambda'].append(lmb)
         return stats
 
     # ---- debugging / test access (not on the hot path)
@@ -1136,11 +1286,12 @@ class VariableRateLossyVAE(CodecBase):
         and force_z (a list of (B, z, h, w) tensors or None per block) replaces the latent a block hands on to the blocks below
         it (teacher forcing: with the oracle's latents every block sees the oracle's inputs up to rounding noise, so a flip is
         never the cascade of an earlier one)."""
-        lmb = lmb or self.default_lmb
         B, _, H, W = im.shape
+        lmb = self._lmb_arg(lmb, B)                                  # one lambda, or one per image
         self._prepare(); self._set_lmb(lmb)
-        pl = self._plan('enc', B, H, W)
+        pl = self._plan('enc', B, H, W, vec=isinstance(lmb, list))
         pl.im.view(B, 3, H, W).copy_(im)
+        self._use_lmb(pl)
         if full or force_z is not None:
             return self._trace_blocks(pl, B, force_z)
         pl.run()
