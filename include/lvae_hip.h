@@ -482,6 +482,27 @@ int lvae_sqerr_sum_f32(const float* a, const float* b, double* out, int B, long 
  * identical, which the sharded evaluation needs to reproduce the single-process means bit for bit. */
 int lvae_sqerr_partials_f32(const float* a, const float* b, double* partials, int n_partials, long n, void* stream);
 
+/* ---- MS-SSIM (Wang, Simoncelli, Bovik 2003) of B image pairs in one call: data range 1, K1 = 0.01, K2 = 0.03, 11-tap Gaussian window
+ * (sigma 1.5, sum 1) as a valid correlation, 5 scales weighted (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), 2x2 mean pool between scales
+ * with zero padding of size % 2 in front of that axis (the zeros counted), per channel prod_s relu(cs_s)^w_s (ssim_4 at the last scale),
+ * mean over channels.
+ * x, y: fp32 NCHW planes with unit column stride; element (b, c, r, q) of x at x[b*x_img + c*x_plane + r*x_row + q] (strides in
+ * elements, likewise y).  hw: HOST array int[B][2], the valid extent (h_b, w_b) of image b inside its planes -- images of one call may
+ * differ in size (crops of one padded batch); nothing outside an extent is read.  Hmax / Wmax: at least every h_b / w_b.
+ * out[b] (device, double): the value of image b.  scale_means (device, double[B][5][C]): the cs-map mean of scales 0..3 and the
+ * ssim-map mean of scale 4 of every channel, before the relu.  ws: device scratch of at least lvae_msssim_workspace_bytes(B, C, Hmax,
+ * Wmax) bytes, 8-byte aligned; ws_bytes its size.
+ * Fixed launch sequence on `stream`, whatever B: one small host-to-device copy of hw, 5 scale launches (each also writes the next
+ * scale's planes), 1 finishing launch.  Windowed moments, maps and sums are fp64; no atomics, every sum in a fixed order that depends
+ * on the image's own extent alone, so a value neither depends on scheduling nor on what else is in the batch.
+ * -22 before any HIP call: a null pointer, B <= 0, C <= 0, min(h_b, w_b) <= 160 (the fifth scale would have no valid pixel), an extent
+ * beyond Hmax / Wmax or beyond what the strides hold, ws_bytes too small. */
+int lvae_msssim_f32(const float* x, long x_img, long x_plane, long x_row, const float* y, long y_img, long y_plane, long y_row,
+                    const int* hw, int B, int C, int Hmax, int Wmax, double* out, double* scale_means, void* ws, size_t ws_bytes,
+                    void* stream);
+/* Bytes of scratch lvae_msssim_f32 needs for these arguments; 0 when they are not acceptable (B, C <= 0, Hmax or Wmax <= 160). */
+size_t lvae_msssim_workspace_bytes(int B, int C, int Hmax, int Wmax);
+
 /* Stream ordering for launch plans with independent branches (lvae/engine.py: Plan.fork / Plan.join): an event without timing, and
  * "work enqueued on to_stream from now on runs after the work enqueued on from_stream so far" (hipEventRecord + hipStreamWaitEvent). */
 void* lvae_event_create(void);

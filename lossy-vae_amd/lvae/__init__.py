@@ -3,4 +3,5 @@ encode/decode path: get_model / compress_mode / compress / decompress / compress
 from .paths import known_datasets
 from .models.registry import get_model
 from . import models
+from . import metrics
 from .engine import NonFiniteError

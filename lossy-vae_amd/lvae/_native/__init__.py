@@ -132,6 +132,8 @@ SIGNATURES = {
     'lvae_encode_blocks': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     'lvae_sqerr_sum_f32': (_i, [_vp, _vp, _vp, _i, _l, _vp]),
     'lvae_sqerr_partials_f32': (_i, [_vp, _vp, _vp, _i, _l, _vp]),
+    'lvae_msssim_f32': (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'lvae_msssim_workspace_bytes': (_sz, [_i, _i, _i, _i]),
 }
 
 

@@ -46,7 +46,25 @@ def _mse(real, fake):
     return (real - fake.cpu()).square().mean().item()
 
 
-def _eval_one(model, impath, tmp_bits_dir, tag=''):
+METRICS = ('psnr', 'ms-ssim')
+
+
+def _want_ms_ssim(metrics):
+    """Validate the `metrics` option of the evaluation functions; 'psnr' (bpp, mse, psnr) is always reported."""
+    unknown = [m for m in metrics if m not in METRICS]
+    if unknown:
+        raise ValueError(f'unknown metrics {unknown}; known: {METRICS}')
+    return 'ms-ssim' in metrics
+
+
+def _ms_ssim(reals, fakes):
+    """Per-image MS-SSIM of a batch as floats: ONE lvae.metrics.ms_ssim call on the reconstructions where they lie (cropped views of the
+    decoder's padded batch on the GPU; CPU tensors of stub codecs take the fp64 path)."""
+    from .metrics import ms_ssim
+    return [float(v) for v in ms_ssim(reals, fakes).tolist()]
+
+
+def _eval_one(model, impath, tmp_bits_dir, tag='', ms=False):
     from PIL import Image
     tmp_bits_path = tmp_bits_dir / f'{impath.stem}{tag}.bits'
     model.compress_file(impath, tmp_bits_path)
@@ -55,13 +73,18 @@ def _eval_one(model, impath, tmp_bits_dir, tag=''):
     tmp_bits_path.unlink()
     real = pil_to_tensor01(Image.open(impath))
     mse = _mse(real, fake)
-    return {'bpp': float(num_bits / float(real.shape[1] * real.shape[2])), 'mse': float(mse),
-            'psnr': float(-10 * math.log10(mse))}
+    out = {'bpp': float(num_bits / float(real.shape[1] * real.shape[2])), 'mse': float(mse),
+           'psnr': float(-10 * math.log10(mse))}
+    if ms:
+        out['ms-ssim'] = _ms_ssim([real], [fake])[0]
+    return out
 
 
 @torch.no_grad()
-def imcoding_evaluate(model, dataset, progress=False):
-    """dict {bpp, mse, psnr}: dataset means of per-image values (evaluation.py:59-66)."""
+def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',)):
+    """dict {bpp, mse, psnr}: dataset means of per-image values (evaluation.py:59-66).  metrics=('psnr', 'ms-ssim') adds the key
+    'ms-ssim' (lvae.metrics.ms_ssim, mean over images); the other keys are the same floats either way."""
+    ms = _want_ms_ssim(metrics)
     assert hasattr(model, 'compress_file') and hasattr(model, 'decompress_file')
     img_paths = _list_images(dataset)
     tmp_bits_dir = Path(gettempdir())
@@ -71,7 +94,7 @@ def imcoding_evaluate(model, dataset, progress=False):
         from tqdm import tqdm
         it = tqdm(img_paths, ascii=True)
     for impath in it:
-        stats = _eval_one(model, impath, tmp_bits_dir)
+        stats = _eval_one(model, impath, tmp_bits_dir, ms=ms)
         n += 1
         for k, v in stats.items():      # timm AverageMeter: running sum / count
             sums[k] += v
@@ -171,37 +194,41 @@ def _decode_images(paths):
     return imgs
 
 
-def _eval_batch(model, paths, tmp_bits_dir, tag='', images=None):
+def _eval_batch(model, paths, tmp_bits_dir, tag='', images=None, ms=False):
     """_eval_one for a batch of same-padded-size images through the model's batched file API (bit-identical per image); every
     PNG is decoded once (`images`: already decoded by the prefetch thread)."""
     if not hasattr(model, 'compress_files'):
-        return [_eval_one(model, p, tmp_bits_dir, tag) for p in paths]
+        return [_eval_one(model, p, tmp_bits_dir, tag, ms) for p in paths]
     imgs = images if images is not None else _decode_images(paths)
     bits = [tmp_bits_dir / f'{p.stem}{tag}.{k}.bits' for k, p in enumerate(paths)]
     model.compress_files(paths, bits, images=imgs)
     fakes = model.decompress_files(bits)
-    out = []
+    out, reals = [], []
     for img, b, fake in zip(imgs, bits, fakes):
         num_bits = b.stat().st_size * 8
         b.unlink()
         real = pil_to_tensor01(img)
+        reals.append(real)
         mse = _mse(real, fake)
         out.append({'bpp': float(num_bits / float(real.shape[1] * real.shape[2])), 'mse': float(mse),
                     'psnr': float(-10 * math.log10(mse))})
+    if ms:
+        for o, v in zip(out, _ms_ssim(reals, fakes)):
+            o['ms-ssim'] = v
     return out
 
 
-def gather_stats(local, world, device=None):
-    """all_gather of per-image (index, bpp, mse, psnr) rows as float64; returns rows sorted by image index so that the
-    mean is computed in exactly the single-process order."""
+def gather_stats(local, world, device=None, columns=4):
+    """all_gather of per-image (index, bpp, mse, psnr) rows as float64 (`columns=5`: with ms-ssim behind them); returns rows sorted
+    by image index so that the mean is computed in exactly the single-process order."""
     import torch.distributed as dist
-    t = torch.tensor(local, dtype=torch.float64).reshape(-1, 4)
+    t = torch.tensor(local, dtype=torch.float64).reshape(-1, columns)
     if device is not None:
         t = t.to(device)
     counts = [torch.zeros(1, dtype=torch.int64, device=t.device) for _ in range(world)]
     dist.all_gather(counts, torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device))
     mx = max(int(c.item()) for c in counts)
-    pad = torch.zeros(mx, 4, dtype=torch.float64, device=t.device)
+    pad = torch.zeros(mx, columns, dtype=torch.float64, device=t.device)
     pad[:t.shape[0]] = t
     bufs = [torch.zeros_like(pad) for _ in range(world)]
     dist.all_gather(bufs, pad)
@@ -210,11 +237,13 @@ def gather_stats(local, world, device=None):
 
 
 @torch.no_grad()
-def imcoding_evaluate_sharded(model, dataset, partition='lpt', max_batch=8):
+def imcoding_evaluate_sharded(model, dataset, partition='lpt', max_batch=8, metrics=('psnr',)):
     """Same result as imcoding_evaluate (to the last bit: per-image values do not depend on batching, means are formed in image
     order), with the image list sharded over torch.distributed ranks: LPT by padded pixel count (`partition='stride'`:
-    rank::world), and inside a rank same-size images coded as batches of up to `max_batch`."""
+    rank::world), and inside a rank same-size images coded as batches of up to `max_batch`.  `metrics` as for imcoding_evaluate."""
     import torch.distributed as dist
+    ms = _want_ms_ssim(metrics)
+    keys = ('bpp', 'mse', 'psnr') + (('ms-ssim',) if ms else ())
     rank, world = dist.get_rank(), dist.get_world_size()
     img_paths = _list_images(dataset)
     tmp_bits_dir = Path(gettempdir())
@@ -233,14 +262,14 @@ def imcoding_evaluate_sharded(model, dataset, partition='lpt', max_batch=8):
             imgs = nxt.result()
             nxt = pool.submit(_decode_images, [img_paths[i] for i in batches[bi + 1]]) if bi + 1 < len(batches) else None
             stats = _eval_batch(model, [img_paths[i] for i in batch], tmp_bits_dir, tag=f'.r{rank}',
-                                images=imgs if hasattr(model, 'compress_files') else None)
+                                images=imgs if hasattr(model, 'compress_files') else None, ms=ms)
             for idx, s in zip(batch, stats):
-                local.append([float(idx), s['bpp'], s['mse'], s['psnr']])
+                local.append([float(idx)] + [s[k] for k in keys])
     dev = next(model.parameters()).device
-    rows = gather_stats(local, world, dev if dist.get_backend() == 'nccl' else None)
+    rows = gather_stats(local, world, dev if dist.get_backend() == 'nccl' else None, columns=1 + len(keys))
     assert rows.shape[0] == len(img_paths)
     out = {}
-    for j, k in enumerate(('bpp', 'mse', 'psnr')):
+    for j, k in enumerate(keys):
         acc = 0.0
         for v in rows[:, j + 1].tolist():
             acc += v

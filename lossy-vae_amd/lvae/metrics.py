@@ -1,0 +1,167 @@
+"""Image-quality metrics: PSNR and MS-SSIM.
+
+MS-SSIM is the form learned-compression evaluations use (Wang, Simoncelli, Bovik 2003): data range 1, K1 = 0.01, K2 = 0.03, an 11-tap
+Gaussian window (sigma 1.5) as a valid correlation, 5 scales with weights (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), a 2x2 mean pool with
+zero padding of size % 2 between them (avg_pool2d's defaults), per channel prod relu(cs_i)^w_i * relu(ssim_4)^w_4, mean over channels.
+Defined for min(h, w) > 160 only.
+
+CUDA tensors go through the HIP kernels (`lvae_msssim_f32`, csrc/metrics.hip: one fixed launch sequence for the whole batch, images of
+different sizes included, read where they lie); CPU tensors through an fp64 torch evaluation of the same definition.
+"""
+import ctypes
+import math
+
+import torch
+import torch.nn.functional as F
+
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MS_SSIM_MIN_SIDE = 161
+
+
+def psnr(real, fake):
+    """-10 log10(mean((real - fake)^2)) of one image pair in [0, 1], as a float."""
+    mse = (real.double() - fake.double().to(real.device)).square().mean().item()
+    return float(-10 * math.log10(mse))
+
+
+def ms_ssim_db(v):
+    """MS-SSIM on the decibel scale result tables use: -10 log10(1 - v)."""
+    if torch.is_tensor(v):
+        return -10 * torch.log10(1 - v)
+    return float(-10 * math.log10(1 - v))
+
+
+def _gauss():
+    c = torch.arange(11, dtype=torch.float64) - 5
+    g = torch.exp(-(c ** 2) / (2 * 1.5 * 1.5))
+    return g / g.sum()
+
+
+def _filt(x, g):
+    C = x.shape[1]
+    x = F.conv2d(x, g.view(1, 1, -1, 1).expand(C, 1, -1, 1), groups=C)
+    return F.conv2d(x, g.view(1, 1, 1, -1).expand(C, 1, 1, -1), groups=C)
+
+
+def _ms_ssim_cpu(x, y):
+    """(B, C, h, w) pairs, everything in fp64 -> ((B,) values, (B, 5, C) per-scale means before the relu)."""
+    x, y, g = x.double(), y.double(), _gauss()
+    C1, C2 = 1e-4, 9e-4
+    raw = []
+    for i in range(5):
+        mx, my = _filt(x, g), _filt(y, g)
+        sxx, syy, sxy = _filt(x * x, g) - mx * mx, _filt(y * y, g) - my * my, _filt(x * y, g) - mx * my
+        cs = (2 * sxy + C2) / (sxx + syy + C2)
+        if i < 4:
+            raw.append(cs.flatten(2).mean(-1))
+            pad = [s % 2 for s in x.shape[2:]]
+            x, y = F.avg_pool2d(x, 2, padding=pad), F.avg_pool2d(y, 2, padding=pad)
+        else:
+            raw.append((((2 * mx * my + C1) / (mx * mx + my * my + C1)) * cs).flatten(2).mean(-1))
+    m = torch.stack(raw, 1)                                                              # (B, 5, C)
+    w = torch.tensor(MS_SSIM_WEIGHTS, dtype=torch.float64).view(1, -1, 1)
+    return torch.prod(torch.relu(m) ** w, 1).mean(1), m
+
+
+def _items(t, name):
+    """A (B, C, H, W) tensor or a list of (1, C, h, w) / (C, h, w) tensors -> list of (C, h, w) views."""
+    if torch.is_tensor(t):
+        if t.dim() != 4:
+            raise ValueError(f'{name}: expected a (B, C, H, W) tensor or a list of images, got shape {tuple(t.shape)}')
+        return [t[i] for i in range(t.shape[0])]
+    out = []
+    for v in t:
+        if v.dim() == 4 and v.shape[0] == 1:
+            v = v[0]
+        if v.dim() != 3:
+            raise ValueError(f'{name}: list items are (1, C, h, w) or (C, h, w) tensors, got shape {tuple(v.shape)}')
+        out.append(v)
+    return out
+
+
+def _strided_batch(items, hmax, wmax, device):
+    """Address a list of (C, h_i, w_i) images as ONE base pointer + (image, plane, row) strides in elements.  Views cut from one tensor
+    with a common spacing (what decompress_files returns: out[i:i+1, :, :h, :w]) are used where they lie; anything else (CPU tensors,
+    separately allocated images, another dtype) is packed into one zero-padded (B, C, hmax, wmax) fp32 tensor on the device.
+    Returns (keep-alive tensor, data_ptr, strides)."""
+    v0 = items[0]
+    ok = all(v.device == device and v.dtype == torch.float32 and v.stride(2) == 1 and v.stride()[:2] == v0.stride()[:2]
+             and v.untyped_storage().data_ptr() == v0.untyped_storage().data_ptr() for v in items)
+    if ok:
+        plane, row = v0.stride(0), v0.stride(1)
+        step = (items[1].data_ptr() - v0.data_ptr()) // 4 if len(items) > 1 else 0
+        ok = all(v.data_ptr() - v0.data_ptr() == 4 * step * i for i, v in enumerate(items)) and (len(items) == 1 or step > 0)
+        # the extents have to fit the strides (an expanded or overlapping view does not): the native entry checks the same
+        ok = ok and all(v.shape[2] <= row and (v.shape[1] - 1) * row + v.shape[2] <= plane for v in items)
+        if ok:
+            return items, v0.data_ptr(), (step, plane, row)
+    C = v0.shape[0]
+    buf = torch.zeros(len(items), C, hmax, wmax, dtype=torch.float32, device=device)
+    for i, v in enumerate(items):
+        buf[i, :, :v.shape[1], :v.shape[2]].copy_(v, non_blocking=True)
+    return buf, buf.data_ptr(), (C * hmax * wmax, hmax * wmax, wmax)
+
+
+def _ms_ssim_hip(xs, ys, device):
+    from . import _native
+    B, C = len(xs), xs[0].shape[0]
+    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
+    hmax, wmax = max(h for h, _ in hw), max(w for _, w in hw)
+    L = _native.lib()
+    with torch.cuda.device(device):                  # the launches go to the current stream of the tensors' device
+        keep_x, px, sx = _strided_batch(xs, hmax, wmax, device)
+        keep_y, py, sy = _strided_batch(ys, hmax, wmax, device)
+        nbytes = int(L.lvae_msssim_workspace_bytes(B, C, hmax, wmax))
+        if nbytes == 0:
+            raise ValueError(f'ms_ssim: unsupported batch B={B} C={C} {hmax}x{wmax}')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        out = torch.empty(B, dtype=torch.float64, device=device)
+        means = torch.empty(B, 5, C, dtype=torch.float64, device=device)
+        hw_arr = (ctypes.c_int * (2 * B))(*[v for p in hw for v in p])
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _native.check(L.lvae_msssim_f32(px, *sx, py, *sy, hw_arr, B, C, hmax, wmax, out.data_ptr(), means.data_ptr(), ws.data_ptr(), nbytes, st),
+                      'msssim')
+    del keep_x, keep_y
+    return out, means
+
+
+def ms_ssim(real, fake, sizes=None, return_scales=False):
+    """MS-SSIM of B image pairs in [0, 1]: a float64 tensor of B values (on the inputs' device).
+
+    real, fake: (B, C, H, W) float tensors, or lists of (1, C, h, w) / (C, h, w) tensors whose sizes may differ from image to image; list
+    items may be views (crops of a padded batch are read in place).  sizes: per-image valid extents [(h, w), ...] inside padded tensors
+    (default: every item whole).  If either side is on a GPU the HIP kernels run there, on that device's current stream; two CPU inputs
+    take the fp64 torch path.  return_scales: also return the (B, 5, C) per-scale means (cs of scales 0..3, ssim of scale 4, before
+    the relu).  ValueError for mismatched shapes and for an image with min(h, w) <= 160."""
+    xs, ys = _items(real, 'real'), _items(fake, 'fake')
+    if len(xs) != len(ys) or not xs:
+        raise ValueError(f'ms_ssim: {len(xs)} real and {len(ys)} fake images')
+    if sizes is not None:
+        if len(sizes) != len(xs):
+            raise ValueError(f'ms_ssim: {len(sizes)} sizes for {len(xs)} images')
+        for i, (h, w) in enumerate(sizes):
+            if h > min(xs[i].shape[1], ys[i].shape[1]) or w > min(xs[i].shape[2], ys[i].shape[2]) or h <= 0 or w <= 0:
+                raise ValueError(f'ms_ssim: size {h}x{w} of image {i} exceeds its tensors {tuple(xs[i].shape)} / {tuple(ys[i].shape)}')
+        xs = [v[:, :h, :w] for v, (h, w) in zip(xs, sizes)]
+        ys = [v[:, :h, :w] for v, (h, w) in zip(ys, sizes)]
+    C = xs[0].shape[0]
+    for i, (a, b) in enumerate(zip(xs, ys)):
+        if a.shape != b.shape or a.shape[0] != C:
+            raise ValueError(f'ms_ssim: image {i} has shapes {tuple(a.shape)} and {tuple(b.shape)} (channels of image 0: {C})')
+        if not (a.is_floating_point() and b.is_floating_point()):
+            raise ValueError(f'ms_ssim: image {i} is not a float tensor in [0, 1]')
+        if min(a.shape[1:]) < MS_SSIM_MIN_SIDE:
+            raise ValueError(f'ms_ssim: image {i} is {a.shape[1]}x{a.shape[2]}; MS-SSIM needs min(h, w) > 160 (5 scales of an 11-tap window)')
+    devs = {v.device for v in xs + ys if v.is_cuda}
+    if len(devs) > 1:
+        raise ValueError(f'ms_ssim: inputs on several GPUs {sorted(map(str, devs))}')
+    if devs:
+        out, means = _ms_ssim_hip(xs, ys, devs.pop())
+        return (out, means) if return_scales else out
+    vals, means = [], []
+    for a, b in zip(xs, ys):                       # per image: sizes may differ, and a value does not depend on the rest of the batch
+        v, m = _ms_ssim_cpu(a.unsqueeze(0), b.unsqueeze(0))
+        vals.append(v)
+        means.append(m)
+    out = torch.cat(vals)
+    return (out, torch.cat(means)) if return_scales else out

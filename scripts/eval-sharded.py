@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Multi-GPU evaluation (BASELINE.json config 4): one process per GPU, the image list sharded rank::world,
-one all_gather of per-image (index, bpp, mse, psnr) rows over RCCL, means formed in image order on rank 0.
+one all_gather of per-image (index, bpp, mse, psnr[, ms-ssim with --ms-ssim]) rows over RCCL, means formed in image order on rank 0.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 scripts/eval-sharded.py \
         -m qarv_base -a "pretrained='qarv_base.pt'" -n clic2022-test -l 16 2048 -s 8
@@ -33,6 +33,7 @@ def main():
     ap.add_argument('--backend', type=str, default='nccl')
     ap.add_argument('--max-batch', type=int, default=8, help='same-size images coded per batch inside a rank (1 = one image at a time)')
     ap.add_argument('--partition', type=str, default='lpt', choices=['lpt', 'stride'], help='LPT by padded pixels, or rank::world')
+    ap.add_argument('--ms-ssim', action='store_true', help="also report 'ms-ssim' (lvae.metrics.ms_ssim on the GPU; images need min(h, w) > 160)")
     args = ap.parse_args()
     rank, world, local = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('LOCAL_RANK', 0))
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1'); os.environ.setdefault('MASTER_PORT', '29511')
@@ -79,7 +80,8 @@ def main():
             model.default_lmb = lmb
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        res = imcoding_evaluate_sharded(model, dataset, partition=args.partition, max_batch=args.max_batch)
+        res = imcoding_evaluate_sharded(model, dataset, partition=args.partition, max_batch=args.max_batch,
+                                        metrics=('psnr', 'ms-ssim') if args.ms_ssim else ('psnr',))
         dt = time.time() - t0
         if rank == 0:
             print(f'lambda={lmb}: {res}', flush=True)
