@@ -503,6 +503,31 @@ int lvae_msssim_f32(const float* x, long x_img, long x_plane, long x_row, const 
 /* Bytes of scratch lvae_msssim_f32 needs for these arguments; 0 when they are not acceptable (B, C <= 0, Hmax or Wmax <= 160). */
 size_t lvae_msssim_workspace_bytes(int B, int C, int Hmax, int Wmax);
 
+/* ---- 8-bit images in and out of the codec (csrc/image_io.hip).  Both entries take B images whose 8-bit side is interleaved RGB
+ * (HWC, 3 bytes per pixel) and whose fp32 side is NCHW planes with unit column stride, and read HOST arrays describing the 8-bit side:
+ * image b at the DEVICE address u8[b], its rows u8_row[b] bytes apart (>= 3 * w_b), its valid extent hw[2b], hw[2b + 1] = (h_b, w_b) --
+ * passed like the hw array of lvae_msssim_f32; the arrays are read before the call returns (they travel as kernel arguments, 16 images
+ * per launch: no copy to the device, no scratch).  Base addresses and row strides may have any alignment: the 12 bytes of 4 pixels move
+ * as dwords where they start on a dword boundary, as bytes where not; the fp32 side moves as 16-byte vectors where base, strides and
+ * width are multiples of 4 elements, as scalars where not.  Nothing outside an extent is read (u8_to_f32) or written (f32_to_u8).
+ * -22 before any HIP call: a null pointer (an entry of src / dst included), B <= 0, H or W <= 0, an extent that is 0 or beyond (H, W),
+ * a row stride below 3 * w_b, image / plane / row strides that do not hold (H, W).
+ * Both entries were added without a change to lvae_abi_version() (no existing signature changed): a client built against an older
+ * library of the same version probes for the symbols (dlsym) before it relies on them.
+ *
+ * lvae_image_u8_to_f32: dst[b*dst_img + c*H*W + y*W + x] = (float)v / 255 (IEEE division: the bits of torch's .to(float32).div(255);
+ * a multiplication by 1/255 differs in 126 of the 256 values), v = byte c of pixel (min(y, h_b - 1), min(x, w_b - 1)) of image b, for
+ * the whole canvas (H, W): pixels right of / below the extent repeat the nearest valid one (np.pad mode='edge', the padding of
+ * lvae/utils/coding.py::pad_divisible_by).  dst_img (elements, >= 3*H*W) lets the planes land in an encode plan's input buffer or in a
+ * larger batch tensor; nothing between the images' planes is written. */
+int lvae_image_u8_to_f32(const uint8_t* const* src, const long* src_row, const int* hw, int B, float* dst, long dst_img, int H, int W,
+                         void* stream);
+/* lvae_image_f32_to_u8: byte c of pixel (y, x) of image b, y < h_b, x < w_b, = rint(clamp(s, 0, 1) * 255) with
+ * s = src[b*src_img + c*src_plane + y*src_row + x] (strides in elements: views of a decoder's padded batch (B, 3, H, W) are read in
+ * place), the product formed in fp32, ties to even -- torch.round(x.clamp(0, 1) * 255) -- and NaN -> 0. */
+int lvae_image_f32_to_u8(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B,
+                         uint8_t* const* dst, const long* dst_row, void* stream);
+
 /* Stream ordering for launch plans with independent branches (lvae/engine.py: Plan.fork / Plan.join): an event without timing, and
  * "work enqueued on to_stream from now on runs after the work enqueued on from_stream so far" (hipEventRecord + hipStreamWaitEvent). */
 void* lvae_event_create(void);

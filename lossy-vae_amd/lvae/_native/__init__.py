@@ -134,6 +134,8 @@ SIGNATURES = {
     'lvae_sqerr_partials_f32': (_i, [_vp, _vp, _vp, _i, _l, _vp]),
     'lvae_msssim_f32': (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'lvae_msssim_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'lvae_image_u8_to_f32': (_i, [_vp, _vp, _vp, _i, _vp, _l, _i, _i, _vp]),
+    'lvae_image_f32_to_u8': (_i, [_vp, _l, _l, _l, _i, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 

@@ -64,17 +64,36 @@ def _ms_ssim(reals, fakes):
     return [float(v) for v in ms_ssim(reals, fakes).tolist()]
 
 
+def _u8_codec(model):
+    """True for the package's codecs on a GPU: the evaluation then uploads each original ONCE, as the bytes its PNG held, codes it from
+    there (compress_images: the bytes compress_file writes) and makes the fp32 `real` of the metrics on the device (to_float01).
+    Anything else with compress_file / decompress_file (CPU stub codecs in the tests) keeps the host float path."""
+    if not hasattr(model, 'compress_images'):
+        return None
+    dev = next(model.parameters()).device
+    return dev if dev.type == 'cuda' else None
+
+
+def _stats(num_bits, real, mse):
+    return {'bpp': float(num_bits / float(real.shape[1] * real.shape[2])), 'mse': float(mse), 'psnr': float(-10 * math.log10(mse))}
+
+
 def _eval_one(model, impath, tmp_bits_dir, tag='', ms=False):
     from PIL import Image
     tmp_bits_path = tmp_bits_dir / f'{impath.stem}{tag}.bits'
-    model.compress_file(impath, tmp_bits_path)
+    dev = _u8_codec(model)
+    if dev is not None:
+        from .utils.image import load_u8, to_float01
+        u8 = load_u8(impath).to(dev, non_blocking=True)
+        with open(tmp_bits_path, 'wb') as f:
+            f.write(model.compress_images([u8])[0])
+    else:
+        model.compress_file(impath, tmp_bits_path)
     num_bits = tmp_bits_path.stat().st_size * 8
     fake = model.decompress_file(tmp_bits_path)
     tmp_bits_path.unlink()
-    real = pil_to_tensor01(Image.open(impath))
-    mse = _mse(real, fake)
-    out = {'bpp': float(num_bits / float(real.shape[1] * real.shape[2])), 'mse': float(mse),
-           'psnr': float(-10 * math.log10(mse))}
+    real = to_float01([u8], device=dev)[0][0] if dev is not None else pil_to_tensor01(Image.open(impath))
+    out = _stats(num_bits, real, _mse(real, fake))
     if ms:
         out['ms-ssim'] = _ms_ssim([real], [fake])[0]
     return out
@@ -201,17 +220,24 @@ def _eval_batch(model, paths, tmp_bits_dir, tag='', images=None, ms=False):
         return [_eval_one(model, p, tmp_bits_dir, tag, ms) for p in paths]
     imgs = images if images is not None else _decode_images(paths)
     bits = [tmp_bits_dir / f'{p.stem}{tag}.{k}.bits' for k, p in enumerate(paths)]
-    model.compress_files(paths, bits, images=imgs)
+    dev = _u8_codec(model)
+    if dev is not None:
+        from .utils.image import load_u8, to_float01
+        u8 = [load_u8(img).to(dev, non_blocking=True) for img in imgs]
+        for blob, b in zip(model.compress_images(u8), bits):
+            with open(b, 'wb') as f:
+                f.write(blob)
+        x, sizes = to_float01(u8, device=dev)             # one launch: the batch's originals as fp32, cropped views below
+        reals = [x[i, :, :h, :w] for i, (h, w) in enumerate(sizes)]
+    else:
+        model.compress_files(paths, bits, images=imgs)
+        reals = [pil_to_tensor01(img) for img in imgs]
     fakes = model.decompress_files(bits)
-    out, reals = [], []
-    for img, b, fake in zip(imgs, bits, fakes):
+    out = []
+    for real, b, fake in zip(reals, bits, fakes):
         num_bits = b.stat().st_size * 8
         b.unlink()
-        real = pil_to_tensor01(img)
-        reals.append(real)
-        mse = _mse(real, fake)
-        out.append({'bpp': float(num_bits / float(real.shape[1] * real.shape[2])), 'mse': float(mse),
-                    'psnr': float(-10 * math.log10(mse))})
+        out.append(_stats(num_bits, real, _mse(real, fake)))
     if ms:
         for o, v in zip(out, _ms_ssim(reals, fakes)):
             o['ms-ssim'] = v

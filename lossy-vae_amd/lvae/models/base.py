@@ -3,6 +3,7 @@ group's host rANS coding overlaps the other group's GPU work), coder thread budg
 import ctypes
 import functools
 import logging
+import math
 import os
 
 import numpy as np
@@ -420,6 +421,80 @@ class CodecBase(nn.Module):
                 err = err or e
         if err is not None:
             raise err
+
+    # ---- 8-bit images in and out (lvae/utils/image.py, csrc/image_io.hip): the file formats of compress_file / decompress_file as bytes
+    variable_rate = False                 # compress_batch takes `lmb`
+
+    def _pack_blob(self, body, size):
+        """One compress_batch result + the image's own (h, w) -> the bytes compress_file writes (the model's container)."""
+        raise NotImplementedError
+
+    def _unpack_blob(self, blob):
+        """Inverse of _pack_blob: (decompress_batch input, (h, w), a key that blobs of one decompress_batch call share)."""
+        raise NotImplementedError
+
+    @staticmethod
+    def _load_input(dst, im, u8, start, n):
+        """Images start .. start + n of a compress_batch call -> `dst`, an (n, 3, H, W) view of an encode plan's input, on the current
+        stream: a copy of the fp32 rows of `im`, or -- `u8`, a utils.image.U8Batch -- the conversion kernel writing there directly."""
+        if u8 is not None:
+            u8.fill(dst, start, n)
+        else:
+            dst.copy_(im[start:start + n])
+
+    @torch.no_grad()
+    def compress_images(self, images, lmb=None):
+        """A list of (h, w, 3) uint8 images -- tensors on the CPU or the model's device, numpy arrays, PIL images -- whose sizes PADDED to
+        multiples of max_stride agree (their own sizes may differ) -> list of bytes, element i being exactly the file compress_file
+        writes for image i.  lmb: as in compress_batch (variable-rate models only).  The bytes of each image go to the device as they
+        are (3 per pixel, unpadded); padding and the division by 255 happen where each pipeline group's plan reads its input."""
+        from ..utils.image import U8Batch
+        batch = U8Batch(images, self.max_stride, self._dummy.device)
+        _, _, H, W = batch.shape
+        d = self.max_stride
+        assert all((d * math.ceil(h / d), d * math.ceil(w / d)) == (H, W) for h, w in batch.sizes), 'compress_images: padded sizes differ'
+        if self.variable_rate:
+            bodies = self.compress_batch(None, lmb=lmb, u8=batch)
+        else:
+            if lmb is not None:
+                raise ValueError(f'{type(self).__name__} is a fixed-rate model: it takes no lmb')
+            bodies = self.compress_batch(None, u8=batch)
+        return [self._pack_blob(body, size) for body, size in zip(bodies, batch.sizes)]
+
+    @torch.no_grad()
+    def decompress_images(self, blobs):
+        """compress_images / compress_file bytes -> list of (h, w, 3) uint8 tensors on the model's device, each cropped to the size in
+        its header and rounded on the device (round-half-even of x * 255).  Blobs that share a latent shape are decoded as one batch."""
+        from ..utils.image import to_u8
+        parsed = [self._unpack_blob(b) for b in blobs]
+        by_key = {}
+        for i, (_, _, key) in enumerate(parsed):
+            by_key.setdefault(key, []).append(i)
+        out = [None] * len(blobs)
+        for idxs in by_key.values():
+            x = self.decompress_batch([parsed[i][0] for i in idxs])
+            for i, u8 in zip(idxs, to_u8(x, [parsed[i][1] for i in idxs])):
+                out[i] = u8
+        return out
+
+    @torch.no_grad()
+    def decompress_to_files(self, bits_paths, image_paths):
+        """Files written by compress_file(s) -> PNGs: decompress_images, one device-to-host copy of h * w * 3 bytes per image, save_u8."""
+        from ..utils.image import save_u8
+        blobs = []
+        for p in bits_paths:
+            with open(p, 'rb') as f:
+                blobs.append(f.read())
+        ims = self.decompress_images(blobs)
+        host = [torch.empty(t.shape, dtype=torch.uint8, pin_memory=True).copy_(t, non_blocking=True) for t in ims]
+        torch.cuda.current_stream(self._dummy.device).synchronize()
+        for t, p in zip(host, image_paths):
+            save_u8(t, p)
+
+    def _compress_to_files(self, images, output_paths, lmb=None):
+        for blob, out in zip(self.compress_images(images, lmb=lmb), output_paths):
+            with open(out, 'wb') as f:
+                f.write(blob)
 
     # ---- test access (not on the hot path)
     @torch.no_grad()

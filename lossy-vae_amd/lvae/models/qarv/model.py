@@ -741,12 +741,15 @@ class VariableRateLossyVAE(CodecBase):
 
     @torch.no_grad()
     @on_model_device
-    def compress_batch(self, im, lmb=None):
+    def compress_batch(self, im, lmb=None, u8=None):
         """Encode a (B,3,H,W) batch -> list of B byte strings.  lmb: None (default_lmb), a number, or a sequence / 1-D tensor of B
-        lambdas, one per image; string b is identical to `compress(im[b:b+1], lmb[b])` and carries its own lambda in its header."""
-        assert im.dim() == 4 and im.shape[1] == 3 and not im.requires_grad
-        B, _, H, W = im.shape
-        assert (H % self.max_stride == 0) and (W % self.max_stride == 0), f'{im.shape=}'
+        lambdas, one per image; string b is identical to `compress(im[b:b+1], lmb[b])` and carries its own lambda in its header.
+        u8 (compress_images): a utils.image.U8Batch in place of `im` (then None) -- 8-bit images already on the device, converted by
+        lvae_image_u8_to_f32 straight into each group's plan input."""
+        if u8 is None:
+            assert im.dim() == 4 and im.shape[1] == 3 and not im.requires_grad
+        B, _, H, W = u8.shape if u8 is not None else im.shape
+        assert (H % self.max_stride == 0) and (W % self.max_stride == 0), f'{(B, 3, H, W)=}'
         lmb = self._lmb_arg(lmb, B)
         vec = isinstance(lmb, list)
         self._prepare()
@@ -761,7 +764,7 @@ class VariableRateLossyVAE(CodecBase):
         def encode_group(g, start, n, stream):
             pl = self._plan('enc', n, H, W, g, vec=vec)
             t0 = time.time()
-            pl.im.view(n, 3, H, W).copy_(im[start:start + n])
+            self._load_input(pl.im.view(n, 3, H, W), im, u8, start, n)
             self._use_lmb(pl, start)
             if self.native_group_loops:
                 # the loop below as ONE foreign call (csrc/plan_runtime.cpp::lvae_encode_blocks): no interpreter between the launches,
@@ -930,17 +933,18 @@ class VariableRateLossyVAE(CodecBase):
         """qarv/model.py:531-557."""
         return self.decompress_batch([string])
 
+    variable_rate = True
+
+    def _pack_blob(self, body, size):
+        return struct.pack('2H', *size) + body
+
+    def _unpack_blob(self, blob):
+        return blob[4:], struct.unpack('2H', blob[:4]), bytes(blob[8:14])         # key: the 3H latent shape behind the lambda
+
     @torch.no_grad()
     def compress_file(self, img_path, output_path, lmb=None):
         """qarv/model.py:559-570."""
-        from PIL import Image
-        img = Image.open(img_path)
-        img_padded = coding.pad_divisible_by(img, div=self.max_stride)
-        im = coding.pil_to_tensor01(img_padded).unsqueeze_(0).to(device=self._dummy.device)
-        body_str = self.compress(im, lmb=lmb)
-        header_str = struct.pack('2H', img.height, img.width)
-        with open(output_path, 'wb') as f:
-            f.write(header_str + body_str)
+        self._compress_to_files([img_path], [output_path], lmb=lmb)
 
     @torch.no_grad()
     def decompress_file(self, bits_path):
@@ -956,15 +960,8 @@ class VariableRateLossyVAE(CodecBase):
     def compress_files(self, img_paths, output_paths, lmb=None, images=None):
         """Batched compress_file: images whose PADDED sizes agree are coded by one compress_batch call (GPU work batched, the B x 9
         rANS streams coded in parallel); every output file is byte-identical to what compress_file writes for that image.  lmb: one
-        lambda, or one per file (a sequence)."""
-        from PIL import Image
-        imgs = images if images is not None else [Image.open(p) for p in img_paths]      # `images`: already decoded PIL images
-        ims = [coding.pil_to_tensor01(coding.pad_divisible_by(img, div=self.max_stride)) for img in imgs]
-        assert all(t.shape == ims[0].shape for t in ims), 'compress_files: padded sizes differ'
-        bodies = self.compress_batch(torch.stack(ims).to(device=self._dummy.device), lmb=lmb)
-        for img, body, out in zip(imgs, bodies, output_paths):
-            with open(out, 'wb') as f:
-                f.write(struct.pack('2H', img.height, img.width) + body)
+        lambda, or one per file (a sequence).  `images`: the files' contents, already decoded (PIL images or uint8 tensors)."""
+        self._compress_to_files(images if images is not None else list(img_paths), output_paths, lmb=lmb)
 
     @torch.no_grad()
     def decompress_files(self, bits_paths):

@@ -18,6 +18,7 @@ decoder by lvae_pixel_sample_f32; `forward_get_latents` takes each block's -ln P
 quantize launch; `inpaint` alternates the two.
 """
 import ctypes
+import io
 import math
 import pickle
 from collections import OrderedDict
@@ -605,11 +606,13 @@ class HierarchicalVAE(CodecBase):
 
     @torch.no_grad()
     @on_model_device
-    def compress_batch(self, im):
-        """(B,3,H,W) -> list of B compressed objects, each `[ [bytes] x 12, (1, C, H/64, W/64) ]` as `compress()` returns."""
-        assert im.dim() == 4 and im.shape[1] == 3
-        B, _, H, W = im.shape
-        assert H % self.max_stride == 0 and W % self.max_stride == 0, f'{im.shape=}'
+    def compress_batch(self, im, u8=None):
+        """(B,3,H,W) -> list of B compressed objects, each `[ [bytes] x 12, (1, C, H/64, W/64) ]` as `compress()` returns.
+        u8 (compress_images): a utils.image.U8Batch in place of `im` (then None), converted straight into each group's plan input."""
+        if u8 is None:
+            assert im.dim() == 4 and im.shape[1] == 3
+        B, _, H, W = u8.shape if u8 is not None else im.shape
+        assert H % self.max_stride == 0 and W % self.max_stride == 0, f'{(B, 3, H, W)=}'
         self._prepare()
         tables = self._dg().host_tables()
         groups = self._groups(B, 'enc')
@@ -618,7 +621,7 @@ class HierarchicalVAE(CodecBase):
 
         def encode_group(g, start, n, stream):
             pl = self._plan('enc', n, H, W, g)
-            pl.im.view(n, 3, H, W).copy_(im[start:start + n])
+            self._load_input(pl.im.view(n, 3, H, W), im, u8, start, n)
             pl.run(stream=stream.cuda_stream)
             pl.sym_host.copy_(pl.sym_all, non_blocking=True)
             pl.idx_host.copy_(pl.idx_all, non_blocking=True)
@@ -716,17 +719,21 @@ class HierarchicalVAE(CodecBase):
         """(:670-687)."""
         return self.decompress_batch([compressed_object])
 
+    def _pack_blob(self, body, size):
+        """(:689-707): pickle of [strings..., feature shape, (h, w)], written through a file object as compress_file always has."""
+        buf = io.BytesIO()
+        pickle.dump(body + [tuple(size)], file=buf)
+        return buf.getvalue()
+
+    def _unpack_blob(self, blob):
+        obj = pickle.loads(blob)
+        size = obj.pop()
+        return obj, size, tuple(obj[-2 if isinstance(self.out_net, GaussianNLLOutParams) else -1])
+
     @torch.no_grad()
     def compress_file(self, img_path, output_path):
         """(:689-707): pickle of [strings..., feature shape, (h, w)]."""
-        from PIL import Image
-        img = Image.open(img_path)
-        img_padded = coding.pad_divisible_by(img, div=self.max_stride)
-        im = coding.pil_to_tensor01(img_padded).unsqueeze_(0).to(device=self._dummy.device)
-        obj = self.compress(im)
-        obj.append((img.height, img.width))
-        with open(output_path, 'wb') as f:
-            pickle.dump(obj, file=f)
+        self._compress_to_files([img_path], [output_path])
 
     @torch.no_grad()
     def decompress_file(self, bits_path):
@@ -738,16 +745,9 @@ class HierarchicalVAE(CodecBase):
 
     @torch.no_grad()
     def compress_files(self, img_paths, output_paths, images=None):
-        """Batched compress_file (same padded size): one compress_batch call; files identical to compress_file's."""
-        from PIL import Image
-        imgs = images if images is not None else [Image.open(p) for p in img_paths]      # `images`: already decoded PIL images
-        ims = [coding.pil_to_tensor01(coding.pad_divisible_by(img, div=self.max_stride)) for img in imgs]
-        assert all(t.shape == ims[0].shape for t in ims), 'compress_files: padded sizes differ'
-        objs = self.compress_batch(torch.stack(ims).to(device=self._dummy.device))
-        for img, obj, out in zip(imgs, objs, output_paths):
-            obj.append((img.height, img.width))
-            with open(out, 'wb') as f:
-                pickle.dump(obj, file=f)
+        """Batched compress_file (same padded size): one compress_batch call; files identical to compress_file's.  `images`: the files'
+        contents, already decoded (PIL images or uint8 tensors)."""
+        self._compress_to_files(images if images is not None else list(img_paths), output_paths)
 
     @torch.no_grad()
     def decompress_files(self, bits_paths):

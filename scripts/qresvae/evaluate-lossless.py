@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Lossless compression rate of qres34m_lossless over an image folder (the reference's scripts/qresvae/evaluate-lossless.py:14-62 on
-this package): compress_file -> file size -> decompress_file, asserting that every image is reproduced bit-exactly.
+this package): compress_file -> file size -> decompress_images (8-bit on the device), asserting that every image is reproduced bit-exactly.
 
     python scripts/qresvae/evaluate-lossless.py --root /path/to/kodak [--weights qres34m-lossless.pt]
     python scripts/qresvae/evaluate-lossless.py --synthetic 4            # seeded weights + seeded images (no network here)
@@ -26,12 +26,11 @@ def evaluate_model(model, img_paths):
     for impath in img_paths:
         model.compress_file(impath, tmp_bit_path)
         num_bits = tmp_bit_path.stat().st_size * 8
-        fake = model.decompress_file(tmp_bit_path).squeeze(0).cpu()
+        fake = model.decompress_images([tmp_bit_path.read_bytes()])[0].cpu()                         # (h, w, 3) uint8, rounded on the device
         tmp_bit_path.unlink()
-        real = torch.from_numpy(np.asarray(Image.open(impath).convert('RGB'))).permute(2, 0, 1)       # uint8
-        fake = torch.round(fake * 255.0).to(dtype=torch.uint8)
+        real = torch.from_numpy(np.asarray(Image.open(impath).convert('RGB')))                       # uint8
         assert torch.equal(real, fake), f'{impath}: not lossless'
-        bpp = num_bits / float(real.shape[1] * real.shape[2])
+        bpp = num_bits / float(real.shape[0] * real.shape[1])
         accumulated_bpp += float(bpp)
         print(f'image {Path(impath).stem}: bpp={bpp:.4f}')
     return accumulated_bpp / len(img_paths)
