@@ -5,15 +5,17 @@ import functools
 import logging
 import math
 import os
+import threading
+import time
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from ..engine import NonFiniteError
+from .. import _native
+from ..engine import NonFiniteError, Plan
+from .entropy_coding import rans_decode_streams
 
-
-import threading
 _W16_LOCK = threading.Lock()
 
 
@@ -142,7 +144,7 @@ class LazyW16:
         with _W16_LOCK:
             h = self.map.get(ptr)
             if h is None:
-                c = (pack_bf16x3(t) if self.mode == 'bf16x3' else pack_mxfp8(t) if self.mode == 'mxfp8'
+                c = (pack_bf16x3(t) if self.mode == 'bf16x3' else pack_mxfp8(t) if self.mode == 'fp8'
                      else pack_f16x2(t) if self.mode == 'f16x2' else pack_f16x2_k32(t) if self.mode == 'f16x2k32'
                      else (pack_mxfp8_q8(t) if t.shape[1] % 64 == 0 else None) if self.mode == 'mxfp8q8'
                      else t.to(torch.bfloat16).contiguous())
@@ -154,36 +156,6 @@ class LazyW16:
         return h or None
 
 
-def bf16x3_weight_map(tensors):
-    m = LazyW16(tensors, 'bf16x3')
-    return m, m.keep
-
-
-def bf16_weight_map(tensors):
-    m = LazyW16(tensors, 'bf16')
-    return m, m.keep
-
-
-def f16x2_weight_map(tensors):
-    m = LazyW16(tensors, 'f16x2')
-    return m, m.keep
-
-
-def f16x2k32_weight_map(tensors):
-    m = LazyW16(tensors, 'f16x2k32')
-    return m, m.keep
-
-
-def mxfp8q8_weight_map(tensors):
-    m = LazyW16(tensors, 'mxfp8q8')
-    return m, m.keep
-
-
-def mxfp8_weight_map(tensors):
-    m = LazyW16(tensors, 'mxfp8')
-    return m, m.keep
-
-
 # GEMM arithmetic of newly built models.  A bitstream decodes only under the arithmetic that produced it (the priors must match bit
 # for bit) and the container -- the reference's, byte for byte -- does not record it: the default is FIXED here (no environment
 # override), another mode is an explicit `model.set_gemm_precision(...)` call that must be made identically on both sides
@@ -193,6 +165,109 @@ PRECISIONS = ('fp32', 'bf16', 'bf16x3', 'f16x2', 'fp8')
 PREC_CODE = {'fp32': 0, 'bf16': 1, 'bf16x3': 2, 'fp8': 3, 'f16x2': 4}        # lvae_gemm_desc.prec
 assert DEFAULT_PRECISION in PRECISIONS, DEFAULT_PRECISION
 _log = logging.getLogger('lvae')
+
+
+class PackedWeights:
+    """Device-resident, kernel-friendly copies of a model's weights (built once per device / weight version).  A model's subclass fills
+    `t` (name -> fp32 tensor) in its own layout."""
+
+    def __init__(self, model, device):
+        self.t, self.device, self._w16 = {}, device, {}
+        dg = model._dg()
+        self.scale_table = dg.scale_table.detach().to(device=device, dtype=torch.float32).contiguous()
+        self.scale_bound = float(dg.lower_bound_scale.bound.item())
+
+    def put(self, name, t):
+        self.t[name] = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+    def p(self, name):
+        return self.t[name].data_ptr()
+
+    def bf16_map(self, mode):
+        """The LazyW16 of a mode, built once, under a lock: plans are recorded concurrently by the pipeline-group threads, and a second
+        builder would free the first one's copies while its plan still points at them."""
+        with _W16_LOCK:
+            if mode not in self._w16:
+                self._w16[mode] = LazyW16(self.t, mode)
+        return self._w16[mode]
+
+
+class CodecPlan(Plan):
+    """What the models' plans share: the GEMM arithmetic and its weight maps, the per-latent-block lists the coder loops and the test
+    hooks read, and the ConvNeXt-block recorder."""
+    lp_storage = False        # the plan has the reduced-precision 'fp8' form (bf16 feature maps, MX-fp8 GEMMs, BASELINE config 5)
+    use_mlp_sk = False        # small-map MLPs as the fused split-K launch (csrc/mlp_sk.hip)
+
+    def __init__(self, model, pk, B):
+        super().__init__(pk.device)
+        self.model, self.pk, self.B = model, pk, B
+        if model._prec == 'fp8' and not self.lp_storage:
+            raise NotImplementedError("the 'fp8' mode (bf16 activation storage + MX-fp8 GEMMs, BASELINE config 5) is built for qarv_base")
+        self.prec = PREC_CODE[model._prec]
+        self.prec_name = model._prec
+        self.w16 = pk.bf16_map(model._prec) if self.prec else None
+        self.w16_x3 = pk.bf16_map('bf16x3') if self.prec == 4 else None
+        self.w16_k32 = pk.bf16_map('f16x2k32') if self.prec == 4 else None
+        self.w16_q8 = pk.bf16_map('mxfp8q8') if self.prec == 3 else None
+        self.lp = self.prec == 3                # feature maps stored as bf16
+        self.adt = torch.bfloat16 if self.lp else torch.float32
+        self.lat_shapes, self.lat_hw = [], []   # per latent block: (z, h * w), (h, w)
+        self.idx_off, self.sym_off = [], []     # ... element offsets into idx_all / sym_all
+        self.cuts, self.qcuts = [], []          # decode plans: op index after each prior_index; encode plans: after each quantize launch
+        self.pm_bufs = []                       # ... prior means [M][z] (NHWC rows)
+        self.prm_bufs, self.qm_bufs, self.zhat_bufs, self.zhat_ld = [], [], [], []   # test access (CodecBase._trace_blocks), the generative API
+
+    def alloc_symbols(self, n_sym, host=True):
+        """Device symbol / index buffers of every latent block; host=True adds the coder's pinned host copies."""
+        self.n_sym = n_sym
+        self.sym_all, self.idx_all = self.new(n_sym, torch.int32), self.new(n_sym, torch.uint8)
+        if host:
+            self.sym_host = torch.empty(n_sym, dtype=torch.int32).pin_memory()
+            self.idx_host = torch.empty(n_sym, dtype=torch.uint8).pin_memory()
+            self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
+
+    def dwln_add(self, fn, p, x, y, H, W, C, k):
+        """Record block p's depthwise + LayerNorm launch `fn` (the kernel of the wanted output format) as p + '.dwln', with the model's
+        affine: LayerNorm weights, or AdaLN vectors."""
+        raise NotImplementedError
+
+    def cnx(self, p, m, x, out, H, W):
+        """A ConvNeXt block = depthwise+LN(+affine) kernel, fc1+GELU GEMM, fc2+gamma+residual GEMM."""
+        pk, lib = self.pk, self.lib
+        C, k, hid = m.dim, m.kernel_size, m.hidden
+        M = self.B * H * W
+        y = self.buf(self.sname('y'), M * C, self.adt).data_ptr()
+        mlp = dict(y=y, M=M, C=C, hid=hid, w1=pk.p(p + '.fc1_w'), b1=pk.p(p + '.fc1_b'), w2=pk.p(p + '.fc2_w'), b2=pk.p(p + '.fc2_b'),
+                   gamma=pk.p(p + '.gamma'), res=x, out=out, label=p + '.mlp')
+        # f16x2 plans: y and the hidden map have one consumer each (fc1 / fc2), so their producers store them pre-split (hi / lo' fp16
+        # planes, 4 bytes per element like fp32) and the two GEMMs stream both operands by LDS-DMA with no conversion in the main loop
+        # (reduced-precision plans: the same idea with MX-fp8 -- the producers quantise, csrc/gemm_q8.hip streams)
+        # (small maps: the split-K layers -- pre-split + serial split-K where the batch makes that the faster form, same bits: engine.mlp_pipeline)
+        if self.mlp_fused_ok(C, hid, k, M=M, rows_per_image=H * W):
+            # the stride-4 blocks: fc1 -> GELU -> fc2 as one launch, the hidden tile never leaves the CU (csrc/mlp_h2c.hip)
+            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y, H, W, C, k)
+            self.mlp_fused(**mlp)
+            return
+        sk = self.mlp_sk_ok(C, hid, k, H * W, M) if self.use_mlp_sk else None
+        if sk is not None:
+            # stride-32 / 64 maps (both GEMMs split-K): fc1 -> GELU -> fc2's partial sums as one launch, then the reduce launch
+            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y, H, W, C, k)
+            self.mlp_sk(S1=sk[0], S2=sk[1], **mlp)
+            return
+        h = self.buf(self.sname('hid'), M * hid, self.adt).data_ptr()
+        if self.mlp_q8_ok(C, hid, k):
+            pre1, pre2, S1, S2 = True, True, None, None
+        else:
+            pre1, pre2, S1, S2 = self.mlp_pipeline(C, hid, k, H * W)
+        if self.lp:
+            fn = lib.lvae_dwconv_ln_q8 if pre1 else lib.lvae_dwconv_ln_bf16
+        else:
+            fn = lib.lvae_dwconv_ln_h2 if pre1 else lib.lvae_dwconv_ln_f32
+        self.dwln_add(fn, p, x, y, H, W, C, k)
+        self.gemm(A0=y, K0=C, M=M, N=hid, Wt=pk.p(p + '.fc1_w'), bias=pk.p(p + '.fc1_b'), out=h,
+                  epi=_native.EPI_BIAS_GELU, a_h2=pre1, out_h2=pre2, ksplit=S1, label=p + '.fc1')
+        self.gemm(A0=h, K0=hid, M=M, N=C, Wt=pk.p(p + '.fc2_w'), bias=pk.p(p + '.fc2_b'),
+                  gamma=pk.p(p + '.gamma'), res=x, ldres=C, out=out, epi=_native.EPI_GAMMA_RES, a_h2=pre2, ksplit=S2, label=p + '.fc2')
 
 
 def on_model_device(fn):
@@ -222,6 +297,54 @@ class CodecBase(nn.Module):
         self.serial_groups = False
         # default: fp32-class accuracy on the bf16 matrix cores (same parity as the exact fp32 MFMA path, 1.2-1.5x faster)
         self._prec = DEFAULT_PRECISION
+        self._packed, self._plans = None, {}
+
+    # ---- packed weights and launch plans: built on first use, dropped when the weights move or change.  A model supplies
+    # _latent_blocks(), _build_packed(dev), _plan_key(kind, ...) and _build_plan(kind, ...)
+    def _invalidate(self):
+        self._packed, self._plans = None, {}
+
+    def _apply(self, fn, *a, **k):
+        self._invalidate()
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, *a, **k):
+        self._invalidate()
+        return super().load_state_dict(*a, **k)
+
+    def _prepare(self):
+        dev = self._dummy.device
+        if self._packed is None or self._packed.device != dev:
+            if dev.type != 'cuda':
+                raise RuntimeError('lvae (MI355X build): compress/decompress run on the GPU only; move the model with '
+                                   '.to("cuda") -- there is deliberately no CPU fallback')
+            _native.lib()
+            self._invalidate()
+            with torch.no_grad():
+                self._packed = self._build_packed(dev)
+        return self._packed
+
+    def _plan(self, kind, *a, **k):
+        key = self._plan_key(kind, *a, **k)
+        pl = self._plans.get(key)
+        if pl is None:
+            self._prepare()
+            pl = self._plans[key] = self._build_plan(kind, *a, **k)
+        return pl
+
+    def _dg(self):
+        for b in self._latent_blocks():
+            return b.discrete_gaussian
+        raise RuntimeError('no latent block')
+
+    def _build_cdf_tables(self, build):
+        """compress_mode(): `build(dg)` on the first latent block's entropy model; all blocks share one scale table, hence identical
+        rows, so the others alias its CDF tables.  -> the blocks' entropy models."""
+        first, *rest = dgs = [b.discrete_gaussian for b in self._latent_blocks()]
+        build(first)
+        for dg in rest:
+            dg._quantized_cdf, dg._offset, dg._cdf_length, dg._host = first._quantized_cdf, first._offset, first._cdf_length, None
+        return dgs
 
     def set_gemm_precision(self, mode):
         """'fp32': exact fp32 MFMA (fmaf chains); 'bf16x3': fp32-class accuracy from three-term bf16 splits on the bf16 MFMA
@@ -254,7 +377,6 @@ class CodecBase(nn.Module):
     @staticmethod
     def _alias_host(pl, seg, n_ops):
         """A copy of a native segment whose launches address pl.sym_host / pl.idx_host wherever the recorded ones address pl.sym_all / pl.idx_all."""
-        from .. import _native
         raster_ops = {_native.OP_KINDS[k] for k in ('lvae_prior_index_f32', 'lvae_prior_index_sk_f32', 'lvae_quantize_f32', 'lvae_quantize_sk_f32', 'lvae_dequantize_f32')}
         spans = [(pl.sym_all.data_ptr(), pl.sym_all.numel() * 4, pl.sym_host.data_ptr()), (pl.idx_all.data_ptr(), pl.idx_all.numel(), pl.idx_host.data_ptr())]
         out = (_native.Op * max(1, n_ops))()
@@ -274,7 +396,6 @@ class CodecBase(nn.Module):
     def _group_blocks(cls_, pl, kind, cuts, offs, n):
         """The plan's latent blocks as a native array, cached on the plan: `cuts` = op index after each block's segment, `offs` = its
         element offset into sym_all / idx_all; per_image from pl.lat_shapes."""
-        from .. import _native
         key = '_native_blocks_' + kind
         cached = getattr(pl, key, None)
         if cached is None:
@@ -308,7 +429,6 @@ class CodecBase(nn.Module):
 
     def _decode_group_native(self, pl, cuts, offs, n, strings, tables, nthreads, stream, T=None):
         """strings[b][li]: image b's stream of latent block li.  Runs the group's whole decode; the caller copies pl.out afterwards."""
-        from .. import _native
         arr, segs, tail, n_tail, early = self._group_blocks(pl, 'dec', cuts, offs, n)
         nb = len(cuts)
         # The first segment (bias -> ... -> prior of the top latent block) does not depend on the bitstream: it is on its way to the GPU
@@ -365,7 +485,6 @@ class CodecBase(nn.Module):
 
     def _encode_group_native(self, pl, cuts, offs, n, tables, nthreads, stream, T=None):
         """Runs the group's whole encode (launches, progressive hand-over, rANS).  -> strings[li][b] (bytes)."""
-        from .. import _native
         arr, _segs, _tail, _nt, _early = self._group_blocks(pl, 'enc', cuts, offs, n)
         nb = len(cuts)
         qcdf, cdf_len, offset = tables
@@ -397,6 +516,36 @@ class CodecBase(nn.Module):
             T['enc_gpu_wait'] = T.get('enc_gpu_wait', 0) + secs[1]
             T['enc_rans'] = T.get('enc_rans', 0) + secs[2]
         return [[outs[li * n + b][:out_len[li * n + b]].tobytes() for b in range(n)] for li in range(nb)]
+
+    def _decode_group_loop(self, pl, n, strings, tables, nthreads, stream, T=None):
+        """A group's decode as a Python loop: the segment up to each cut of pl.cuts, then the host decode of that block's streams
+        (strings[b][li]: image b's stream for cut li), then the tail; the caller copies pl.out afterwards."""
+        lo = 0
+        for li, cut in enumerate(pl.cuts):
+            t0 = time.time()
+            pl.run(lo, cut, stream=stream.cuda_stream)
+            lo = cut
+            t1 = self._decode_block(pl, li, n, [s[li] for s in strings], tables, nthreads, stream)
+            if T is not None:
+                t2 = time.time()
+                T['dec_gpu_seg'] = T.get('dec_gpu_seg', 0) + t1 - t0
+                T['dec_rans'] = T.get('dec_rans', 0) + t2 - t1
+        pl.run(lo, None, stream=stream.cuda_stream)
+        pl.fetch_status()                               # read by _check_decoded() after the groups have finished
+
+    def _decode_block(self, pl, li, n, strings, tables, nthreads, stream):
+        """The host step behind cut li: indexes to pinned memory, rANS decode of the n streams, symbols back to the device.  -> the time
+        at which the GPU segment in front of it had finished."""
+        z, hw = pl.lat_shapes[li]
+        o, cnt = pl.idx_off[li], n * z * hw
+        pl.idx_host[o:o + cnt].copy_(pl.idx_all[o:o + cnt], non_blocking=True)
+        stream.synchronize()
+        t1 = time.time()
+        iv = [pl.idx_np[o + b * z * hw:o + (b + 1) * z * hw] for b in range(n)]
+        sv = [pl.sym_np[o + b * z * hw:o + (b + 1) * z * hw] for b in range(n)]
+        rans_decode_streams(tables, strings, iv, sv, nthreads)
+        pl.sym_all[o:o + cnt].copy_(pl.sym_host[o:o + cnt], non_blocking=True)
+        return t1
 
     @staticmethod
     def _reset_status(pl):
@@ -496,7 +645,56 @@ class CodecBase(nn.Module):
             with open(out, 'wb') as f:
                 f.write(blob)
 
+    # ---- the reference's single-image and file API, on the batch interfaces.  A variable-rate model adds `lmb` to the compress side
+    @torch.no_grad()
+    def compress(self, im):
+        assert im.shape[0] == 1, 'use compress_batch for more than one image'
+        return self.compress_batch(im)[0]
+
+    @torch.no_grad()
+    def decompress(self, compressed):
+        return self.decompress_batch([compressed])
+
+    @torch.no_grad()
+    def compress_file(self, img_path, output_path):
+        self._compress_to_files([img_path], [output_path])
+
+    @torch.no_grad()
+    def compress_files(self, img_paths, output_paths, images=None):
+        """Batched compress_file (same padded size): one compress_batch call; files identical to compress_file's.  `images`: the files'
+        contents, already decoded (PIL images or uint8 tensors)."""
+        self._compress_to_files(images if images is not None else list(img_paths), output_paths)
+
+    @torch.no_grad()
+    def decompress_file(self, bits_path):
+        return self.decompress_files([bits_path])[0]
+
+    @torch.no_grad()
+    def decompress_files(self, bits_paths):
+        """Batched decompress_file for files of one latent shape -> list of (1,3,h,w) tensors, each cropped to the size in its header."""
+        bodies, sizes = [], []
+        for p in bits_paths:
+            with open(p, 'rb') as f:
+                body, size, _ = self._unpack_blob(f.read())
+            bodies.append(body); sizes.append(size)
+        out = self.decompress_batch(bodies)
+        return [out[i:i + 1, :, :h, :w] for i, (h, w) in enumerate(sizes)]
+
     # ---- test access (not on the hot path)
+    @torch.no_grad()
+    def _trace(self, pl, B, full=False, force_z=None):
+        """encode_trace() once the plan's input is loaded: per latent block dict(symbols, indexes), (B, z, hw) int arrays in the coder's
+        NCHW raster order, from ONE run of the plan; full / force_z: _trace_blocks."""
+        if full or force_z is not None:
+            return self._trace_blocks(pl, B, force_z)
+        pl.run()
+        pl.fetch_status()
+        torch.cuda.current_stream(pl.device).synchronize()
+        pl.raise_if_flagged(where='(encode trace)')
+        sym, idx = pl.sym_all.cpu().numpy(), pl.idx_all.cpu().numpy()
+        return [dict(symbols=sym[o:o + B * z * hw].reshape(B, z, hw).copy(), indexes=idx[o:o + B * z * hw].reshape(B, z, hw).copy())
+                for o, (z, hw) in zip(pl.sym_off, pl.lat_shapes)]
+
     @torch.no_grad()
     def _trace_blocks(self, pl, B, force_z=None):
         """Run an encode plan latent block by latent block (`pl.qcuts`: the op index right after each block's quantize launch)

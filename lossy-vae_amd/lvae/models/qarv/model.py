@@ -23,10 +23,10 @@ import torch
 import torch.nn as nn
 
 from ... import _native
-from ...engine import Plan, ptr
+from ...engine import ptr
 from ...utils import coding
-from ..base import CodecBase, PREC_CODE, on_model_device
-from ..entropy_coding import DiscretizedGaussian, rans_decode_streams, rans_encode_streams
+from ..base import CodecBase, CodecPlan, PackedWeights, on_model_device
+from ..entropy_coding import DiscretizedGaussian, rans_encode_streams
 
 EMBED_DIM = 256
 # `model.side_streams` (default on since round 5): encode plans up to this many pixels per launch run posterior0 and the prior heads on a
@@ -121,19 +121,16 @@ class _Encoder(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------- launch plans
-class _Packed:
-    """Device-resident, kernel-friendly copies of the weights (built once per device / weight version)."""
+class _Packed(PackedWeights):
+    """qarv layout: NHWC / GEMM-friendly weights, the lambda embedding and one AdaLN matrix for all blocks."""
 
     def __init__(self, model, device):
-        self.t = {}
+        super().__init__(model, device)
         self.adaln_off = {}
-        dev = device
-        f32 = dict(device=dev, dtype=torch.float32)
+        f32 = dict(device=device, dtype=torch.float32)
         ws, bs = [], []
         total = 0
-
-        def put(name, t):
-            self.t[name] = t.detach().to(**f32).contiguous()
+        put = self.put
 
         def cnx(p, m):
             nonlocal total
@@ -193,52 +190,20 @@ class _Packed:
         self.emb_h = torch.zeros(EMBED_DIM, **f32)
         self.emb = torch.zeros(EMBED_DIM, **f32)
         self.tab_cap, self.adaln_tab = 0, None          # per-image lambdas: [tab_cap][adaln_total] table (model._set_lmb with a sequence)
-        self.scale_table = model._dg().scale_table.detach().to(**f32).contiguous()
-        self.scale_bound = float(model._dg().lower_bound_scale.bound.item())
-
-    def p(self, name):
-        return self.t[name].data_ptr()
-
-    def bf16_map(self, mode):
-        """Built once per mode, under a lock: plans are recorded concurrently by the pipeline-group threads, and a second
-        builder would free the first one's bf16 copies while its plan still points at them."""
-        from ..base import (bf16_weight_map, bf16x3_weight_map, f16x2_weight_map, f16x2k32_weight_map, mxfp8_weight_map,
-                            mxfp8q8_weight_map, _W16_LOCK)
-        with _W16_LOCK:
-            if not hasattr(self, '_w16'):
-                self._w16 = {}
-            if mode not in self._w16:
-                self._w16[mode] = {'bf16': bf16_weight_map, 'bf16x3': bf16x3_weight_map, 'f16x2': f16x2_weight_map,
-                                   'f16x2k32': f16x2k32_weight_map, 'fp8': mxfp8_weight_map, 'mxfp8q8': mxfp8q8_weight_map}[mode](self.t)
-        return self._w16[mode][0]
 
 
-class _NetPlan(Plan):
+class _NetPlan(CodecPlan):
     """Shared recording helpers for the encode and decode plans."""
+    lp_storage = use_mlp_sk = True
 
     def __init__(self, model, pk, B, vec=False):
-        super().__init__(pk.adaln.device)
-        self.model, self.pk, self.B = model, pk, B
+        super().__init__(model, pk, B)
         # vec: one lambda PER IMAGE.  The depthwise launches then read image b's (shift | 1+scale) vectors from row b of a slab this plan
         # owns ([B][adaln_total], filled by load_lmb before a run) instead of the model-wide pk.adaln.  The slab is the plan's own because
         # plans are cached with their addresses baked in while a pipeline group's first image index is not part of the cache key
         self.vec = bool(vec)
-        self.adaln_slab = torch.zeros(B * pk.adaln_total, dtype=torch.float32, device=pk.adaln.device) if vec else None
-        self.prec = PREC_CODE[model._prec]
-        self.prec_name = model._prec
-        self.w16 = pk.bf16_map(model._prec) if self.prec else None
-        self.w16_x3 = pk.bf16_map('bf16x3') if self.prec == 4 else None
-        self.w16_k32 = pk.bf16_map('f16x2k32') if self.prec == 4 else None
-        self.w16_q8 = pk.bf16_map('mxfp8q8') if self.prec == 3 else None
-        self.lp = self.prec == 3                # reduced precision (BASELINE config 5): feature maps stored as bf16, MX-fp8 GEMMs
-        self.adt = torch.bfloat16 if self.lp else torch.float32
-        self.dwln = self.lib.lvae_dwconv_ln_bf16 if self.lp else self.lib.lvae_dwconv_ln_f32
-        self.sym_off, self.idx_off = [], []     # per latent block element offsets into sym_all / idx_all
-        self.pm_bufs = []                       # per latent block prior means [M][z] (NHWC rows)
-        self.qcuts = []                         # encode plans: op index right after each block's quantize launch
-        self.prm_ptrs, self.zhat_ptrs, self.zhat_bufs = [], [], []  # per latent block: raw prior conv output / latent buffer (scratch may be re-grown)
-        self.prm_bufs, self.qm_bufs, self.zhat_ld = [], [], []      # test access (CodecBase._trace_blocks): tensors behind those launches
-        self.lat_shapes = []                    # (z, HW)
+        self.adaln_slab = torch.zeros(B * pk.adaln_total, dtype=torch.float32, device=pk.device) if vec else None
+        self.prm_ptrs, self.zhat_ptrs = [], []  # per latent block: raw prior conv output / latent buffer (scratch may be re-grown)
 
     def load_lmb(self, table, start):
         """vec plans: rows start .. start + B of the model's per-image table -> this plan's slab, on the current stream (the stream the
@@ -257,43 +222,11 @@ class _NetPlan(Plan):
             self.add(fn, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), None, None, ptr(pk.adaln, off), ptr(pk.adaln, off + C), y, self.B, H, W, C, k),
                      p + '.dwln')
 
-    def scratch(self, M, C, hid):
-        y = self.buf(self.sname('y'), M * C, self.adt)
-        h = self.buf(self.sname('hid'), M * hid, self.adt)
-        return y, h
-
     def cnx(self, p, m, x, out, H, W):
-        """ConvNeXtBlockAdaLN (common.py:142-161) = dwconv+LN+AdaLN kernel, fc1+GELU GEMM, fc2+gamma+residual GEMM."""
-        pk, lib = self.pk, self.lib
-        C, k, hid = m.dim, m.kernel_size, m.hidden
-        M = self.B * H * W
-        y, h = self.scratch(M, C, hid)
-        # f16x2 plans: y and the hidden map have one consumer each (fc1 / fc2), so their producers store them pre-split (hi / lo' fp16
-        # planes, 4 bytes per element like fp32) and the two GEMMs stream both operands by LDS-DMA with no conversion in the main loop
-        # (reduced-precision plans: the same idea with MX-fp8 -- the producers quantise, csrc/gemm_q8.hip streams)
-        # (small maps: the split-K layers -- pre-split + serial split-K where the batch makes that the faster form, same bits: engine.mlp_pipeline)
-        if self.mlp_fused_ok(C, hid, k, M=M, rows_per_image=H * W):
-            # C = 128 / hidden = 192 (the decoder's stride-4 blocks): fc1 -> GELU -> fc2 as one launch, the hidden tile never leaves the CU
-            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y.data_ptr(), H, W, C, k)
-            self.mlp_fused(y=y.data_ptr(), M=M, C=C, hid=hid, w1=pk.p(p + '.fc1_w'), b1=pk.p(p + '.fc1_b'), w2=pk.p(p + '.fc2_w'),
-                           b2=pk.p(p + '.fc2_b'), gamma=pk.p(p + '.gamma'), res=x, out=out, label=p + '.mlp')
-            return
-        sk = self.mlp_sk_ok(C, hid, k, H * W, M)
-        if sk is not None:
-            # stride-32 / 64 maps (both GEMMs split-K): fc1 -> GELU -> fc2's partial sums as one launch, then the reduce launch (csrc/mlp_sk.hip)
-            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y.data_ptr(), H, W, C, k)
-            self.mlp_sk(y=y.data_ptr(), M=M, C=C, hid=hid, S1=sk[0], S2=sk[1], w1=pk.p(p + '.fc1_w'), b1=pk.p(p + '.fc1_b'), w2=pk.p(p + '.fc2_w'),
-                        b2=pk.p(p + '.fc2_b'), gamma=pk.p(p + '.gamma'), res=x, out=out, label=p + '.mlp')
-            return
-        if self.mlp_q8_ok(C, hid, k):
-            pre1, pre2, S1, S2 = True, True, None, None
-        else:
-            pre1, pre2, S1, S2 = self.mlp_pipeline(C, hid, k, H * W)
-        self.dwln_add((lib.lvae_dwconv_ln_q8 if self.lp else lib.lvae_dwconv_ln_h2) if pre1 else self.dwln, p, x, y.data_ptr(), H, W, C, k)
-        self.gemm(A0=y.data_ptr(), K0=C, M=M, N=hid, Wt=pk.p(p + '.fc1_w'), bias=pk.p(p + '.fc1_b'), out=h.data_ptr(),
-                  epi=_native.EPI_BIAS_GELU, a_h2=pre1, out_h2=pre2, ksplit=S1, label=p + '.fc1')
-        self.gemm(A0=h.data_ptr(), K0=hid, M=M, N=C, Wt=pk.p(p + '.fc2_w'), bias=pk.p(p + '.fc2_b'),
-                  gamma=pk.p(p + '.gamma'), res=x, ldres=C, out=out, epi=_native.EPI_GAMMA_RES, a_h2=pre2, ksplit=S2, label=p + '.fc2')
+        """ConvNeXtBlockAdaLN (common.py:142-161).  The hidden-map scratch is sized at every block, also where the MLP runs fused: the
+        encoder's first (largest) blocks then size it for the whole plan."""
+        self.buf(self.sname('hid'), self.B * H * W * m.hidden, self.adt)
+        super().cnx(p, m, x, out, H, W)
 
     def upsample(self, p, m, x, out, H, W, raw=False):
         """raw (final conv only): the launch of the ST_IMAGE store with the raw NHWC fp32 store of the pre-clamp output instead."""
@@ -357,13 +290,7 @@ class _NetPlan(Plan):
                 s *= m.rate
             elif m.kind == 'stop':
                 break
-        self.n_sym = total * B
-        self.sym_all = self.new(self.n_sym, torch.int32)
-        self.idx_all = self.new(self.n_sym, torch.uint8)
-        if host:
-            self.sym_host = torch.empty(self.n_sym, dtype=torch.int32).pin_memory()
-            self.idx_host = torch.empty(self.n_sym, dtype=torch.uint8).pin_memory()
-            self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
+        self.alloc_symbols(total * B, host)
 
 
 class _EncPlan(_NetPlan):
@@ -518,13 +445,11 @@ class _DecPlan(_NetPlan):
     def __init__(self, model, pk, B, nH, nW, evaluate=False, vec=False):
         super().__init__(model, pk, B, vec)
         lib = self.lib
-        self.alloc_latent_io_full(nH, nW, host=not evaluate)
+        self.alloc_latent_io(nH, nW, host=not evaluate)
         h, w = nH, nW
         width = model.dec_blocks[0].width
         f = self.new(B * h * w * width, self.adt)
         self.add(lib.lvae_bias_expand_bf16 if self.lp else lib.lvae_bias_expand_f32, (pk.p('bias'), f.data_ptr(), B * h * w, width), 'bias')
-        self.cuts = []        # op index after each prior_index (host decode happens there)
-        self.lat_hw = []      # (h, w) of each latent block
         self.out = None
         for i, m in enumerate(model.dec_blocks):
             p = f'dec_blocks.{i}'
@@ -560,9 +485,6 @@ class _DecPlan(_NetPlan):
                     self.out = nf.view(B, m.cout, h, w)
         assert self.out is not None
 
-    def alloc_latent_io_full(self, nH, nW, host=True):
-        self.alloc_latent_io(nH, nW, host)
-
 
 # ----------------------------------------------------------------------------------------------- the model
 class VariableRateLossyVAE(CodecBase):
@@ -592,9 +514,6 @@ class VariableRateLossyVAE(CodecBase):
         self.register_buffer('_dummy', torch.zeros(1), persistent=False)
         self.compressing = False
         self._init_codec_base()
-        self._packed = None
-        self._packed_key = None
-        self._plans = {}
         self._cur_lmb = None
         self._cur_lmbs = None             # tuple of fp32 lambdas whose vectors the per-image table holds
         self.timing = {} if os.environ.get('LVAE_TIMING') else None      # host-side phase timers (debug)
@@ -602,34 +521,15 @@ class VariableRateLossyVAE(CodecBase):
         self.side_streams = True
 
     # ---- helpers
-    def _dg(self) -> DiscretizedGaussian:
-        for b in self.dec_blocks:
-            if getattr(b, 'is_latent_block', False):
-                return b.discrete_gaussian
-        raise RuntimeError('no latent block')
-
-    def _apply(self, fn, *a, **k):
-        self._invalidate()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._invalidate()
-        return super().load_state_dict(*a, **k)
+    def _latent_blocks(self):
+        return [b for b in self.dec_blocks if getattr(b, 'is_latent_block', False)]
 
     def _invalidate(self):
-        self._packed, self._plans, self._cur_lmb, self._cur_lmbs = None, {}, None, None
+        super()._invalidate()
+        self._cur_lmb = self._cur_lmbs = None
 
-    def _prepare(self):
-        dev = self._dummy.device
-        if self._packed is None or self._packed.adaln.device != dev:
-            if dev.type != 'cuda':
-                raise RuntimeError('lvae (MI355X build): compress/decompress run on the GPU only; move the model with '
-                                   '.to("cuda") -- there is deliberately no CPU fallback')
-            _native.lib()
-            with torch.no_grad():
-                self._packed = _Packed(self, dev)
-            self._plans, self._cur_lmb, self._cur_lmbs = {}, None, None
-        return self._packed
+    def _build_packed(self, dev):
+        return _Packed(self, dev)
 
     def _lmb_features(self, lmb):
         """Sinusoidal features of one lambda (qarv/model.py:266-287) on the host, fp32: 128 cos + 128 sin."""
@@ -704,38 +604,19 @@ class VariableRateLossyVAE(CodecBase):
         if pl.vec:
             pl.load_lmb(self._packed.adaln_tab, start)
 
-    def _plan(self, kind, B, a, b, group=0, vec=False):
-        key = (kind, B, a, b, group, bool(getattr(self, 'side_streams', False)) and kind != 'dec', self._prec) + (('vec',) if vec else ())
-        pl = self._plans.get(key)
-        if pl is None:
-            pk = self._prepare()
-            if kind == 'enc':
-                pl = _EncPlan(self, pk, B, a, b, vec=vec)
-            elif kind == 'encb':
-                pl = _EncPlan(self, pk, B, a, b, with_bits=True, vec=vec)
-            elif kind == 'ence':
-                pl = _EncPlan(self, pk, B, a, b, chan_bits=True, vec=vec)
-            elif kind == 'evald':
-                pl = _DecPlan(self, pk, B, a, b, evaluate=True, vec=vec)
-            else:
-                pl = _DecPlan(self, pk, B, a, b, vec=vec)
-            self._plans[key] = pl
-        return pl
+    def _plan_key(self, kind, B, a, b, group=0, vec=False):
+        return (kind, B, a, b, group, bool(getattr(self, 'side_streams', False)) and kind != 'dec', self._prec) + (('vec',) if vec else ())
+
+    def _build_plan(self, kind, B, a, b, group=0, vec=False):
+        if kind in ('enc', 'encb', 'ence'):
+            return _EncPlan(self, self._packed, B, a, b, with_bits=(kind == 'encb'), chan_bits=(kind == 'ence'), vec=vec)
+        return _DecPlan(self, self._packed, B, a, b, evaluate=(kind == 'evald'), vec=vec)
 
     # ---- reference API
     def compress_mode(self, mode=True):
         """qarv/model.py:509-514: (re)build the CDF tables of every latent block."""
         if mode:
-            first = None
-            for block in self.dec_blocks:
-                if getattr(block, 'is_latent_block', False):
-                    dg = block.discrete_gaussian
-                    if first is None:
-                        dg.update()
-                        first = dg
-                    else:       # all blocks share one scale table: identical rows, build once
-                        dg._quantized_cdf, dg._offset, dg._cdf_length = first._quantized_cdf, first._offset, first._cdf_length
-                        dg._host = None
+            self._build_cdf_tables(lambda dg: dg.update())
             self._log_precision()
         self.compressing = mode
 
@@ -888,7 +769,6 @@ class VariableRateLossyVAE(CodecBase):
                 T['dec_head_thread'] = T.get('dec_head_thread', 0) + time.time() - t_b          # submit -> the group's thread runs
             pl = self._plan('dec', n, nH, nW, g, vec=vec)
             self._use_lmb(pl, start)
-            lo = 0
             if T is not None:
                 T['dec_head'] = T.get('dec_head', 0) + time.time() - t_entry                    # entry -> this group's first launch
             if self.native_group_loops:
@@ -897,25 +777,7 @@ class VariableRateLossyVAE(CodecBase):
                 out[start:start + n].copy_(pl.out, non_blocking=True)
                 return None
             assert all(len(lv[start + b]) == len(pl.cuts) for b in range(n)), f'expected {len(pl.cuts)} strings per image'
-            for li, cut in enumerate(pl.cuts):
-                t0 = time.time()
-                pl.run(lo, cut, stream=stream.cuda_stream)
-                lo = cut
-                z, hw = pl.lat_shapes[li]
-                o, cnt = pl.idx_off[li], n * z * hw
-                pl.idx_host[o:o + cnt].copy_(pl.idx_all[o:o + cnt], non_blocking=True)
-                stream.synchronize()
-                t1 = time.time()
-                iv = [pl.idx_np[o + b * z * hw:o + (b + 1) * z * hw] for b in range(n)]
-                sv = [pl.sym_np[o + b * z * hw:o + (b + 1) * z * hw] for b in range(n)]
-                rans_decode_streams(tables, [lv[start + b][li] for b in range(n)], iv, sv, nthreads)
-                pl.sym_all[o:o + cnt].copy_(pl.sym_host[o:o + cnt], non_blocking=True)
-                if T is not None:
-                    t2 = time.time()
-                    T['dec_gpu_seg'] = T.get('dec_gpu_seg', 0) + t1 - t0
-                    T['dec_rans'] = T.get('dec_rans', 0) + t2 - t1
-            pl.run(lo, None, stream=stream.cuda_stream)
-            pl.fetch_status()                               # read by _check_decoded() after the groups have finished
+            self._decode_group_loop(pl, n, lv[start:start + n], tables, nthreads, stream, T)
             out[start:start + n].copy_(pl.out, non_blocking=True)
             return None
 
@@ -927,11 +789,6 @@ class VariableRateLossyVAE(CodecBase):
             T['dec_groups_total'] = T.get('dec_groups_total', 0) + time.time() - t_g
             T['dec_calls'] = T.get('dec_calls', 0) + 1
         return out
-
-    @torch.no_grad()
-    def decompress(self, string):
-        """qarv/model.py:531-557."""
-        return self.decompress_batch([string])
 
     variable_rate = True
 
@@ -947,32 +804,11 @@ class VariableRateLossyVAE(CodecBase):
         self._compress_to_files([img_path], [output_path], lmb=lmb)
 
     @torch.no_grad()
-    def decompress_file(self, bits_path):
-        """qarv/model.py:572-581."""
-        with open(bits_path, 'rb') as f:
-            header_str = f.read(4)
-            body_str = f.read()
-        img_h, img_w = struct.unpack('2H', header_str)
-        im_hat = self.decompress(body_str)
-        return im_hat[:, :, :img_h, :img_w]
-
-    @torch.no_grad()
     def compress_files(self, img_paths, output_paths, lmb=None, images=None):
         """Batched compress_file: images whose PADDED sizes agree are coded by one compress_batch call (GPU work batched, the B x 9
         rANS streams coded in parallel); every output file is byte-identical to what compress_file writes for that image.  lmb: one
         lambda, or one per file (a sequence).  `images`: the files' contents, already decoded (PIL images or uint8 tensors)."""
         self._compress_to_files(images if images is not None else list(img_paths), output_paths, lmb=lmb)
-
-    @torch.no_grad()
-    def decompress_files(self, bits_paths):
-        """Batched decompress_file for files of one latent shape (any lambdas) -> list of (1,3,h,w) tensors (cropped)."""
-        heads, bodies = [], []
-        for p in bits_paths:
-            with open(p, 'rb') as f:
-                heads.append(struct.unpack('2H', f.read(4)))
-                bodies.append(f.read())
-        out = self.decompress_batch(bodies)
-        return [out[i:i + 1, :, :h, :w] for i, (h, w) in enumerate(heads)]
 
     @torch.no_grad()
     def compress_to_target(self, im, target_bytes, n_probe=8, max_rounds=50, tol=1, verbose=False):
@@ -1289,17 +1125,4 @@ class VariableRateLossyVAE(CodecBase):
         pl = self._plan('enc', B, H, W, vec=isinstance(lmb, list))
         pl.im.view(B, 3, H, W).copy_(im)
         self._use_lmb(pl)
-        if full or force_z is not None:
-            return self._trace_blocks(pl, B, force_z)
-        pl.run()
-        pl.fetch_status()
-        torch.cuda.current_stream(pl.device).synchronize()
-        pl.raise_if_flagged(where='(encode trace)')
-        sym, idx = pl.sym_all.cpu().numpy(), pl.idx_all.cpu().numpy()
-        out = []
-        h, w = H // 64, W // 64
-        for li, (z, hw) in enumerate(pl.lat_shapes):
-            o = pl.sym_off[li]
-            out.append(dict(symbols=sym[o:o + B * z * hw].reshape(B, z, hw).copy(),
-                            indexes=idx[o:o + B * z * hw].reshape(B, z, hw).copy()))
-        return out
+        return self._trace(pl, B, full, force_z)

@@ -21,6 +21,7 @@ import ctypes
 import io
 import math
 import pickle
+import time
 from collections import OrderedDict
 
 import numpy as np
@@ -28,9 +29,9 @@ import torch
 import torch.nn as nn
 
 from ... import _native
-from ...engine import Plan, ptr
+from ...engine import ptr
 from ...utils import coding
-from ..base import CodecBase, PREC_CODE, on_model_device
+from ..base import CodecBase, CodecPlan, PackedWeights, on_model_device
 from ..entropy_coding import DiscretizedGaussian, log_spaced_table, rans_decode_streams, rans_encode_streams
 from ..qarv.model import UpParams, _conv
 
@@ -163,13 +164,11 @@ class GaussianNLLOutParams(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------- packed weights
-class _Packed:
+class _Packed(PackedWeights):
     def __init__(self, model, dev):
-        self.t = {}
+        super().__init__(model, dev)
         f32 = dict(device=dev, dtype=torch.float32)
-
-        def put(name, t):
-            self.t[name] = t.detach().to(**f32).contiguous()
+        put = self.put
 
         def cnx(p, m):
             C, k = m.dim, m.kernel_size
@@ -260,46 +259,17 @@ class _Packed:
             odg = on.discrete_gaussian
             self.out_scale_table = odg.scale_table.detach().to(**f32).contiguous()
             self.out_scale_bound = float(odg.lower_bound_scale.bound.item())
-        dg = model._dg()
-        self.scale_table = dg.scale_table.detach().to(**f32).contiguous()
-        self.scale_bound = float(dg.lower_bound_scale.bound.item())
-        self.device = dev
-
-    def p(self, name):
-        return self.t[name].data_ptr()
-
-    def bf16_map(self, mode):
-        """Built once per mode, under a lock: plans are recorded concurrently by the pipeline-group threads, and a second
-        builder would free the first one's bf16 copies while its plan still points at them."""
-        from ..base import bf16_weight_map, bf16x3_weight_map, f16x2_weight_map, f16x2k32_weight_map, _W16_LOCK
-        with _W16_LOCK:
-            if not hasattr(self, '_w16'):
-                self._w16 = {}
-            if mode not in self._w16:
-                self._w16[mode] = {'bf16': bf16_weight_map, 'bf16x3': bf16x3_weight_map, 'f16x2': f16x2_weight_map,
-                                   'f16x2k32': f16x2k32_weight_map}[mode](self.t)
-        return self._w16[mode][0]
 
 
-class _QresPlan(Plan):
+class _QresPlan(CodecPlan):
     def __init__(self, model, pk, B, H, W, encode, evaluate=False):
         """encode: the encode plan ('enc'); evaluate (with encode): the eval plan of forward() ('eval') -- the encode plan with each
         block's per-channel rate behind its quantize launch (kl_chan, fp64 [L][B][z_l] at chan_off[l]), and the distortion in place of
         the coder's sinks: the lossy models' final conv stored raw + lvae_rd_image_f32, the lossless model's lvae_pixel_nll_f32 on the
         out-net map (rd_sums, fp64 [B][2]; `out` = im_hat)."""
-        super().__init__(pk.device)
+        super().__init__(model, pk, B)
         evaluate = bool(evaluate and encode)
-        lib, self.pk, self.B = self.lib, pk, B
-        if model._prec == 'fp8':
-            raise NotImplementedError("the 'fp8' mode (bf16 activation storage + MX-fp8 GEMMs, BASELINE config 5) is built for qarv_base")
-        self.prec = PREC_CODE[model._prec]
-        self.prec_name = model._prec
-        self.w16 = pk.bf16_map(model._prec) if self.prec else None
-        self.w16_x3 = pk.bf16_map('bf16x3') if self.prec == 4 else None
-        self.w16_k32 = pk.bf16_map('f16x2k32') if self.prec == 4 else None
-        self.lat_shapes, self.idx_off, self.sym_off, self.cuts = [], [], [], []
-        self.qcuts, self.prm_bufs, self.qm_bufs, self.zhat_bufs, self.zhat_ld = [], [], [], [], []   # test access (CodecBase._trace_blocks)
-        self.pm_bufs, self.lat_hw = [], []          # per latent block: prior means [B*h*w][z], map size (h, w) (the generative API)
+        lib = self.lib
         nH, nW = H // 64, W // 64
         # latent I/O sizes: resolution doubles at every rate-2 upsample of the top-down path
         tot, s = 0, 1
@@ -308,18 +278,13 @@ class _QresPlan(Plan):
                 tot += m.zdim * nH * s * nW * s
             elif not (m.kind == 'up' and m.cout <= 3):
                 s *= m.rate
-        self.n_sym = tot * B
         self.evaluate = evaluate
         if evaluate:
             self.kl_chan = self.new(B * sum(m.zdim for m in model.decoder.dec_blocks if m.kind == 'qlb'), torch.float64)
             self.rd_sums = self.new(B * 2, torch.float64)
             self.rd_ws = self.new(B * _native.EVAL_CHUNKS * 2, torch.float64)     # per-chunk partials of the distortion kernel
             self.chan_off = []
-        self.sym_all, self.idx_all = self.new(self.n_sym, torch.int32), self.new(self.n_sym, torch.uint8)
-        if not evaluate:            # the coder's host copies (the eval plan's symbols never leave the device)
-            self.sym_host = torch.empty(self.n_sym, dtype=torch.int32).pin_memory()
-            self.idx_host = torch.empty(self.n_sym, dtype=torch.uint8).pin_memory()
-            self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
+        self.alloc_symbols(tot * B, host=not evaluate)       # (the eval plan's symbols never leave the device)
         feats = {}
         if encode:
             self.im = self.new(B * 3 * H * W)
@@ -468,28 +433,10 @@ class _QresPlan(Plan):
         if not encode:
             assert self.out is not None
 
-    def cnx(self, p, m, x, out, H, W):
-        pk, lib = self.pk, self.lib
-        C, k, hid = m.dim, m.kernel_size, m.hidden
-        M = self.B * H * W
-        if self.mlp_fused_ok(C, hid, k, M=M, rows_per_image=H * W):
-            # C = 192 / hidden = 384 (the stride-4 blocks of qres34m, encoder and decoder): fc1 -> GELU -> fc2 as one launch (csrc/mlp_h2c.hip),
-            # the bits of the two launches below
-            y = self.buf('y', M * C)
-            self.add(lib.lvae_dwconv_ln_h2, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), pk.p(p + '.ln_w'), pk.p(p + '.ln_b'), None, None,
-                                             y.data_ptr(), self.B, H, W, C, k), p + '.dwln')
-            self.mlp_fused(y=y.data_ptr(), M=M, C=C, hid=hid, w1=pk.p(p + '.fc1_w'), b1=pk.p(p + '.fc1_b'), w2=pk.p(p + '.fc2_w'),
-                           b2=pk.p(p + '.fc2_b'), gamma=pk.p(p + '.gamma'), res=x, out=out, label=p + '.mlp')
-            return
-        y, hbuf = self.buf('y', M * C), self.buf('hid', M * hid)
-        pre1, pre2, S1, S2 = self.mlp_pipeline(C, hid, k, H * W)        # f16x2 plans: pre-split y / hidden map (see the qarv plan's cnx)
-        self.add(lib.lvae_dwconv_ln_h2 if pre1 else lib.lvae_dwconv_ln_f32,
-                 (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), pk.p(p + '.ln_w'), pk.p(p + '.ln_b'), None, None,
-                  y.data_ptr(), self.B, H, W, C, k), p + '.dwln')
-        self.gemm(A0=y.data_ptr(), K0=C, M=M, N=hid, Wt=pk.p(p + '.fc1_w'), bias=pk.p(p + '.fc1_b'), out=hbuf.data_ptr(),
-                  epi=_native.EPI_BIAS_GELU, a_h2=pre1, out_h2=pre2, ksplit=S1, label=p + '.fc1')
-        self.gemm(A0=hbuf.data_ptr(), K0=hid, M=M, N=C, Wt=pk.p(p + '.fc2_w'), bias=pk.p(p + '.fc2_b'), gamma=pk.p(p + '.gamma'),
-                  res=x, ldres=C, out=out, epi=_native.EPI_GAMMA_RES, a_h2=pre2, ksplit=S2, label=p + '.fc2')
+    def dwln_add(self, fn, p, x, y, H, W, C, k):
+        """MyConvNeXtBlock (:168-182): the affine is the block's LayerNorm weights."""
+        pk = self.pk
+        self.add(fn, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), pk.p(p + '.ln_w'), pk.p(p + '.ln_b'), None, None, y, self.B, H, W, C, k), p + '.dwln')
 
     def vdblock(self, p, m, a0, a1, out, H, W):
         """c4(g(c3(g(c2(g(c1(g(x)))))))) with x = a0 or cat[a0, a1] (each of width cin or cin/2)."""
@@ -537,23 +484,14 @@ class HierarchicalVAE(CodecBase):
         self.compressing = False
         self.num_latents = sum(1 for b in self.decoder.dec_blocks if b.kind == 'qlb')
         self._stats_log = dict()
-        self._packed, self._plans = None, {}
         self._init_codec_base()
 
-    def _dg(self):
-        for b in self.decoder.dec_blocks:
-            if b.kind == 'qlb':
-                return b.discrete_gaussian
-        raise RuntimeError('no latent block')
-
-    def _apply(self, fn, *a, **k):
-        self._packed, self._plans = None, {}
-        return super()._apply(fn, *a, **k)
+    def _latent_blocks(self):
+        return [b for b in self.decoder.dec_blocks if b.kind == 'qlb']
 
     def load_state_dict(self, state_dict, strict=True, **k):
         """Reference key names; entropy-model buffers (`*.discrete_gaussian.*`) absent from / extra in a checkpoint are
         tolerated (their set differs between CompressAI versions; the tables are rebuilt by compress_mode())."""
-        self._packed, self._plans = None, {}
         own = self.state_dict()
         sd = {kk: v for kk, v in state_dict.items() if not ('.discrete_gaussian.' in kk and (kk not in own or own[kk].shape != v.shape))}
         for kk, v in own.items():
@@ -561,47 +499,28 @@ class HierarchicalVAE(CodecBase):
                 sd[kk] = v
         return super().load_state_dict(sd, strict=strict, **k)
 
-    def _prepare(self):
-        dev = self._dummy.device
-        if self._packed is None or self._packed.device != dev:
-            if dev.type != 'cuda':
-                raise RuntimeError('lvae (MI355X build): compress/decompress run on the GPU only; move the model with '
-                                   '.to("cuda") -- there is deliberately no CPU fallback')
-            _native.lib()
-            with torch.no_grad():
-                self._packed = _Packed(self, dev)
-            self._plans = {}
-        return self._packed
+    def _build_packed(self, dev):
+        return _Packed(self, dev)
 
-    def _plan(self, kind, B, H, W, group=0):
-        key = (kind, B, H, W, group, self._prec)
-        pl = self._plans.get(key)
-        if pl is None:
-            pl = _QresPlan(self, self._prepare(), B, H, W, encode=(kind in ('enc', 'eval')), evaluate=(kind == 'eval'))
-            self._plans[key] = pl
-        return pl
+    def _plan_key(self, kind, B, H, W, group=0):
+        return (kind, B, H, W, group, self._prec)
+
+    def _build_plan(self, kind, B, H, W, group=0):
+        return _QresPlan(self, self._packed, B, H, W, encode=(kind in ('enc', 'eval')), evaluate=(kind == 'eval'))
 
     def compress_mode(self, mode=True):
         """(:640-647) -> QLatentBlockX.update (:317-325): 64 log-spaced scales 0.1..20, stock erfc-form tables."""
         if mode:
             table = log_spaced_table(0.1, 20, 64)
-            first = None
-            for b in self.decoder.dec_blocks:
-                if b.kind != 'qlb':
-                    continue
-                dg = b.discrete_gaussian
-                if first is None:
-                    dg.update_scale_table(table, force=True)
-                    first = dg
-                else:
-                    dg.scale_table = first.scale_table
-                    dg._quantized_cdf, dg._offset, dg._cdf_length, dg._host = first._quantized_cdf, first._offset, first._cdf_length, None
+            dgs = self._build_cdf_tables(lambda dg: dg.update_scale_table(table, force=True))
+            for dg in dgs[1:]:
+                dg.scale_table = dgs[0].scale_table
             if isinstance(self.out_net, GaussianNLLOutParams):            # (:645-646)
                 self.out_net.update()
             self._log_precision()
             # the packed device copy holds the scale table: one built before this call (encode_trace(), or a compress() that
             # stopped at 'Uninitialized CDFs') would keep the empty pre-update table
-            self._packed, self._plans = None, {}
+            self._invalidate()
         self.compressing = mode
 
     @torch.no_grad()
@@ -654,12 +573,6 @@ class HierarchicalVAE(CodecBase):
         return out
 
     @torch.no_grad()
-    def compress(self, im):
-        """(:649-668)."""
-        assert im.shape[0] == 1, 'use compress_batch for more than one image'
-        return self.compress_batch(im)[0]
-
-    @torch.no_grad()
     @on_model_device
     def decompress_batch(self, objs):
         B = len(objs)
@@ -685,39 +598,27 @@ class HierarchicalVAE(CodecBase):
                                           tables, nthreads, stream)
                 out[start:start + n].copy_(pl.out, non_blocking=True)
                 return
-            lo = 0
-            for li, cut in enumerate(pl.cuts):
-                pl.run(lo, cut, stream=stream.cuda_stream)
-                lo = cut
-                if pl.lossless and li == len(pl.cuts) - 1:   # the per-pixel stream of the output net (:680-682)
-                    px = 3 * H * W
-                    pl.px_idx_host.copy_(pl.px_idx, non_blocking=True)
-                    stream.synchronize()
-                    rans_decode_streams(self.out_net.discrete_gaussian.host_tables(), [objs[start + b][-1][0] for b in range(n)],
-                                        [pl.px_idx_np[b * px:(b + 1) * px] for b in range(n)],
-                                        [pl.px_sym_np[b * px:(b + 1) * px] for b in range(n)], nthreads)
-                    pl.px_sym.copy_(pl.px_sym_host, non_blocking=True)
-                    continue
-                z, hw = pl.lat_shapes[li]
-                o, cnt = pl.idx_off[li], n * z * hw
-                pl.idx_host[o:o + cnt].copy_(pl.idx_all[o:o + cnt], non_blocking=True)
-                stream.synchronize()
-                iv = [pl.idx_np[o + b * z * hw:o + (b + 1) * z * hw] for b in range(n)]
-                sv = [pl.sym_np[o + b * z * hw:o + (b + 1) * z * hw] for b in range(n)]
-                rans_decode_streams(tables, [objs[start + b][li][0] for b in range(n)], iv, sv, nthreads)
-                pl.sym_all[o:o + cnt].copy_(pl.sym_host[o:o + cnt], non_blocking=True)
-            pl.run(lo, None, stream=stream.cuda_stream)
-            pl.fetch_status()                               # read by _check_decoded() after the groups have finished
+            # (every entry but the feature-shape tuple: one string per cut, the lossless model's last being its pixels')
+            strings = [[s[0] for s in o[:si] + o[len(o) + si + 1:]] for o in objs[start:start + n]]
+            self._decode_group_loop(pl, n, strings, tables, nthreads, stream)
             out[start:start + n].copy_(pl.out, non_blocking=True)
 
         self._run_groups(decode_group, groups)
         self._check_decoded(groups, lambda g, n: self._plan('dec', n, H, W, g))
         return out
 
-    @torch.no_grad()
-    def decompress(self, compressed_object):
-        """(:670-687)."""
-        return self.decompress_batch([compressed_object])
+    def _decode_block(self, pl, li, n, strings, tables, nthreads, stream):
+        if not (pl.lossless and li == len(pl.cuts) - 1):
+            return super()._decode_block(pl, li, n, strings, tables, nthreads, stream)
+        px = pl.px_idx.numel() // n                         # the per-pixel stream of the output net (:680-682)
+        pl.px_idx_host.copy_(pl.px_idx, non_blocking=True)
+        stream.synchronize()
+        t1 = time.time()
+        rans_decode_streams(self.out_net.discrete_gaussian.host_tables(), strings,
+                            [pl.px_idx_np[b * px:(b + 1) * px] for b in range(n)],
+                            [pl.px_sym_np[b * px:(b + 1) * px] for b in range(n)], nthreads)
+        pl.px_sym.copy_(pl.px_sym_host, non_blocking=True)
+        return t1
 
     def _pack_blob(self, body, size):
         """(:689-707): pickle of [strings..., feature shape, (h, w)], written through a file object as compress_file always has."""
@@ -731,36 +632,6 @@ class HierarchicalVAE(CodecBase):
         return obj, size, tuple(obj[-2 if isinstance(self.out_net, GaussianNLLOutParams) else -1])
 
     @torch.no_grad()
-    def compress_file(self, img_path, output_path):
-        """(:689-707): pickle of [strings..., feature shape, (h, w)]."""
-        self._compress_to_files([img_path], [output_path])
-
-    @torch.no_grad()
-    def decompress_file(self, bits_path):
-        """(:709-725)."""
-        with open(bits_path, 'rb') as f:
-            obj = pickle.load(file=f)
-        img_h, img_w = obj.pop()
-        return self.decompress(obj)[:, :, :img_h, :img_w]
-
-    @torch.no_grad()
-    def compress_files(self, img_paths, output_paths, images=None):
-        """Batched compress_file (same padded size): one compress_batch call; files identical to compress_file's.  `images`: the files'
-        contents, already decoded (PIL images or uint8 tensors)."""
-        self._compress_to_files(images if images is not None else list(img_paths), output_paths)
-
-    @torch.no_grad()
-    def decompress_files(self, bits_paths):
-        objs, sizes = [], []
-        for p in bits_paths:
-            with open(p, 'rb') as f:
-                obj = pickle.load(file=f)
-            sizes.append(obj.pop())
-            objs.append(obj)
-        out = self.decompress_batch(objs)
-        return [out[i:i + 1, :, :h, :w] for i, (h, w) in enumerate(sizes)]
-
-    @torch.no_grad()
     @on_model_device
     def encode_trace(self, im, full=False, force_z=None):
         """Per-block symbols / indexes of the encode plan (parity tests); `full` / `force_z` as in the qarv model's encode_trace."""
@@ -768,15 +639,7 @@ class HierarchicalVAE(CodecBase):
         self._prepare()
         pl = self._plan('enc', B, H, W)
         pl.im.view(B, 3, H, W).copy_(im)
-        if full or force_z is not None:
-            return self._trace_blocks(pl, B, force_z)
-        pl.run()
-        pl.fetch_status()
-        torch.cuda.current_stream(pl.device).synchronize()
-        pl.raise_if_flagged(where='(encode trace)')
-        sym, idx = pl.sym_all.cpu().numpy(), pl.idx_all.cpu().numpy()
-        return [dict(symbols=sym[o:o + B * z * hw].reshape(B, z, hw).copy(), indexes=idx[o:o + B * z * hw].reshape(B, z, hw).copy())
-                for o, (z, hw) in zip(pl.sym_off, pl.lat_shapes)]
+        return self._trace(pl, B, full, force_z)
 
     # ---- the eval-mode forward pass (reference qresvae/model.py:517-576): rate and distortion without entropy coding
     @torch.no_grad()

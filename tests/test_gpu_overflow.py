@@ -292,7 +292,7 @@ def test_qres_overflow_raises():
     w0 = qlb.z_proj[2].weight.data.clone()
     for scale in (1e5, 1e6, 1e7, 1e8):                  # the first scale that pushes the top-down state past fp16's range
         qlb.z_proj[2].weight.data.copy_(w0 * scale)
-        m._packed, m._plans = None, {}
+        m._invalidate()
         try:
             m.compress(im)
         except lvae.NonFiniteError:
@@ -304,5 +304,5 @@ def test_qres_overflow_raises():
     with pytest.raises(lvae.NonFiniteError):
         m.decompress(obj)
     m.set_gemm_precision('bf16x3')
-    m._packed, m._plans = None, {}
+    m._invalidate()
     assert torch.isfinite(m.decompress(m.compress(im))).all()

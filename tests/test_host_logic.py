@@ -311,3 +311,47 @@ def test_bench_dump_outputs_format_and_cap(tmp_path, monkeypatch):
     assert b.dtype == np.float32 and np.array_equal(b, c)
     assert sum(os.path.getsize(str(tmp_path / 'b' / f)) - 128 for f in os.listdir(str(tmp_path / 'b'))) <= 4 * 64
     assert np.all(np.diff(b) > 0) and set(b.tolist()) <= set(x.numpy().reshape(-1).tolist())
+
+
+class _StubCodec(lvae.models.base.CodecBase):
+    """CodecBase's file decoding on the CPU: a blob is '2H' (h, w) + one byte, the fill value of a 64x64 'reconstruction'."""
+
+    def _unpack_blob(self, blob):
+        return blob[4:], struct.unpack('2H', blob[:4]), len(blob)
+
+    def decompress_batch(self, bodies):
+        self.batches.append(list(bodies))
+        return torch.stack([torch.full((3, 64, 64), float(b[0])) for b in bodies])
+
+
+def test_decompress_file_and_files_crop_to_each_blobs_header(tmp_path):
+    m = _StubCodec()
+    m.batches = []
+    sizes = [(64, 64), (17, 50), (1, 64)]
+    paths = []
+    for i, size in enumerate(sizes):
+        paths.append(tmp_path / f'{i}.bits')
+        paths[-1].write_bytes(struct.pack('2H', *size) + bytes([i + 1]))
+    outs = m.decompress_files(paths)
+    assert m.batches == [[b'\x01', b'\x02', b'\x03']]              # one decompress_batch call, the bodies without their headers
+    for i, (h, w) in enumerate(sizes):
+        assert outs[i].shape == (1, 3, h, w) and bool((outs[i] == i + 1).all())
+    one = m.decompress_file(paths[1])
+    assert one.shape == (1, 3, 17, 50) and bool((one == 2).all())
+    assert m.batches[-1] == [b'\x02']
+
+
+@pytest.mark.parametrize('name', ['qarv_base', 'qres34m'])
+def test_moving_or_loading_weights_invalidates_packed_weights_and_plans(name):
+    m = lvae.get_model(name)
+    sentinel = object()
+    for touch in (lambda: m.to('cpu'), lambda: m.float(), lambda: m.load_state_dict(m.state_dict())):
+        m._packed, m._plans = sentinel, {'key': sentinel}
+        if name == 'qarv_base':
+            m._cur_lmb, m._cur_lmbs = 1.0, (1.0, 2.0)
+        touch()
+        assert m._packed is None and m._plans == {}
+        if name == 'qarv_base':
+            assert m._cur_lmb is None and m._cur_lmbs is None
+    with pytest.raises(RuntimeError, match='GPU only'):
+        m._prepare()
