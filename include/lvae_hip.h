@@ -528,6 +528,33 @@ int lvae_image_u8_to_f32(const uint8_t* const* src, const long* src_row, const i
 int lvae_image_f32_to_u8(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B,
                          uint8_t* const* dst, const long* dst_row, void* stream);
 
+/* ---- Tiled images (csrc/tile_stitch.hip; lvae/utils/tiling.py states the grid rule and the weights): a window of an (h, w) image from
+ * the fp32 reconstructions of the tiles that cover it.  The tiles form a rows x cols grid of common extent (th, tw) with origins oy[rows],
+ * ox[cols] (HOST arrays; they must be what the grid rule gives for (h, th, overlap) and (w, tw, overlap): origin k * (T - overlap) for
+ * every tile but the last of an axis, size - T for the last, a single origin 0 when size <= T -- the tile then holds `size` valid rows /
+ * columns).  tiles: HOST array of rows * cols DEVICE addresses, row-major, null for a tile that was not decoded; element (c, r, q) of a
+ * tile at tile[c*tile_plane + r*tile_row + q] (strides in elements, shared by all tiles: crops of a decoder's padded batch are read
+ * in place).  All three arrays are read before the call returns.
+ * Pixel (y, x) of the image, per axis and covering tile (origin o, u = x - o, r = max(overlap, 1)): wl = o > 0 ? min(1, (u + 0.5) / r) : 1,
+ * wr = o + T < size ? min(1, (T - u - 0.5) / r) : 1, w_axis = min(wl, wr); a tile's weight is wy * wx.  A pixel covered by one tile
+ * takes its value unchanged; otherwise sum_k(w_k v_k) / sum_k(w_k) over the (at most 3 x 3) covering tiles in ascending tile number,
+ * every product, sum and the division rounded to fp32 on its own.  No atomics: two calls give the same bits.
+ * The window (y0, x0, hh, ww) goes to dst: out_u8 == 0: fp32 planes, dst[c*dst_plane + (y - y0)*dst_row + (x - x0)] (elements);
+ * out_u8 != 0: interleaved RGB bytes, dst[(y - y0)*dst_row + 3*(x - x0) + c] = rint(clamp(v, 0, 1) * 255), ties to even, NaN -> 0
+ * (the rounding of lvae_image_f32_to_u8; dst_row in bytes, dst_plane unused).  Only tiles that meet the window are read; nothing outside
+ * the window is written.  Any alignment is accepted: one-tile quads move as 16-byte vectors / 3 dwords where the addresses allow it.
+ * ws: device scratch of at least lvae_tile_stitch_workspace_bytes(rows, cols) bytes, 8-byte aligned.
+ * Fixed sequence on `stream`, whatever the number of tiles: one small host-to-device copy (addresses and origins into ws), one launch.
+ * -22 before any HIP call: a null pointer, a null entry of `tiles` for a tile that meets the window, a window that is empty or not
+ * inside the image, tile strides that do not hold (th, tw), destination strides that do not hold the window, overlap outside
+ * [0, T / 2] on an axis with more than one tile, origins that are not the grid rule's, ws too small or misaligned.
+ * Added without a change to lvae_abi_version(), like the image entries above. */
+int lvae_tile_stitch(const float* const* tiles, long tile_plane, long tile_row, const int* oy, const int* ox, int rows, int cols,
+                     int th, int tw, int overlap, int h, int w, int y0, int x0, int hh, int ww, void* dst, long dst_plane,
+                     long dst_row, int out_u8, void* ws, size_t ws_bytes, void* stream);
+/* Bytes of scratch lvae_tile_stitch needs; 0 when rows or cols <= 0. */
+size_t lvae_tile_stitch_workspace_bytes(int rows, int cols);
+
 /* Stream ordering for launch plans with independent branches (lvae/engine.py: Plan.fork / Plan.join): an event without timing, and
  * "work enqueued on to_stream from now on runs after the work enqueued on from_stream so far" (hipEventRecord + hipStreamWaitEvent). */
 void* lvae_event_create(void);

@@ -136,6 +136,8 @@ SIGNATURES = {
     'lvae_msssim_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'lvae_image_u8_to_f32': (_i, [_vp, _vp, _vp, _i, _vp, _l, _i, _i, _vp]),
     'lvae_image_f32_to_u8': (_i, [_vp, _l, _l, _l, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    'lvae_tile_stitch': (_i, [_vp, _l, _l, _vp, _vp] + [_i] * 11 + [_vp, _l, _l, _i, _vp, _sz, _vp]),
+    'lvae_tile_stitch_workspace_bytes': (_sz, [_i, _i]),
 }
 
 

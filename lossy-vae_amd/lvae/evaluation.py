@@ -78,6 +78,22 @@ def _stats(num_bits, real, mse):
     return {'bpp': float(num_bits / float(real.shape[1] * real.shape[2])), 'mse': float(mse), 'psnr': float(-10 * math.log10(mse))}
 
 
+def _eval_one_tiled(model, impath, tile, overlap, ms=False):
+    """_eval_one through the tiled path: compress_tiled / decompress_tiled(out='f32'); the bits are the whole container's."""
+    from .utils.image import load_u8, to_float01
+    dev = _u8_codec(model)
+    if dev is None or not hasattr(model, 'compress_tiled'):
+        raise ValueError('tile=...: the model has no tiled coding (compress_tiled) or is not on a GPU')
+    u8 = load_u8(impath).to(dev, non_blocking=True)
+    blob = model.compress_tiled(u8, tile=tile, overlap=overlap)
+    fake = model.decompress_tiled(blob, out='f32')
+    real = to_float01([u8], device=dev)[0][0]
+    out = _stats(len(blob) * 8, real, _mse(real, fake))
+    if ms:
+        out['ms-ssim'] = _ms_ssim([real], [fake])[0]
+    return out
+
+
 def _eval_one(model, impath, tmp_bits_dir, tag='', ms=False):
     from PIL import Image
     tmp_bits_path = tmp_bits_dir / f'{impath.stem}{tag}.bits'
@@ -100,9 +116,11 @@ def _eval_one(model, impath, tmp_bits_dir, tag='', ms=False):
 
 
 @torch.no_grad()
-def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',)):
+def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=None, overlap=0):
     """dict {bpp, mse, psnr}: dataset means of per-image values (evaluation.py:59-66).  metrics=('psnr', 'ms-ssim') adds the key
-    'ms-ssim' (lvae.metrics.ms_ssim, mean over images); the other keys are the same floats either way."""
+    'ms-ssim' (lvae.metrics.ms_ssim, mean over images); the other keys are the same floats either way.  tile=(th, tw): every image is
+    coded in tiles (compress_tiled / decompress_tiled(out='f32') with `overlap`) and bpp counts the whole tiled container; tile=None
+    is the whole-image path, float for float."""
     ms = _want_ms_ssim(metrics)
     assert hasattr(model, 'compress_file') and hasattr(model, 'decompress_file')
     img_paths = _list_images(dataset)
@@ -113,7 +131,7 @@ def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',)):
         from tqdm import tqdm
         it = tqdm(img_paths, ascii=True)
     for impath in it:
-        stats = _eval_one(model, impath, tmp_bits_dir, ms=ms)
+        stats = _eval_one(model, impath, tmp_bits_dir, ms=ms) if tile is None else _eval_one_tiled(model, impath, tile, overlap, ms=ms)
         n += 1
         for k, v in stats.items():      # timm AverageMeter: running sum / count
             sums[k] += v

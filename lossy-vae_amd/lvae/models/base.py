@@ -645,6 +645,122 @@ class CodecBase(nn.Module):
             with open(out, 'wb') as f:
                 f.write(blob)
 
+    # ---- tiled coding of large images (lvae/utils/tiling.py: grid, weights, container; csrc/tile_stitch.hip: the blend).  A tile's bytes
+    # are exactly compress_images' for that crop, so the streams of the models do not change; all tiles of an image share one shape,
+    # hence one launch plan, and activation memory follows the tile and max_batch, not the image.
+    def _blob_lmb(self, blob):
+        """The lambda a compress_images blob was coded at (variable-rate models; header parsing only)."""
+        return None
+
+    def _tile_args(self, tile, overlap):
+        th, tw = (int(v) for v in tile)
+        d = self.max_stride
+        if th <= 0 or tw <= 0 or th % d or tw % d:
+            raise ValueError(f'tile {(th, tw)}: both sides must be positive multiples of max_stride = {d}')
+        return th, tw, int(overlap)
+
+    @torch.no_grad()
+    def compress_tiled(self, image, tile=(512, 768), overlap=0, lmb=None, max_batch=8):
+        """One (h, w, 3) uint8 image (anything compress_images takes) -> the bytes of a tiled container (utils.tiling.pack_tiled).  The
+        image is uploaded once; its tiles (utils.tiling.tile_grid) are views of it, coded `max_batch` at a time through compress_images,
+        so tile k's blob is compress_images([image[y:y + th, x:x + tw]])[0].  tile: (th, tw), multiples of max_stride; overlap: pixels
+        neighbouring tiles share (blended on decode).  lmb: None, a number or -- variable-rate models -- a (rows, cols) array with one
+        lambda per tile; fixed-rate models raise ValueError on anything but None."""
+        from ..utils import tiling
+        from ..utils.image import _as_u8
+        th, tw, overlap = self._tile_args(tile, overlap)
+        if lmb is not None and not self.variable_rate:
+            raise ValueError(f'{type(self).__name__} is a fixed-rate model: it takes no lmb')
+        img = _as_u8(image).to(self._dummy.device, non_blocking=True)
+        h, w = int(img.shape[0]), int(img.shape[1])
+        ys, xs = tiling.tile_grid(h, w, th, tw, overlap)
+        n = len(ys) * len(xs)
+        lmbs = None
+        if lmb is not None and not isinstance(lmb, (int, float)):
+            lmbs = np.asarray(lmb.detach().cpu() if isinstance(lmb, torch.Tensor) else lmb, dtype=np.float64)
+            if lmbs.ndim == 0:
+                lmb, lmbs = float(lmbs), None
+            elif lmbs.shape != (len(ys), len(xs)):
+                raise ValueError(f'lmb map of shape {lmbs.shape} for a {len(ys)} x {len(xs)} tile grid')
+            else:
+                lmbs = lmbs.reshape(-1).tolist()
+        views = [img[y:y + th, x:x + tw] for y in ys for x in xs]
+        blobs, step = [], max(1, int(max_batch))
+        for o in range(0, n, step):
+            kw = {} if lmb is None else {'lmb': lmbs[o:o + step] if lmbs is not None else lmb}
+            blobs += self.compress_images(views[o:o + step], **kw)
+        return tiling.pack_tiled(h, w, th, tw, overlap, blobs)
+
+    def tiled_info(self, blob):
+        """Header parsing only (no GPU): dict(h, w, tile, overlap, rows, cols, ys, xs, lengths, lmb) of a tiled container; lmb: the
+        (rows, cols) nested list of the tiles' lambdas on variable-rate models, else None."""
+        from ..utils import tiling
+        c = tiling.unpack_tiled(blob)
+        lm = None
+        if self.variable_rate:
+            flat = [self._blob_lmb(t) for t in c['tiles']]
+            lm = [flat[r * c['cols']:(r + 1) * c['cols']] for r in range(c['rows'])]
+        return dict(h=c['h'], w=c['w'], tile=(c['th'], c['tw']), overlap=c['overlap'], rows=c['rows'], cols=c['cols'], ys=c['ys'], xs=c['xs'],
+                    lengths=c['lengths'], lmb=lm)
+
+    @torch.no_grad()
+    def _decode_tiled(self, blob, box, out, max_batch):
+        from ..utils import tiling
+        from ..utils.image import stitch_tiles
+        if out not in ('u8', 'f32'):
+            raise ValueError(f"out is 'u8' or 'f32', got {out!r}")
+        c = tiling.unpack_tiled(blob)
+        h, w, th, tw = c['h'], c['w'], c['th'], c['tw']
+        self._tile_args((th, tw), c['overlap'])
+        if box is None:
+            box = (0, 0, h, w)
+        y0, x0, hh, ww = (int(v) for v in box)
+        if y0 < 0 or x0 < 0 or hh <= 0 or ww <= 0 or y0 + hh > h or x0 + ww > w:
+            raise ValueError(f'box {(y0, x0, hh, ww)} is not inside the {h} x {w} image')
+        d = self.max_stride
+        eth, etw = min(th, d * math.ceil(h / d)), min(tw, d * math.ceil(w / d))      # what a tile's reconstruction holds
+        need = tiling.tiles_in_box(c['ys'], c['xs'], th, tw, (y0, x0, hh, ww))
+        tiles, keep, step = [None] * len(c['tiles']), [], max(1, int(max_batch))
+        for o in range(0, len(need), step):
+            idxs = need[o:o + step]
+            parsed = [self._unpack_blob(c['tiles'][k]) for k in idxs]
+            for k, (_, size, _) in zip(idxs, parsed):
+                if tuple(size) != (min(h, th), min(w, tw)):
+                    raise ValueError(f'tiled container: tile {k} holds {tuple(size)} pixels, the grid says {(min(h, th), min(w, tw))}')
+            x = self.decompress_batch([p[0] for p in parsed])
+            if tuple(x.shape[1:]) != (3, eth, etw):
+                raise ValueError(f'tiled container: tiles decode to {tuple(x.shape[2:])}, the header says {(eth, etw)}')
+            keep.append(x)
+            for i, k in enumerate(idxs):
+                tiles[k] = x[i]
+        return stitch_tiles(tiles, h, w, eth, etw, c['overlap'], box=(y0, x0, hh, ww), out=out)
+
+    def decompress_tiled(self, blob, out='u8', max_batch=8):
+        """compress_tiled bytes -> the (h, w, 3) uint8 image on the model's device, or (out='f32') the (1, 3, h, w) fp32 one: tiles decoded
+        `max_batch` at a time with decompress_batch, overlaps blended and rounded on the device (lvae_tile_stitch)."""
+        return self._decode_tiled(blob, None, out, max_batch)
+
+    def decompress_region(self, blob, box, out='u8', max_batch=8):
+        """box = (y0, x0, hh, ww) of a tiled image: only the tiles that intersect the box are decoded and only the window is stitched;
+        equal to decompress_tiled(blob)[y0:y0 + hh, x0:x0 + ww]."""
+        return self._decode_tiled(blob, box, out, max_batch)
+
+    def compress_file_tiled(self, img_path, out_path, tile=(512, 768), overlap=0, lmb=None, max_batch=8):
+        blob = self.compress_tiled(img_path, tile=tile, overlap=overlap, lmb=lmb, max_batch=max_batch)
+        with open(out_path, 'wb') as f:
+            f.write(blob)
+        return len(blob)
+
+    def decompress_file_tiled(self, bits_path, png_path=None, box=None, out='u8', max_batch=8):
+        """A compress_file_tiled file -> the image (box: a region of it) as decompress_tiled returns it; png_path: also written as a PNG."""
+        from ..utils.image import save_u8
+        with open(bits_path, 'rb') as f:
+            blob = f.read()
+        x = self._decode_tiled(blob, box, out, max_batch)
+        if png_path is not None:
+            save_u8(x if out == 'u8' else self._decode_tiled(blob, box, 'u8', max_batch), png_path)
+        return x
+
     # ---- the reference's single-image and file API, on the batch interfaces.  A variable-rate model adds `lmb` to the compress side
     @torch.no_grad()
     def compress(self, im):

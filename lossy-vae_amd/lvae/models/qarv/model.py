@@ -798,6 +798,9 @@ class VariableRateLossyVAE(CodecBase):
     def _unpack_blob(self, blob):
         return blob[4:], struct.unpack('2H', blob[:4]), bytes(blob[8:14])         # key: the 3H latent shape behind the lambda
 
+    def _blob_lmb(self, blob):
+        return struct.unpack('f', blob[4:8])[0]
+
     @torch.no_grad()
     def compress_file(self, img_path, output_path, lmb=None):
         """qarv/model.py:559-570."""

@@ -3,6 +3,7 @@
 On the GPU the two conversions are the HIP kernels of csrc/image_io.hip (`lvae_image_u8_to_f32`, `lvae_image_f32_to_u8`): an image is
 uploaded as the 3 bytes per pixel its PNG held, replicate-padded and converted where the encoder reads it, and a reconstruction is rounded
 to bytes on the device before it is copied back.  CPU tensors take the expressions of lvae/utils/coding.py -- the same bits.
+`stitch_tiles` puts the decoded tiles of a tiled image (lvae/utils/tiling.py) together on the GPU (csrc/tile_stitch.hip).
 """
 import ctypes
 import math
@@ -143,3 +144,49 @@ def to_u8(x, sizes=None):
                       'image_f32_to_u8')
     del keep
     return outs
+
+
+def stitch_tiles(tiles, h, w, th, tw, overlap, box=None, out='u8', strides=None):
+    """A window of an (h, w) image from the fp32 reconstructions of its tiles (grid and weights: lvae/utils/tiling.py), on the GPU
+    (lvae_tile_stitch: one small copy and one launch on the current stream).  tiles: row-major list with one entry per tile of
+    the grid (utils.tiling.axis_origins per axis) -- a (3, >= th', >= tw') fp32 device tensor with unit column stride, th' = min(th, rows the tile
+    holds), all with the same plane and row strides (crops of a decoder's padded batch are read in place), or None for a tile that was
+    not decoded (allowed where it does not meet the box).  box = (y0, x0, hh, ww), default the whole image.  -> (hh, ww, 3) uint8
+    (out='u8': rint(clamp(v, 0, 1) * 255), ties to even) or (1, 3, hh, ww) fp32 (out='f32').  (th, tw) is the extent the tiles' buffers
+    hold: for an image smaller than a tile along an axis, its padded size there."""
+    from .. import _native
+    from .tiling import axis_origins
+    if out not in ('u8', 'f32'):
+        raise ValueError(f"stitch_tiles: out is 'u8' or 'f32', got {out!r}")
+    if min(h, w, th, tw) <= 0 or overlap < 0 or (h > th and overlap > th // 2) or (w > tw and overlap > tw // 2):
+        raise ValueError(f'stitch_tiles: image {(h, w)}, tiles {(th, tw)}, overlap {overlap}')
+    ys, xs = axis_origins(h, th, overlap), axis_origins(w, tw, overlap)
+    if len(tiles) != len(ys) * len(xs):
+        raise ValueError(f'stitch_tiles: {len(tiles)} tiles for a {len(ys)} x {len(xs)} grid')
+    y0, x0, hh, ww = (0, 0, h, w) if box is None else (int(v) for v in box)
+    have = [t for t in tiles if t is not None]
+    if not have:
+        raise ValueError('stitch_tiles: no decoded tile')
+    t0 = have[0]
+    device = t0.device
+    for t in have:
+        if (t.dtype != torch.float32 or t.device != device or t.dim() != 3 or t.shape[0] != 3 or t.stride(2) != 1
+                or t.stride()[:2] != t0.stride()[:2]):
+            raise ValueError('stitch_tiles: tiles are (3, th, tw) fp32 tensors on one device with unit column stride and common strides')
+    lib = _native.lib()
+    n = len(tiles)
+    addr = (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in tiles])
+    oy, ox = (ctypes.c_int * len(ys))(*ys), (ctypes.c_int * len(xs))(*xs)
+    with torch.cuda.device(device):
+        if out == 'u8':
+            dst = torch.empty(hh, ww, 3, dtype=torch.uint8, device=device)
+            d_plane, d_row = 0, 3 * ww
+        else:
+            dst = torch.empty(1, 3, hh, ww, dtype=torch.float32, device=device)
+            d_plane, d_row = hh * ww, ww
+        nbytes = lib.lvae_tile_stitch_workspace_bytes(len(ys), len(xs))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _native.check(lib.lvae_tile_stitch(addr, t0.stride(0), t0.stride(1), oy, ox, len(ys), len(xs), th, tw, overlap, h, w, y0, x0, hh, ww,
+                                           dst.data_ptr(), d_plane, d_row, 1 if out == 'u8' else 0, ws.data_ptr(), nbytes, st), 'tile_stitch')
+    return dst
