@@ -231,7 +231,9 @@ int lvae_gemm_num_configs(void);      /* number of selectable tile configuration
 
 /* Native replay of a recorded launch-plan segment (csrc/plan_runtime.cpp; lvae/engine.py: Plan.run): ONE foreign call instead of one
  * per launch.  Every entry names an entry point of this header (`kind`) and carries its arguments by class in call order: pointers in
- * p[], integers (int / long) in i[], floats in f[]; the stream argument comes from the call (`side` != 0: the side stream).
+ * p[], integers (int / long) in i[], floats in f[]; the stream argument comes from the call (`side` != 0: the side stream).  That rule
+ * is all there is: the library walks the entry point's prototype above / below, left to right, and takes each parameter from the next
+ * slot of its class, cast to the parameter's type (csrc/plan_ops.h) -- no per-kind argument layout exists beside the prototypes.
  * LVAE_OP_ORDER: p[0] = event, i[0] != 0: side stream waits for main (fork), else main waits for side (join).
  * Returns 0, or the first failing launch's code with its index in *failed_index (may be NULL). */
 enum {

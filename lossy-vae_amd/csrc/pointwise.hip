@@ -931,101 +931,83 @@ __global__ __launch_bounds__(256) void sqerr_kernel(const float* __restrict__ a,
 int lvae_dwln_cl_try(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b, const float* shift,
                      const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, long vs, hipStream_t st, int* rc);
 
-extern "C" int lvae_dwconv_ln_f32(const float* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
-                                  const float* shift, const float* scale1p, float* y, int B, int H, int W, int C, int k,
-                                  void* stream) {
+// The eight lvae_dwconv_ln_* entry points differ in the output format (`fmt` of lvae_dwln_cl_try: 0 fp32, 1 bf16, 2 H2K32, 3 Q8) and in
+// whether the AdaLN vectors are per image (`vstride` given: image b is modulated by shift + b * *vstride / scale1p + b * *vstride, in
+// elements; no LayerNorm affine).  Only the channel-per-lane kernel has the pre-split / quantised formats and the per-image form: there
+// every other shape is an argument error (-22), never another kernel.
+static int dwln(int fmt, const long* vstride, const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
+                const float* shift, const float* scale1p, void* y, int B, int H, int W, int C, int k, void* stream) {
     if (!x || !wt || !bias || !y || B <= 0 || H <= 0 || W <= 0) return -22;
-    if ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr)) return -22;
-    {
-        int rc = 0;
-        if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 0, 0, (hipStream_t)stream, &rc)) return rc;
-    }
+    if (vstride ? (!shift || !scale1p || *vstride < 0) : ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr))) return -22;
     hipStream_t st = (hipStream_t)stream;
+    int rc = 0;
+    if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, fmt, vstride ? *vstride : 0, st, &rc)) return rc;
+    if (vstride || fmt >= 2) return -22;
+    // the sliding-window kernel: the other channel counts (qres17m: C = 144 / 288) and the two-affine case, fp32 and bf16 maps
+    const float* xf = (const float*)x;
+    float* yf = (float*)y;
     switch (k) {
-        case 1: return dispatch_dwln_c<1>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 3: return dispatch_dwln_c<3>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 5: return dispatch_dwln_c<5>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 7: return dispatch_dwln_c<7>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
+        case 1: return fmt ? dispatch_dwln_bf16<1>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
+                           : dispatch_dwln_c<1>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
+        case 3: return fmt ? dispatch_dwln_bf16<3>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
+                           : dispatch_dwln_c<3>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
+        case 5: return fmt ? dispatch_dwln_bf16<5>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
+                           : dispatch_dwln_c<5>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
+        case 7: return fmt ? dispatch_dwln_bf16<7>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
+                           : dispatch_dwln_c<7>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
     }
     return -22;
 }
 
+extern "C" int lvae_dwconv_ln_f32(const float* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
+                                  const float* shift, const float* scale1p, float* y, int B, int H, int W, int C, int k, void* stream) {
+    return dwln(0, nullptr, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, stream);
+}
+extern "C" int lvae_dwconv_ln_bf16(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
+                                   const float* shift, const float* scale1p, void* y, int B, int H, int W, int C, int k, void* stream) {
+    return dwln(1, nullptr, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, stream);
+}
 extern "C" int lvae_dwconv_ln_h2(const float* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
                                  const float* shift, const float* scale1p, void* y, int B, int H, int W, int C, int k, void* stream) {
-    if (!x || !wt || !bias || !y || B <= 0 || H <= 0 || W <= 0) return -22;
-    if ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr)) return -22;
-    int rc = 0;
-    return lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 2, 0, (hipStream_t)stream, &rc) ? rc : -22;
+    return dwln(2, nullptr, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, stream);
 }
-
 extern "C" int lvae_dwconv_ln_q8(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
                                  const float* shift, const float* scale1p, void* y, int B, int H, int W, int C, int k, void* stream) {
-    if (!x || !wt || !bias || !y || B <= 0 || H <= 0 || W <= 0) return -22;
-    if ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr)) return -22;
-    int rc = 0;
-    return lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 3, 0, (hipStream_t)stream, &rc) ? rc : -22;
-}
-
-extern "C" int lvae_stem_f32(const float* im, const float* wt, const float* bias, float* out, int B, int H, int W,
-                             int Cout, float im_shift, float im_scale, int* range_flag, void* stream) {
-    if (!im || !wt || !bias || !out || B <= 0 || (H & 3) || (W & 3) || Cout <= 0 || Cout > 256) return -22;
-    const long M = (long)B * (H / 4) * (W / 4);
-    hipLaunchKernelGGL(stem_kernel<false>, dim3((unsigned)((M + 63) / 64)), dim3(Cout), 0, (hipStream_t)stream, im, wt, bias, out,
-                       B, H, W, Cout, im_shift, im_scale, M, range_flag);
-    return (int)hipGetLastError();
-}
-
-extern "C" int lvae_stem_bf16(const float* im, const float* wt, const float* bias, void* out, int B, int H, int W,
-                              int Cout, float im_shift, float im_scale, int* range_flag, void* stream) {
-    if (!im || !wt || !bias || !out || B <= 0 || (H & 3) || (W & 3) || Cout <= 0 || Cout > 256) return -22;
-    const long M = (long)B * (H / 4) * (W / 4);
-    hipLaunchKernelGGL(stem_kernel<true>, dim3((unsigned)((M + 63) / 64)), dim3(Cout), 0, (hipStream_t)stream, im, wt, bias, out,
-                       B, H, W, Cout, im_shift, im_scale, M, range_flag);
-    return (int)hipGetLastError();
-}
-
-extern "C" int lvae_dwconv_ln_bf16(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
-                                   const float* shift, const float* scale1p, void* y, int B, int H, int W, int C, int k,
-                                   void* stream) {
-    if (!x || !wt || !bias || !y || B <= 0 || H <= 0 || W <= 0) return -22;
-    if ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr)) return -22;
-    hipStream_t st = (hipStream_t)stream;
-    {
-        int rc = 0;
-        if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, 1, 0, st, &rc)) return rc;
-    }
-    switch (k) {
-        case 1: return dispatch_dwln_bf16<1>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 3: return dispatch_dwln_bf16<3>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 5: return dispatch_dwln_bf16<5>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 7: return dispatch_dwln_bf16<7>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-    }
-    return -22;
-}
-
-// Per-image AdaLN vectors: image b of the batch is modulated by shift + b * vstride / scale1p + b * vstride (elements).  Only the
-// channel-per-lane kernel has this form; every other shape is an argument error (-22), never another kernel.
-static int dwln_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y, int B, int H, int W,
-                  int C, int k, long vstride, int fmt, void* stream) {
-    if (!x || !wt || !bias || !y || !shift || !scale1p || B <= 0 || H <= 0 || W <= 0 || vstride < 0) return -22;
-    int rc = 0;
-    return lvae_dwln_cl_try(x, wt, bias, nullptr, nullptr, shift, scale1p, y, B, H, W, C, k, fmt, vstride, (hipStream_t)stream, &rc) ? rc : -22;
+    return dwln(3, nullptr, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, stream);
 }
 extern "C" int lvae_dwconv_ln_f32_v(const float* x, const float* wt, const float* bias, const float* shift, const float* scale1p, float* y,
                                     int B, int H, int W, int C, int k, long vstride, void* stream) {
-    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 0, stream);
+    return dwln(0, &vstride, x, wt, bias, nullptr, nullptr, shift, scale1p, y, B, H, W, C, k, stream);
 }
 extern "C" int lvae_dwconv_ln_bf16_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
                                      int B, int H, int W, int C, int k, long vstride, void* stream) {
-    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 1, stream);
+    return dwln(1, &vstride, x, wt, bias, nullptr, nullptr, shift, scale1p, y, B, H, W, C, k, stream);
 }
 extern "C" int lvae_dwconv_ln_h2_v(const float* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
                                    int B, int H, int W, int C, int k, long vstride, void* stream) {
-    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 2, stream);
+    return dwln(2, &vstride, x, wt, bias, nullptr, nullptr, shift, scale1p, y, B, H, W, C, k, stream);
 }
 extern "C" int lvae_dwconv_ln_q8_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
                                    int B, int H, int W, int C, int k, long vstride, void* stream) {
-    return dwln_v(x, wt, bias, shift, scale1p, y, B, H, W, C, k, vstride, 3, stream);
+    return dwln(3, &vstride, x, wt, bias, nullptr, nullptr, shift, scale1p, y, B, H, W, C, k, stream);
+}
+
+template <bool BF>
+static int stem(const float* im, const float* wt, const float* bias, void* out, int B, int H, int W, int Cout, float im_shift, float im_scale,
+                int* range_flag, void* stream) {
+    if (!im || !wt || !bias || !out || B <= 0 || (H & 3) || (W & 3) || Cout <= 0 || Cout > 256) return -22;
+    const long M = (long)B * (H / 4) * (W / 4);
+    hipLaunchKernelGGL(stem_kernel<BF>, dim3((unsigned)((M + 63) / 64)), dim3(Cout), 0, (hipStream_t)stream, im, wt, bias, out,
+                       B, H, W, Cout, im_shift, im_scale, M, range_flag);
+    return (int)hipGetLastError();
+}
+extern "C" int lvae_stem_f32(const float* im, const float* wt, const float* bias, float* out, int B, int H, int W,
+                             int Cout, float im_shift, float im_scale, int* range_flag, void* stream) {
+    return stem<false>(im, wt, bias, out, B, H, W, Cout, im_shift, im_scale, range_flag, stream);
+}
+extern "C" int lvae_stem_bf16(const float* im, const float* wt, const float* bias, void* out, int B, int H, int W,
+                              int Cout, float im_shift, float im_scale, int* range_flag, void* stream) {
+    return stem<true>(im, wt, bias, out, B, H, W, Cout, im_shift, im_scale, range_flag, stream);
 }
 
 namespace {

@@ -226,14 +226,14 @@ class CodecPlan(Plan):
             self.idx_host = torch.empty(n_sym, dtype=torch.uint8).pin_memory()
             self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
 
-    def dwln_add(self, fn, p, x, y, H, W, C, k):
-        """Record block p's depthwise + LayerNorm launch `fn` (the kernel of the wanted output format) as p + '.dwln', with the model's
-        affine: LayerNorm weights, or AdaLN vectors."""
+    def dwln_add(self, fmt, p, x, y, H, W, C, k):
+        """Record block p's depthwise + LayerNorm launch with output format `fmt` ('f32' | 'h2' | 'bf16' | 'q8': lvae_dwconv_ln_<fmt>) as
+        p + '.dwln', with the model's affine: LayerNorm weights, or AdaLN vectors."""
         raise NotImplementedError
 
     def cnx(self, p, m, x, out, H, W):
         """A ConvNeXt block = depthwise+LN(+affine) kernel, fc1+GELU GEMM, fc2+gamma+residual GEMM."""
-        pk, lib = self.pk, self.lib
+        pk = self.pk
         C, k, hid = m.dim, m.kernel_size, m.hidden
         M = self.B * H * W
         y = self.buf(self.sname('y'), M * C, self.adt).data_ptr()
@@ -245,13 +245,13 @@ class CodecPlan(Plan):
         # (small maps: the split-K layers -- pre-split + serial split-K where the batch makes that the faster form, same bits: engine.mlp_pipeline)
         if self.mlp_fused_ok(C, hid, k, M=M, rows_per_image=H * W):
             # the stride-4 blocks: fc1 -> GELU -> fc2 as one launch, the hidden tile never leaves the CU (csrc/mlp_h2c.hip)
-            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y, H, W, C, k)
+            self.dwln_add('h2', p, x, y, H, W, C, k)
             self.mlp_fused(**mlp)
             return
         sk = self.mlp_sk_ok(C, hid, k, H * W, M) if self.use_mlp_sk else None
         if sk is not None:
             # stride-32 / 64 maps (both GEMMs split-K): fc1 -> GELU -> fc2's partial sums as one launch, then the reduce launch
-            self.dwln_add(lib.lvae_dwconv_ln_h2, p, x, y, H, W, C, k)
+            self.dwln_add('h2', p, x, y, H, W, C, k)
             self.mlp_sk(S1=sk[0], S2=sk[1], **mlp)
             return
         h = self.buf(self.sname('hid'), M * hid, self.adt).data_ptr()
@@ -259,11 +259,8 @@ class CodecPlan(Plan):
             pre1, pre2, S1, S2 = True, True, None, None
         else:
             pre1, pre2, S1, S2 = self.mlp_pipeline(C, hid, k, H * W)
-        if self.lp:
-            fn = lib.lvae_dwconv_ln_q8 if pre1 else lib.lvae_dwconv_ln_bf16
-        else:
-            fn = lib.lvae_dwconv_ln_h2 if pre1 else lib.lvae_dwconv_ln_f32
-        self.dwln_add(fn, p, x, y, H, W, C, k)
+        fmt = ('q8' if pre1 else 'bf16') if self.lp else ('h2' if pre1 else 'f32')
+        self.dwln_add(fmt, p, x, y, H, W, C, k)
         self.gemm(A0=y, K0=C, M=M, N=hid, Wt=pk.p(p + '.fc1_w'), bias=pk.p(p + '.fc1_b'), out=h,
                   epi=_native.EPI_BIAS_GELU, a_h2=pre1, out_h2=pre2, ksplit=S1, label=p + '.fc1')
         self.gemm(A0=h, K0=hid, M=M, N=C, Wt=pk.p(p + '.fc2_w'), bias=pk.p(p + '.fc2_b'),
@@ -404,16 +401,14 @@ class CodecBase(nn.Module):
             segs, lo = [], 0
             for li, cut in enumerate(cuts):
                 seg, n_ops = pl._segment(lo, cut)
+                seg = cls_._alias_host(pl, seg, n_ops)     # the launches write / read the pinned host arrays: no device arrays, no copies
                 segs.append(seg)
                 z, hw = pl.lat_shapes[li]
                 o = offs[li]
                 b = arr[li]
                 b.ops, b.n_ops, b.per_image = ctypes.cast(seg, ctypes.c_void_p).value, n_ops, z * hw
-                b.idx_dev, b.idx_host = pl.idx_all.data_ptr() + o, pl.idx_host.data_ptr() + o
-                b.sym_dev, b.sym_host = pl.sym_all.data_ptr() + 4 * o, pl.sym_host.data_ptr() + 4 * o
-                seg = cls_._alias_host(pl, seg, n_ops)
-                segs[-1] = seg
-                b.ops, b.idx_dev, b.sym_dev = ctypes.cast(seg, ctypes.c_void_p).value, None, None
+                b.idx_dev, b.idx_host = None, pl.idx_host.data_ptr() + o
+                b.sym_dev, b.sym_host = None, pl.sym_host.data_ptr() + 4 * o
                 lo = cut
             tail, n_tail = pl._segment(lo, len(pl.ops)) if kind == 'dec' else (None, 0)
             if n_tail:                                     # (the last block's symbols are read by the tail's first launch)

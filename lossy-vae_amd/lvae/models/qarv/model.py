@@ -211,16 +211,17 @@ class _NetPlan(CodecPlan):
         n = self.pk.adaln_total
         self.adaln_slab.copy_(table[start * n:(start + self.B) * n], non_blocking=True)
 
-    def dwln_add(self, fn, p, x, y, H, W, C, k):
-        """Record the depthwise + LayerNorm + AdaLN launch of block p: `fn` with the model-wide vectors, its _v form with the slab's."""
+    def dwln_add(self, fmt, p, x, y, H, W, C, k):
+        """Record the depthwise + LayerNorm + AdaLN launch of block p: lvae_dwconv_ln_<fmt> with the model-wide vectors, its _v form with
+        the slab's."""
         pk = self.pk
         off = pk.adaln_off[p]
         if self.vec:
-            self.add(getattr(self.lib, fn.lvae_name + '_v'), (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), ptr(self.adaln_slab, off),
-                                                             ptr(self.adaln_slab, off + C), y, self.B, H, W, C, k, pk.adaln_total), p + '.dwln')
+            self.add(getattr(self.lib, f'lvae_dwconv_ln_{fmt}_v'), (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), ptr(self.adaln_slab, off),
+                                                                   ptr(self.adaln_slab, off + C), y, self.B, H, W, C, k, pk.adaln_total), p + '.dwln')
         else:
-            self.add(fn, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), None, None, ptr(pk.adaln, off), ptr(pk.adaln, off + C), y, self.B, H, W, C, k),
-                     p + '.dwln')
+            self.add(getattr(self.lib, f'lvae_dwconv_ln_{fmt}'), (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), None, None, ptr(pk.adaln, off),
+                                                                 ptr(pk.adaln, off + C), y, self.B, H, W, C, k), p + '.dwln')
 
     def cnx(self, p, m, x, out, H, W):
         """ConvNeXtBlockAdaLN (common.py:142-161).  The hidden-map scratch is sized at every block, also where the MLP runs fused: the

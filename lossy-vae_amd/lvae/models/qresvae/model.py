@@ -433,10 +433,10 @@ class _QresPlan(CodecPlan):
         if not encode:
             assert self.out is not None
 
-    def dwln_add(self, fn, p, x, y, H, W, C, k):
+    def dwln_add(self, fmt, p, x, y, H, W, C, k):
         """MyConvNeXtBlock (:168-182): the affine is the block's LayerNorm weights."""
         pk = self.pk
-        self.add(fn, (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), pk.p(p + '.ln_w'), pk.p(p + '.ln_b'), None, None, y, self.B, H, W, C, k), p + '.dwln')
+        self.add(getattr(self.lib, 'lvae_dwconv_ln_' + fmt), (x, pk.p(p + '.dw_w'), pk.p(p + '.dw_b'), pk.p(p + '.ln_w'), pk.p(p + '.ln_b'), None, None, y, self.B, H, W, C, k), p + '.dwln')
 
     def vdblock(self, p, m, a0, a1, out, H, W):
         """c4(g(c3(g(c2(g(c1(g(x)))))))) with x = a0 or cat[a0, a1] (each of width cin or cin/2)."""

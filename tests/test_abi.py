@@ -75,3 +75,44 @@ def test_c99_client_round_trips_the_coder(tmp_path):
     assert run.returncode == 0, run.stdout + run.stderr
     tag, abi, nbytes = run.stdout.split()
     assert tag == 'ok' and int(abi) == _native.ABI_VERSION and int(nbytes) > 8
+
+
+def _classes(argtypes):
+    """Plan._segment's rule (lvae/engine.py): the class of every argument in front of the stream."""
+    import ctypes
+    return ''.join('f' if t in (ctypes.c_float, ctypes.c_double) else 'i' if t in (ctypes.c_int, ctypes.c_long) else 'p' for t in argtypes[:-1])
+
+
+def test_plan_ops_routing_matches_the_python_side(tmp_path):
+    """csrc/plan_ops.h derives lvae_run_ops' casts from the prototypes of include/lvae_hip.h; Plan._segment sorts the arguments by the
+    ctypes argtypes of _native.SIGNATURES.  tests/c_client/plan_ops_check.cpp routes sentinel values through the trampoline into fake
+    functions of every shape the table has (it exits non-zero on a mismatch) and prints `kind name classes` for every row of the real
+    table: kinds and names must be _native.OP_KINDS / OP_ORDER, the header's enum must name the same entry points, and every class string
+    must be what _segment's rule gives for that entry point's argtypes -- a c_int where the prototype says float, or a row out of order,
+    fails here and not as a wrong argument of a launch."""
+    import shutil
+    if shutil.which('g++') is None:
+        pytest.skip('no g++ on this host')
+    libdir = os.path.dirname(os.path.abspath(_native.LIB_PATH))
+    exe = str(tmp_path / 'plan_ops_check')
+    cc = subprocess.run(['g++', '-std=c++17', '-Wall', '-Wextra', '-Werror', '-O1', '-I' + os.path.join(REPO, 'lossy-vae_amd', 'csrc'),
+                         os.path.join(REPO, 'tests', 'c_client', 'plan_ops_check.cpp'), '-o', exe, '-L' + libdir, '-l:' + os.path.basename(_native.LIB_PATH),
+                         '-Wl,-rpath,' + libdir], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    rows = [ln.split() for ln in run.stdout.splitlines()]
+    assert rows[-1] == [str(_native.OP_ORDER), 'ORDER', '-']
+    rows = rows[:-1]
+    assert len(rows) == 26
+    assert [(name, int(kind)) for kind, name, _ in rows] == list(_native.OP_KINDS.items())
+    # the header's enum: identifier k (1-based) names row k's entry point
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'lvae_hip.h')).read(), flags=re.S)
+    enum = re.search(r'enum\s*\{\s*(LVAE_OP_GEMM\s*=\s*1\b[^}]*)\}', src).group(1)
+    idents = [e.split('=')[0].strip() for e in enum.split(',')]
+    assert idents[-1] == 'LVAE_OP_ORDER' and len(idents) == _native.OP_ORDER
+    for ident, (_, name, _) in zip(idents, rows):
+        base = 'lvae_' + ident[len('LVAE_OP_'):].lower()
+        assert [n for n in (base, base + '_f32') if n in _native.SIGNATURES] == [name], (ident, name)
+    for _, name, classes in rows:
+        assert classes == _classes(_native.SIGNATURES[name][1]), name
