@@ -530,6 +530,48 @@ int lvae_image_u8_to_f32(const uint8_t* const* src, const long* src_row, const i
 int lvae_image_f32_to_u8(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B,
                          uint8_t* const* dst, const long* dst_row, void* stream);
 
+/* ---- 8-bit YUV 4:2:0 frames in and out of the codec (csrc/yuv_io.hip), with the conventions of the image entries above: HOST arrays
+ * of DEVICE plane addresses and row strides in bytes, hw[2b], hw[2b + 1] = (h_b, w_b), all read before the call returns (16 frames per
+ * launch, descriptors as kernel arguments); fp32 side NCHW RGB planes with unit column stride; any alignment (dword / 16-byte accesses
+ * where the addresses allow, bytes / scalars where not).  A frame is a luma plane of (h, w) bytes and chroma at (h/2, w/2); h and w even.
+ * fmt LVAE_YUV_I420: u[b], v[b] are the two chroma planes; LVAE_YUV_NV12: u[b] is the interleaved UV plane (row stride >= w) and the
+ * arrays v / v_row are not read (they may be null).  matrix: LVAE_YUV_BT601 (Kr, Kb = 0.299, 0.114) / LVAE_YUV_BT709 (0.2126, 0.0722);
+ * range: LVAE_YUV_LIMITED (Y 16..235, C 16..240) / LVAE_YUV_FULL (0..255).  Chroma siting is centre (JPEG / MPEG-1): a chroma sample
+ * sits in the middle of its 2x2 luma block; co-sited chroma is not supported.
+ * The colour parameters are the caller's: no stream or container records them.
+ * -22 before any HIP call: a null pointer (an entry of a plane array included), B <= 0, H or W <= 0, an extent that is 0, odd or beyond
+ * (H, W), a row stride below its plane's width in bytes, fp32 strides that do not hold (H, W), an unknown fmt / matrix / range / chroma.
+ *
+ * lvae_image_yuv420_to_f32: the whole canvas (H, W) of dst[b*dst_img + c*H*W + y*W + x], c = R, G, B, from the luma pixel
+ * (min(y, h_b - 1), min(x, w_b - 1)) (replicate padding, as lvae_image_u8_to_f32).  Chroma at a luma pixel (y, x): chroma
+ * LVAE_YUV_NEAREST: sample (y/2, x/2); LVAE_YUV_BILINEAR: per axis 3/4 of sample x/2 and 1/4 of its neighbour on the pixel's side
+ * (x/2 - 1 for even x, x/2 + 1 for odd x, clamped to the plane) -- exact on bytes.  Then, every operation rounded to fp32 on its own (IEEE
+ * division, no fused multiply-add): y' = (Y - 16) / 219, c = (C - 128) / 224 (limited) or Y / 255, (C - 128) / 255 (full);
+ * R = y' + a*cr, B = y' + b*cb, G = (y' - d*cb) - e*cr with a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg as fp32
+ * constants; clamped to [0, 1].  lvae/utils/yuv.py states the same expression with torch ops; the bits agree. */
+enum { LVAE_YUV_I420 = 0, LVAE_YUV_NV12 = 1 };
+enum { LVAE_YUV_BT601 = 0, LVAE_YUV_BT709 = 1 };
+enum { LVAE_YUV_LIMITED = 0, LVAE_YUV_FULL = 1 };
+enum { LVAE_YUV_NEAREST = 0, LVAE_YUV_BILINEAR = 1 };
+int lvae_image_yuv420_to_f32(const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v, const long* y_row,
+                             const long* u_row, const long* v_row, const int* hw, int B, int fmt, int matrix, int range, int chroma,
+                             float* dst, long dst_img, int H, int W, void* stream);
+/* lvae_image_f32_to_yuv420: the inverse, for reconstructions; src addressed as in lvae_image_f32_to_u8 (crops of a decoder's padded
+ * batch are read in place).  Per pixel, in fp32 with every operation rounded on its own: r, g, b clamped to [0, 1] (NaN -> 0);
+ * y' = (Kr*r + Kg*g) + Kb*b; cb = (b - y') / (2(1 - Kb)), cr = (r - y') / (2(1 - Kr)).  A chroma sample is the mean of its 2x2 block,
+ * ((tl + tr) + (bl + br)) * 0.25.  Bytes: rint(y' * 219 + 16), rint(c * 224 + 128) (limited) or rint(y' * 255), rint(c * 255 + 128)
+ * (full), ties to even, clamped to 0..255.  Nothing outside a plane's extent is written. */
+int lvae_image_f32_to_yuv420(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int fmt,
+                             int matrix, int range, uint8_t* const* y, uint8_t* const* u, uint8_t* const* v, const long* y_row,
+                             const long* u_row, const long* v_row, void* stream);
+/* lvae_sse_u8: out[k] (DEVICE, one 64-bit unsigned integer per pair) = sum over the (h_k, w_k) bytes of (a_k - b_k)^2 for n pairs of byte
+ * planes (HOST arrays of DEVICE addresses, row strides in bytes >= w_k, hw as above), in integer arithmetic throughout: exact, whatever
+ * the scheduling.  `out` is zeroed by the call (a memset on `stream`), then every wave adds its share with one integer atomic.
+ * -22 before any HIP call: a null pointer or entry, n <= 0, a plane of 0 rows or columns, a row stride below w_k. */
+int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uint8_t* const* b, const long* b_row, const int* hw, int n,
+                uint64_t* out, void* stream);
+/* The three entries above were added without a change to lvae_abi_version() (no existing signature changed). */
+
 /* ---- Tiled images (csrc/tile_stitch.hip; lvae/utils/tiling.py states the grid rule and the weights): a window of an (h, w) image from
  * the fp32 reconstructions of the tiles that cover it.  The tiles form a rows x cols grid of common extent (th, tw) with origins oy[rows],
  * ox[cols] (HOST arrays; they must be what the grid rule gives for (h, th, overlap) and (w, tw, overlap): origin k * (T - overlap) for

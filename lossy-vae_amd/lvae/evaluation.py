@@ -138,6 +138,40 @@ def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=No
     return {k: v / n for k, v in sums.items()}
 
 
+@torch.no_grad()
+def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, **colour):
+    """A raw 8-bit 4:2:0 file coded frame by frame (an image codec as an intra-frame coder) -> dict of means over its frames: 'bpp'
+    (8 * len(blob) / (h * w)) and the keys of lvae.metrics.psnr_yuv420 ('mse-y' ... 'psnr-yuv'), computed between the file's bytes and
+    decompress_yuv420's.  colour: matrix / range / chroma of compress_yuv420 (matrix and range also go to decompress_yuv420).  Every frame
+    is uploaded once, as the 1.5 bytes per pixel the file holds; conversion, coding, reconstruction and the squared errors stay on the
+    device, and three integers per frame come back.  Frames are coded `batch` at a time; lmb: as in compress_yuv420."""
+    from .metrics import PSNR_YUV_KEYS, psnr_yuv420
+    from .utils.yuv import read_yuv420
+    unknown = set(colour) - {'matrix', 'range', 'chroma'}
+    if unknown:
+        raise TypeError(f'yuv_evaluate: unexpected arguments {sorted(unknown)}')
+    dev = next(model.parameters()).device
+    frames = [f.to(dev, non_blocking=True) for f in read_yuv420(yuv_path, width, height, fmt, frames=max_frames)]
+    dec = {k: v for k, v in colour.items() if k != 'chroma'}
+    rows, step = [], max(1, int(batch))
+    for o in range(0, len(frames), step):
+        chunk = frames[o:o + step]
+        enc = dict(colour)
+        if lmb is not None:                    # a number, or one lambda per frame of the file
+            enc['lmb'] = lmb if isinstance(lmb, (int, float)) else list(lmb)[o:o + step]
+        blobs = model.compress_yuv420(chunk, **enc)
+        recs = model.decompress_yuv420(blobs, fmt=fmt, **dec)
+        for blob, stats in zip(blobs, psnr_yuv420(chunk, recs)):
+            rows.append(dict(stats, bpp=float(8 * len(blob) / float(height * width))))
+    out = {}
+    for k in ('bpp',) + PSNR_YUV_KEYS:
+        acc = 0.0
+        for r in rows:                         # frame order: the means do not depend on `batch`
+            acc += r[k]
+        out[k] = acc / len(rows)
+    return out
+
+
 class AverageMeter:
     """timm.utils.AverageMeter: running sum / count of the values it is updated with (tensors stay tensors)."""
 

@@ -26,6 +26,67 @@ def psnr(real, fake):
     return float(-10 * math.log10(mse))
 
 
+PSNR_YUV_KEYS = ('mse-y', 'mse-u', 'mse-v', 'psnr-y', 'psnr-u', 'psnr-v', 'psnr-yuv')
+
+
+def sse_u8(pairs):
+    """[(a, b)] pairs of equally shaped 2-D uint8 planes -> their sums of squared differences as Python ints, exact.  If a plane is on a
+    GPU: ONE lvae_sse_u8 launch for all pairs on that device's current stream (integer arithmetic on the device, one 64-bit word per pair
+    comes back; planes with unit column stride are read where they lie); CPU planes: numpy int64."""
+    for a, b in pairs:
+        if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 2 or a.shape != b.shape or a.numel() == 0:
+            raise ValueError(f'sse_u8: expected two equally shaped, non-empty 2-D uint8 planes, got {tuple(a.shape)} and {tuple(b.shape)}')
+    devs = {p.device for ab in pairs for p in ab if p.is_cuda}
+    if len(devs) > 1:
+        raise ValueError(f'sse_u8: planes on several GPUs {sorted(map(str, devs))}')
+    if not devs:
+        out = []
+        for a, b in pairs:
+            d = a.numpy().astype('int64') - b.numpy().astype('int64')
+            out.append(int((d * d).sum()))
+        return out
+    from . import _native
+    device, n = devs.pop(), len(pairs)
+    plane = lambda p: (p if p.stride(1) == 1 and p.stride(0) >= p.shape[1] else p.contiguous())
+    a = [plane(p.to(device, non_blocking=True)) for p, _ in pairs]
+    b = [plane(p.to(device, non_blocking=True)) for _, p in pairs]
+    ptr = lambda ps: (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
+    row = lambda ps: (ctypes.c_long * n)(*[p.stride(0) for p in ps])
+    hw = (ctypes.c_int * (2 * n))(*[int(v) for p in a for v in p.shape])
+    out = torch.empty(n, dtype=torch.int64, device=device)            # (the sums stay far below 2^63: 255^2 per byte)
+    with torch.cuda.device(device):
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _native.check(_native.lib().lvae_sse_u8(ptr(a), row(a), ptr(b), row(b), hw, n, out.data_ptr(), st), 'sse_u8')
+    return [int(v) for v in out.cpu().tolist()]
+
+
+def psnr_yuv420(ref_frames, rec_frames):
+    """PSNR of 8-bit 4:2:0 frames (lists of utils.yuv.Yuv420Frame, or two frames) as video-side comparisons report it: per frame a dict
+    {'mse-y', 'mse-u', 'mse-v', 'psnr-y', 'psnr-u', 'psnr-v', 'psnr-yuv'} of floats.  mse = the plane's exact sum of squared byte
+    differences (sse_u8) / its sample count, in float64; psnr = 10 log10(255^2 / mse), inf for identical planes;
+    psnr-yuv = (6 psnr-y + psnr-u + psnr-v) / 8, the weighting of the HM / VTM reference software for 4:2:0."""
+    from .utils.yuv import Yuv420Frame
+    if isinstance(ref_frames, Yuv420Frame):
+        return psnr_yuv420([ref_frames], [rec_frames])[0]
+    ref, rec = list(ref_frames), list(rec_frames)
+    if len(ref) != len(rec) or not ref:
+        raise ValueError(f'psnr_yuv420: {len(ref)} reference and {len(rec)} reconstructed frames')
+    for i, (a, b) in enumerate(zip(ref, rec)):
+        if a.size != b.size:
+            raise ValueError(f'psnr_yuv420: frame {i} is {a.size} against {b.size}')
+    sse = sse_u8([(getattr(a, p), getattr(b, p)) for a, b in zip(ref, rec) for p in 'yuv'])
+    out = []
+    for i, a in enumerate(ref):
+        row = {}
+        for j, p in enumerate('yuv'):
+            mse = sse[3 * i + j] / float(getattr(a, p).numel())
+            row['mse-' + p] = mse
+            row['psnr-' + p] = float(10 * math.log10(255.0 ** 2 / mse)) if mse > 0 else math.inf
+        row['psnr-yuv'] = (6 * row['psnr-y'] + row['psnr-u'] + row['psnr-v']) / 8
+        out.append({k: row[k] for k in PSNR_YUV_KEYS})
+    return out
+
+
 def ms_ssim_db(v):
     """MS-SSIM on the decibel scale result tables use: -10 log10(1 - v)."""
     if torch.is_tensor(v):

@@ -593,10 +593,14 @@ class CodecBase(nn.Module):
         writes for image i.  lmb: as in compress_batch (variable-rate models only).  The bytes of each image go to the device as they
         are (3 per pixel, unpadded); padding and the division by 255 happen where each pipeline group's plan reads its input."""
         from ..utils.image import U8Batch
-        batch = U8Batch(images, self.max_stride, self._dummy.device)
+        return self._compress_byte_batch(U8Batch(images, self.max_stride, self._dummy.device), lmb, 'compress_images')
+
+    def _compress_byte_batch(self, batch, lmb, who):
+        """compress_batch on a batch of 8-bit inputs (utils.image.U8Batch, utils.yuv.Yuv420Batch: `.shape`, `.sizes`, `.device`, `.fill`)
+        -> the models' containers, one per input."""
         _, _, H, W = batch.shape
         d = self.max_stride
-        assert all((d * math.ceil(h / d), d * math.ceil(w / d)) == (H, W) for h, w in batch.sizes), 'compress_images: padded sizes differ'
+        assert all((d * math.ceil(h / d), d * math.ceil(w / d)) == (H, W) for h, w in batch.sizes), f'{who}: padded sizes differ'
         if self.variable_rate:
             bodies = self.compress_batch(None, lmb=lmb, u8=batch)
         else:
@@ -605,11 +609,8 @@ class CodecBase(nn.Module):
             bodies = self.compress_batch(None, u8=batch)
         return [self._pack_blob(body, size) for body, size in zip(bodies, batch.sizes)]
 
-    @torch.no_grad()
-    def decompress_images(self, blobs):
-        """compress_images / compress_file bytes -> list of (h, w, 3) uint8 tensors on the model's device, each cropped to the size in
-        its header and rounded on the device (round-half-even of x * 255).  Blobs that share a latent shape are decoded as one batch."""
-        from ..utils.image import to_u8
+    def _decompress_blobs(self, blobs, convert):
+        """Blobs -> convert(decompress_batch's (n, 3, H, W) output, [(h, w)]) per group of blobs that share a latent shape, in input order."""
         parsed = [self._unpack_blob(b) for b in blobs]
         by_key = {}
         for i, (_, _, key) in enumerate(parsed):
@@ -617,9 +618,36 @@ class CodecBase(nn.Module):
         out = [None] * len(blobs)
         for idxs in by_key.values():
             x = self.decompress_batch([parsed[i][0] for i in idxs])
-            for i, u8 in zip(idxs, to_u8(x, [parsed[i][1] for i in idxs])):
-                out[i] = u8
+            for i, item in zip(idxs, convert(x, [parsed[i][1] for i in idxs])):
+                out[i] = item
         return out
+
+    # ---- 8-bit YUV 4:2:0 frames in and out (lvae/utils/yuv.py, csrc/yuv_io.hip): an image codec run as an intra-frame coder
+    @torch.no_grad()
+    def compress_yuv420(self, frames, lmb=None, matrix='bt709', range='limited', chroma='bilinear'):
+        """A list of utils.yuv.Yuv420Frame (I420 or NV12 planes on the CPU or the model's device) whose sizes PADDED to multiples of
+        max_stride agree -> list of bytes, element i being the model's own container: exactly the file compress_file would write for the
+        RGB image utils.yuv.to_rgb01 gives for frame i.  lmb: as in compress_images.  The planes go to the device as they are (1.5 bytes
+        per pixel); chroma upsampling ('nearest' | 'bilinear', centre siting), the matrix ('bt601' | 'bt709'), the range ('limited' |
+        'full') and the padding happen where each pipeline group's plan reads its input.  The colour parameters are NOT stored in the
+        stream -- the containers do not change -- so decompress_yuv420 has to be given the same matrix and range."""
+        from ..utils.yuv import Yuv420Batch
+        return self._compress_byte_batch(Yuv420Batch(frames, self.max_stride, self._dummy.device, matrix, range, chroma), lmb, 'compress_yuv420')
+
+    @torch.no_grad()
+    def decompress_yuv420(self, blobs, fmt='i420', matrix='bt709', range='limited'):
+        """compress_yuv420 (or compress_images / compress_file) bytes -> list of utils.yuv.Yuv420Frame of layout `fmt` on the model's device,
+        each cropped to the size in its header (which must be even) and converted on the device (utils.yuv.from_rgb01: forward matrix,
+        2x2 chroma mean, round-half-even).  matrix / range: the stream does not record them; pass what the encoder was given."""
+        from ..utils.yuv import from_rgb01
+        return self._decompress_blobs(blobs, lambda x, sizes: from_rgb01(x, sizes, fmt=fmt, matrix=matrix, range=range))
+
+    @torch.no_grad()
+    def decompress_images(self, blobs):
+        """compress_images / compress_file bytes -> list of (h, w, 3) uint8 tensors on the model's device, each cropped to the size in
+        its header and rounded on the device (round-half-even of x * 255).  Blobs that share a latent shape are decoded as one batch."""
+        from ..utils.image import to_u8
+        return self._decompress_blobs(blobs, to_u8)
 
     @torch.no_grad()
     def decompress_to_files(self, bits_paths, image_paths):

@@ -1,0 +1,312 @@
+"""8-bit YUV 4:2:0 frames in and out of the codec: planar I420 / semi-planar NV12 bytes <-> the fp32 NCHW RGB tensors in [0, 1] the
+models code, and raw .yuv files.
+
+This file DEFINES the two conversions, as torch expressions on CPU tensors (`yuv_to_rgb_expr`, `rgb_to_yuv_expr`): fp32 throughout, the
+constants below as fp32 values, every operation rounded on its own, divisions IEEE.  On the GPU the conversions are the HIP kernels of
+csrc/yuv_io.hip (`lvae_image_yuv420_to_f32`, `lvae_image_f32_to_yuv420`), which reproduce the expressions' bits: a frame is uploaded as
+the 1.5 bytes per pixel its file held, upsampled, converted and replicate-padded where the encoder reads it, and a reconstruction becomes
+bytes on the device before it is copied back.  The same split as utils.image.to_float01 / to_u8.
+
+Conventions: ITU-R BT.601 / BT.709 matrices (Kr, Kb = 0.299, 0.114 / 0.2126, 0.0722), limited (Y 16..235, C 16..240) or full (0..255)
+range, chroma sited in the CENTRE of its 2x2 luma block (JPEG / MPEG-1).  Co-sited chroma (MPEG-2 'left'), 4:2:2 / 4:4:4 and more than
+8 bits are not supported.  The colour parameters are the caller's on both sides: no stream or container stores them.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .image import _canvas
+
+from .._native import YUV_CHROMA as CHROMA, YUV_FORMATS as FORMATS, YUV_MATRICES as MATRICES, YUV_RANGES as RANGES   # index = LVAE_YUV_* code
+# per matrix: Kr, Kg, Kb, a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg -- the literals of csrc/yuv_io.hip
+COEF = {'bt601': (0.299, 0.587, 0.114, 1.402, 1.772, 0.344136286, 0.714136286),
+        'bt709': (0.2126, 0.7152, 0.0722, 1.5748, 1.8556, 0.187324273, 0.468124273)}
+SCALES = {'limited': (16.0, 219.0, 224.0), 'full': (0.0, 255.0, 255.0)}       # luma offset, luma scale, chroma scale
+
+
+def _check(matrix, range, chroma='bilinear', fmt='i420'):
+    for v, known, what in ((matrix, MATRICES, 'matrix'), (range, RANGES, 'range'), (chroma, CHROMA, 'chroma'), (fmt, FORMATS, 'fmt')):
+        if v not in known:
+            raise ValueError(f'{what} is one of {known}, got {v!r}')
+
+
+class Yuv420Frame:
+    """One 8-bit 4:2:0 frame: `fmt` 'i420' with planes y (h, w), u, v (h/2, w/2), or 'nv12' with y (h, w) and uv (h/2, w/2, 2) -- uint8
+    tensors on one device (numpy arrays become CPU tensors).  `u` / `v` of an NV12 frame are strided views of `uv`.  h and w are even."""
+
+    def __init__(self, fmt, y, u=None, v=None, uv=None):
+        if fmt not in FORMATS:
+            raise ValueError(f'fmt is one of {FORMATS}, got {fmt!r}')
+        t = lambda a: None if a is None else (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a)))
+        y, u, v, uv = t(y), t(u), t(v), t(uv)
+        if y is None or y.dim() != 2 or y.dtype != torch.uint8:
+            raise ValueError('y is an (h, w) uint8 plane')
+        h, w = int(y.shape[0]), int(y.shape[1])
+        if h <= 0 or w <= 0 or h % 2 or w % 2:
+            raise ValueError(f'a 4:2:0 frame has even, positive sides, got {h} x {w}')
+        if fmt == 'i420':
+            if uv is not None or any(p is None or p.dtype != torch.uint8 or tuple(p.shape) != (h // 2, w // 2) or p.device != y.device for p in (u, v)):
+                raise ValueError(f'i420: u and v are ({h // 2}, {w // 2}) uint8 planes on the device of y')
+        else:
+            if u is not None or v is not None or uv is None or uv.dtype != torch.uint8 or tuple(uv.shape) != (h // 2, w // 2, 2) or uv.device != y.device:
+                raise ValueError(f'nv12: uv is an ({h // 2}, {w // 2}, 2) uint8 plane on the device of y')
+            u, v = uv[..., 0], uv[..., 1]
+        self.fmt, self.y, self.u, self.v, self.uv, self.h, self.w = fmt, y, u, v, uv, h, w
+
+    @property
+    def device(self):
+        return self.y.device
+
+    @property
+    def size(self):
+        return (self.h, self.w)
+
+    def planes(self):
+        """The planes as the file holds them: (y, u, v) or (y, uv)."""
+        return (self.y, self.u, self.v) if self.fmt == 'i420' else (self.y, self.uv)
+
+    def to(self, device, non_blocking=False):
+        if torch.device(device) == self.device:
+            return self
+        mv = lambda p: p.to(device, non_blocking=non_blocking)
+        return Yuv420Frame('i420', mv(self.y), mv(self.u), mv(self.v)) if self.fmt == 'i420' else Yuv420Frame('nv12', mv(self.y), uv=mv(self.uv))
+
+    def cpu(self):
+        return self.to('cpu')
+
+    def as_format(self, fmt):
+        """The same samples in the other plane layout (a copy of the chroma) or, for its own format, the frame itself."""
+        if fmt == self.fmt:
+            return self
+        if fmt == 'nv12':
+            return Yuv420Frame('nv12', self.y, uv=torch.stack([self.u, self.v], -1))
+        return Yuv420Frame('i420', self.y, self.u.contiguous(), self.v.contiguous())
+
+
+def frame_bytes(width, height):
+    return width * height * 3 // 2
+
+
+def read_yuv420(path, width, height, fmt='i420', frames=None):
+    """A raw .yuv file of `width` x `height` 8-bit 4:2:0 frames -> list of Yuv420Frame on the CPU (all of them, or the first `frames`).
+    The file is read into ONE buffer -- pinned when a GPU is there, so a frame's upload is an asynchronous copy -- and the planes are
+    views of it.  ValueError: odd or non-positive sides, a file size that is not a whole number of frames, an unknown fmt."""
+    _check('bt709', 'limited', fmt=fmt)
+    if width <= 0 or height <= 0 or width % 2 or height % 2:
+        raise ValueError(f'read_yuv420: a 4:2:0 frame has even, positive sides, got {width} x {height}')
+    per = frame_bytes(width, height)
+    size = os.path.getsize(path)
+    if size == 0 or size % per:
+        raise ValueError(f'read_yuv420: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
+    n = size // per if frames is None else min(int(frames), size // per)
+    if n <= 0:
+        raise ValueError(f'read_yuv420: frames={frames}')
+    buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    with open(path, 'rb') as f:
+        got = f.readinto(buf.numpy())
+    if got != n * per:
+        raise ValueError(f'read_yuv420: short read of {path}')
+    out, ny, nc = [], width * height, (width // 2) * (height // 2)
+    for i in range(n):
+        fr = buf[i * per:(i + 1) * per]
+        y = fr[:ny].view(height, width)
+        if fmt == 'i420':
+            out.append(Yuv420Frame('i420', y, fr[ny:ny + nc].view(height // 2, width // 2), fr[ny + nc:].view(height // 2, width // 2)))
+        else:
+            out.append(Yuv420Frame('nv12', y, uv=fr[ny:].view(height // 2, width // 2, 2)))
+    return out
+
+
+def write_yuv420(frames, path, append=False):
+    """Write frames (any device) to a raw .yuv file, each in its own plane layout, one after the other."""
+    with open(path, 'ab' if append else 'wb') as f:
+        for fr in frames:
+            for p in fr.planes():
+                f.write(p.cpu().contiguous().numpy().tobytes())
+
+
+# ----------------------------------------------------------------------------------------------- the defining expressions (CPU, fp32)
+def _f32(v):
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def _upsample(c, chroma):
+    """(ch, cw) uint8 chroma -> (2 ch, 2 cw) fp32 at the luma positions, centre siting.  'bilinear': per axis 3/4 of the sample a pixel
+    lies in and 1/4 of the neighbour on the pixel's side, indices clamped at the plane's edges; sixteenths of bytes: exact in fp32."""
+    c = c.to(torch.float32)
+    if chroma == 'nearest':
+        return c.repeat_interleave(2, 0).repeat_interleave(2, 1)
+    for dim in (0, 1):
+        n = c.shape[dim]
+        i = torch.arange(n)
+        prev, nxt = c.index_select(dim, (i - 1).clamp(min=0)), c.index_select(dim, (i + 1).clamp(max=n - 1))
+        even, odd = c * 0.75 + prev * 0.25, c * 0.75 + nxt * 0.25
+        c = torch.stack([even, odd], dim + 1).flatten(dim, dim + 1)
+    return c
+
+
+def yuv_to_rgb_expr(y, u, v, matrix='bt709', range='limited', chroma='bilinear'):
+    """THE DEFINITION of lvae_image_yuv420_to_f32 inside a frame's extent: uint8 planes y (h, w), u, v (h/2, w/2) on the CPU -> (3, h, w)
+    fp32 RGB in [0, 1]."""
+    _check(matrix, range, chroma)
+    _, _, _, a, b, d, e = (_f32(k) for k in COEF[matrix])
+    yo, ys, cs = (_f32(k) for k in SCALES[range])
+    yn = (y.to(torch.float32) - yo) / ys
+    cb = (_upsample(u, chroma) - _f32(128.0)) / cs
+    cr = (_upsample(v, chroma) - _f32(128.0)) / cs
+    r = yn + a * cr
+    bl = yn + b * cb
+    g = (yn - d * cb) - e * cr
+    return torch.stack([r, g, bl]).clamp(0, 1)
+
+
+def rgb_to_yuv_expr(x, matrix='bt709', range='limited'):
+    """THE DEFINITION of lvae_image_f32_to_yuv420: (3, h, w) fp32 RGB on the CPU, h and w even -> uint8 planes y (h, w), u, v (h/2, w/2).
+    Values are clamped to [0, 1] first and a NaN counts as 0."""
+    _check(matrix, range)
+    kr, kg, kb, a, b, _, _ = (_f32(k) for k in COEF[matrix])
+    yo, ys, cs = (_f32(k) for k in SCALES[range])
+    x = x.to(torch.float32)
+    x = torch.where(x > 0, x, torch.zeros((), dtype=torch.float32))
+    x = torch.where(x < 1, x, torch.ones((), dtype=torch.float32))
+    r, g, bl = x[0], x[1], x[2]
+    yn = (kr * r + kg * g) + kb * bl
+    cb, cr = (bl - yn) / b, (r - yn) / a
+    mean4 = lambda c: ((c[0::2, 0::2] + c[0::2, 1::2]) + (c[1::2, 0::2] + c[1::2, 1::2])) * 0.25
+    byte = lambda t: torch.round(t).clamp(0, 255).to(torch.uint8)
+    return byte(yn * ys + yo), byte(mean4(cb) * cs + _f32(128.0)), byte(mean4(cr) * cs + _f32(128.0))
+
+
+# ----------------------------------------------------------------------------------------------- batches and the kernel path
+def _as_frame(f):
+    if not isinstance(f, Yuv420Frame):
+        raise ValueError(f'expected a Yuv420Frame, got {type(f).__name__}')
+    return f
+
+
+def _plane_args(frames):
+    """Host arrays of plane addresses / row strides of device frames of ONE format, as the native entries take them; the second item
+    keeps alive what had to be made contiguous."""
+    fmt = frames[0].fmt
+    if any(f.fmt != fmt for f in frames):
+        raise ValueError('the frames of one call share a plane layout (use Yuv420Frame.as_format)')
+    n, keep = len(frames), []
+
+    def rows_ok(p, unit):
+        return p.stride(-1) == 1 and (p.dim() == 2 or p.stride(1) == 2) and p.stride(0) >= unit
+    ys = [f.y if rows_ok(f.y, f.w) else f.y.contiguous() for f in frames]
+    if fmt == 'i420':
+        us = [f.u if rows_ok(f.u, f.w // 2) else f.u.contiguous() for f in frames]
+        vs = [f.v if rows_ok(f.v, f.w // 2) else f.v.contiguous() for f in frames]
+    else:
+        us = [f.uv if rows_ok(f.uv, f.w) else f.uv.contiguous() for f in frames]
+        vs = None
+    keep = [ys, us, vs]
+    ptr = lambda ps: (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
+    row = lambda ps: (ctypes.c_long * n)(*[p.stride(0) for p in ps])
+    hw = (ctypes.c_int * (2 * n))(*[v for f in frames for v in f.size])
+    args = (ptr(ys), ptr(us), ptr(vs) if vs else None, row(ys), row(us), row(vs) if vs else None, hw)
+    return fmt, args, keep
+
+
+class Yuv420Batch:
+    """B 4:2:0 frames on one device that share a canvas (H, W) >= their own sizes, with the colour parameters of their conversion: the
+    utils.image.U8Batch counterpart that CodecBase.compress_yuv420 hands to compress_batch as `u8=`.  `shape` is the fp32 tensor's;
+    `fill(dst, start, n)` converts frames start .. start + n straight into `dst` -- an (n, 3, H, W) fp32 view of an encode plan's input --
+    with one launch on the current stream."""
+
+    def __init__(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear'):
+        _check(matrix, range, chroma)
+        fs = [_as_frame(f) for f in frames]
+        if not fs:
+            raise ValueError('no frames')
+        self.sizes = [f.size for f in fs]
+        H, W = _canvas(self.sizes, div)
+        self.shape = (len(fs), 3, H, W)
+        self.device = torch.device(device)
+        self.matrix, self.range, self.chroma = matrix, range, chroma
+        self.frames = [f.to(self.device, non_blocking=True) for f in fs]      # 1.5 bytes per pixel cross the bus, unpadded
+
+    def fill(self, dst, start=0, n=None):
+        from .. import _native
+        n = len(self.frames) - start if n is None else n
+        _, _, H, W = self.shape
+        assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
+        fmt, args, keep = _plane_args(self.frames[start:start + n])
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _native.check(_native.lib().lvae_image_yuv420_to_f32(
+                *args, n, FORMATS.index(fmt), MATRICES.index(self.matrix), RANGES.index(self.range), CHROMA.index(self.chroma),
+                dst.data_ptr(), dst.stride(0) if n > 1 else 3 * H * W, H, W, st), 'image_yuv420_to_f32')
+        del keep
+
+
+def to_rgb01(frames, div=1, device=None, matrix='bt709', range='limited', chroma='bilinear'):
+    """A list of Yuv420Frame -> ((B, 3, H, W) fp32 RGB in [0, 1], [(h, w)]): chroma upsampled ('nearest' | 'bilinear', centre siting),
+    the inverse matrix applied, clamped, every frame replicate-padded on the right / bottom to the common canvas, the smallest (H, W) of
+    multiples of `div` that holds them all.  CPU frames with device=None: the defining expression on the host.  Otherwise: one upload
+    of each frame's bytes (none for device frames) and one kernel launch for the batch, on `device` (default: the frames' device)."""
+    fs = [_as_frame(f) for f in frames]
+    if not fs:
+        raise ValueError('no frames')
+    if device is None and all(f.device.type == 'cpu' for f in fs):
+        _check(matrix, range, chroma)
+        sizes = [f.size for f in fs]
+        H, W = _canvas(sizes, div)
+        out = []
+        for f in fs:
+            x = yuv_to_rgb_expr(f.y, f.u, f.v, matrix, range, chroma)
+            out.append(F.pad(x.unsqueeze(0), (0, W - f.w, 0, H - f.h), mode='replicate')[0] if f.size != (H, W) else x)
+        return torch.stack(out), sizes
+    if device is None:
+        device = next(f.device for f in fs if f.device.type != 'cpu')
+    batch = Yuv420Batch(fs, div, device, matrix, range, chroma)
+    out = torch.empty(batch.shape, dtype=torch.float32, device=batch.device)
+    batch.fill(out)
+    return out, batch.sizes
+
+
+def from_rgb01(x, sizes=None, fmt='i420', matrix='bt709', range='limited'):
+    """The inverse: fp32 RGB images in [0, 1] -> a list of Yuv420Frame of layout `fmt` on the same device.  Values are clamped to [0, 1]
+    (NaN -> 0), the forward matrix is applied per pixel, a chroma sample is the mean of its 2x2 block, bytes are rounded with ties to
+    even.  x: a (B, 3, H, W) tensor or a list of (1, 3, h, w) / (3, h, w) tensors (crops of a decoder's padded batch are read in place);
+    sizes: per-image valid extents [(h, w)] (default: every item whole); odd extents raise ValueError.  Device tensors: one kernel launch
+    for the batch on the current stream; CPU tensors: the defining expression."""
+    from .views import items, strided_batch
+    _check(matrix, range, fmt=fmt)
+    xs = items(x, 'x')
+    if sizes is not None:
+        if len(sizes) != len(xs):
+            raise ValueError(f'from_rgb01: {len(sizes)} sizes for {len(xs)} images')
+        xs = [v[:, :h, :w] for v, (h, w) in zip(xs, sizes)]
+    if not xs or any(v.shape[0] != 3 or v.shape[1] == 0 or v.shape[2] == 0 for v in xs):
+        raise ValueError('from_rgb01: expected 3-channel, non-empty images')
+    if any(v.shape[1] % 2 or v.shape[2] % 2 for v in xs):
+        raise ValueError(f'from_rgb01: a 4:2:0 frame has even sides, got {[tuple(v.shape[1:]) for v in xs]}')
+    device = xs[0].device
+    if device.type == 'cpu':
+        return [Yuv420Frame('i420', *rgb_to_yuv_expr(v, matrix, range)).as_format(fmt) for v in xs]
+    from .. import _native
+    B = len(xs)
+    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
+    hmax, wmax = max(h for h, _ in hw), max(w for _, w in hw)
+    with torch.cuda.device(device):
+        keep, px, (s_img, s_plane, s_row) = strided_batch(xs, hmax, wmax, device)
+        span = (hmax - 1) * s_row + wmax             # views whose common strides do not hold the largest extent are packed instead
+        if s_row < wmax or s_plane < span or (B > 1 and s_img < 2 * s_plane + span):
+            keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in xs], hmax, wmax, device)
+        new = lambda *s: torch.empty(*s, dtype=torch.uint8, device=device)
+        if fmt == 'i420':
+            outs = [Yuv420Frame('i420', new(h, w), new(h // 2, w // 2), new(h // 2, w // 2)) for h, w in hw]
+        else:
+            outs = [Yuv420Frame('nv12', new(h, w), uv=new(h // 2, w // 2, 2)) for h, w in hw]
+        _, args, _ = _plane_args(outs)
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _native.check(_native.lib().lvae_image_f32_to_yuv420(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[6], B,
+                                                             FORMATS.index(fmt), MATRICES.index(matrix), RANGES.index(range), *args[:6], st),
+                      'image_f32_to_yuv420')
+    del keep
+    return outs

@@ -7,11 +7,16 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py encode --synthetic 3 IMAGES/ BITS/ -m qres34m     # seeded weights; writes N seeded PNGs to IMAGES/ first
     python scripts/lvae-codec.py encode IMAGES/ BITS/ --tile 512 768 --overlap 32   # large images: one tiled container per image
     python scripts/lvae-codec.py region BITS/ CROPS/ --box 100 200 512 512          # y0 x0 h w of every tiled file, nothing else decoded
+    python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 1920 1080 [--format nv12] [--frames N]   # raw 8-bit 4:2:0: one .bits per frame
+    python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv [--format nv12]
 
 Images whose sizes padded to the model's stride agree are coded as batches of up to --batch (lvae.evaluation.batch_same_size).  A .bits
 file is what compress_file writes; decode names every PNG after its .bits file.  --synthetic (on decode: seeded weights only) needs no
 checkpoint on disk.  With --tile every image is coded on its own as a tiled container (CodecBase.compress_tiled: tiles of one shape, coded
---batch at a time, whatever the image's size); decode recognises such files by their magic, region decodes only the tiles a box touches."""
+--batch at a time, whatever the image's size); decode recognises such files by their magic, region decodes only the tiles a box touches.
+encode-yuv / decode-yuv code the frames of a raw .yuv file as an intra-frame coder (CodecBase.compress_yuv420 / decompress_yuv420): frame
+k becomes BITS/frame<k>.bits, a file compress_file could have written; --matrix / --range / --chroma are NOT stored, give decode-yuv the
+same --matrix and --range.  With --synthetic N, encode-yuv first writes N seeded frames of --size to IN.yuv."""
 import argparse
 import os
 import sys
@@ -74,10 +79,40 @@ def decode(model, src, dst, batch, box=None):
     print(f'decoded {len(paths) + len(tiled)} files')
 
 
+def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour):
+    from lvae.utils.yuv import read_yuv420
+    fs = read_yuv420(src, size[0], size[1], fmt, frames=frames)
+    total = 0
+    for o in range(0, len(fs), batch):
+        blobs = model.compress_yuv420(fs[o:o + batch], **colour, **({'lmb': lmb} if lmb is not None else {}))
+        for k, blob in enumerate(blobs, o):
+            (Path(dst) / f'frame{k:05d}.bits').write_bytes(blob)
+            total += len(blob)
+    print(f'encoded {len(fs)} frames -> {total} bytes')
+
+
+def decode_yuv(model, src, dst, fmt, batch, colour):
+    from lvae.utils.yuv import write_yuv420
+    paths = sorted(Path(src).glob('*.bits'))
+    for o in range(0, len(paths), batch):
+        frames = model.decompress_yuv420([p.read_bytes() for p in paths[o:o + batch]], fmt=fmt, matrix=colour['matrix'], range=colour['range'])
+        write_yuv420(frames, dst, append=o > 0)
+    print(f'decoded {len(paths)} frames')
+
+
+def synthetic_yuv(path, n, size, fmt, colour):
+    """N seeded frames of size (w, h) as a raw .yuv file: seeded RGB images through the defining host conversion."""
+    import seeded_init
+    from lvae.utils.yuv import from_rgb01, write_yuv420
+    w, h = size
+    rgb = [torch.from_numpy(seeded_init.synthetic_image_u8(h, w, 300 + i)).permute(2, 0, 1).float().div(255) for i in range(n)]
+    write_yuv420(from_rgb01(rgb, fmt=fmt, matrix=colour['matrix'], range=colour['range']), path)
+
+
 @torch.no_grad()
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('command', choices=['encode', 'decode', 'region'])
+    ap.add_argument('command', choices=['encode', 'decode', 'region', 'encode-yuv', 'decode-yuv'])
     ap.add_argument('src')
     ap.add_argument('dst')
     ap.add_argument('-m', '--model', type=str, default='qarv_base')
@@ -88,7 +123,27 @@ def main():
     ap.add_argument('--overlap', type=int, default=0, help='encode with --tile: pixels neighbouring tiles share')
     ap.add_argument('--box', type=int, nargs=4, default=None, metavar=('Y0', 'X0', 'H', 'W'), help='region: the window to decode')
     ap.add_argument('--synthetic', type=int, default=0, help='seeded weights; on encode also write N seeded 120x180 / 128x192 PNGs to SRC')
+    ap.add_argument('--size', type=int, nargs=2, default=None, metavar=('W', 'H'), help='encode-yuv: the frame size of the raw file')
+    ap.add_argument('--format', type=str, default='i420', choices=['i420', 'nv12'], help='encode-yuv / decode-yuv: the plane layout of the raw file')
+    ap.add_argument('--frames', type=int, default=None, help='encode-yuv: code only the first N frames')
+    ap.add_argument('--matrix', type=str, default='bt709', choices=['bt601', 'bt709'])
+    ap.add_argument('--range', type=str, default='limited', choices=['limited', 'full'])
+    ap.add_argument('--chroma', type=str, default='bilinear', choices=['nearest', 'bilinear'], help='encode-yuv: the chroma upsampling filter')
     args = ap.parse_args()
+    if args.command in ('encode-yuv', 'decode-yuv'):
+        colour = dict(matrix=args.matrix, range=args.range, chroma=args.chroma)
+        if args.command == 'encode-yuv':
+            if args.size is None:
+                ap.error('encode-yuv needs --size W H')
+            os.makedirs(args.dst, exist_ok=True)
+            if args.synthetic:
+                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour)
+            model = load_model(args.model, args.synthetic, torch.device(args.device))
+            encode_yuv(model, args.src, args.dst, args.size, args.format, args.frames, args.lmb, args.batch, colour)
+        else:
+            model = load_model(args.model, args.synthetic, torch.device(args.device))
+            decode_yuv(model, args.src, args.dst, args.format, args.batch, colour)
+        return
     os.makedirs(args.dst, exist_ok=True)
     if args.synthetic and args.command == 'encode':
         import seeded_init

@@ -1,0 +1,151 @@
+"""How a YUV 4:2:0 frame gets into and out of the codec: the host path (numpy: upsample the chroma, apply the matrix, build the fp32
+(B, 3, H, W) tensor at 12 bytes per pixel, upload it) against the byte path (upload 1.5 bytes per pixel, lvae_image_yuv420_to_f32 /
+lvae_image_f32_to_yuv420 on the device), and one evaluation step (lvae.evaluation.yuv_evaluate) against the same step with the
+conversions and the squared errors on the host.  Workloads: 8 frames of 512 x 768 and 2 of 1080 x 1920 (which pad to 1088 x 1920); seeded
+synthetic frames, BT.709 limited range, bilinear chroma.
+  (a) host_in  : numpy fp32 conversion + edge padding to multiples of 64, torch.from_numpy(...).to(device)
+  (b) yuv_in   : to_rgb01(frames, div=64, device)             -- frames as read_yuv420 leaves them (views of one pinned buffer)
+  (c) host_out : x.cpu(), then the numpy fp32 forward conversion to I420 bytes
+      yuv_out  : from_rgb01(x) + one device-to-host copy per plane
+  (d) eval_step     : yuv_evaluate(model, file, ...) with qarv_base (bench.py's seeded model)
+      eval_step_host: the same frames through host_in -> compress_batch -> decompress_batch -> host_out, numpy int64 squared errors
+The variants of a group alternate step by step in one process, the device synchronised after every call; medians, min, max in ms.  The
+numpy conversions follow the same formulas as lvae/utils/yuv.py but are not bit-identical to it (numpy may contract nothing either, yet
+its chroma filter is written in floats); the outputs are compared within 1e-6 / one byte.  One JSON line.
+    python tools/yuv_io_bench.py [--steps 20] [--warmup 3] [--skip-eval] [--tag NAME]"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, 'lossy-vae_amd'))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+WORKLOADS = {'b8_512x768': (8, 512, 768), 'b2_1080x1920': (2, 1080, 1920)}
+KR, KB = 0.2126, 0.0722
+KG = 1 - KR - KB
+F = np.float32
+
+
+def _up(c):
+    """(ch, cw) bytes -> (2 ch, 2 cw) fp32, the 3/4 - 1/4 filter with clamped edges."""
+    c = c.astype(F)
+    for ax in (0, 1):
+        prev = np.concatenate([c.take([0], ax), c.take(range(c.shape[ax] - 1), ax)], ax)
+        nxt = np.concatenate([c.take(range(1, c.shape[ax]), ax), c.take([-1], ax)], ax)
+        even, odd = F(0.75) * c + F(0.25) * prev, F(0.75) * c + F(0.25) * nxt
+        c = np.stack([even, odd], ax + 1).reshape([s * (2 if i == ax else 1) for i, s in enumerate(c.shape)])
+    return c
+
+
+def host_to_rgb(frames, div):
+    """What a user without the kernels writes: numpy, fp32, BT.709 limited range, edge padding to multiples of `div`."""
+    out = []
+    for f in frames:
+        y, u, v = f.y.numpy(), f.u.numpy(), f.v.numpy()
+        yn = (y.astype(F) - F(16)) / F(219)
+        cb, cr = (_up(u) - F(128)) / F(224), (_up(v) - F(128)) / F(224)
+        rgb = np.stack([yn + F(2 * (1 - KR)) * cr, yn - F(2 * KB * (1 - KB) / KG) * cb - F(2 * KR * (1 - KR) / KG) * cr, yn + F(2 * (1 - KB)) * cb])
+        np.clip(rgb, 0, 1, out=rgb)
+        h, w = y.shape
+        out.append(np.pad(rgb, ((0, 0), (0, -h % div), (0, -w % div)), mode='edge'))
+    return torch.from_numpy(np.stack(out))
+
+
+def host_to_yuv(x, sizes):
+    """(B, 3, H, W) fp32 CPU tensor -> [(y, u, v)] uint8 arrays, BT.709 limited range."""
+    out = []
+    for xi, (h, w) in zip(x.numpy(), sizes):
+        r, g, b = np.clip(np.nan_to_num(xi[:, :h, :w]), 0, 1)
+        yn = F(KR) * r + F(KG) * g + F(KB) * b
+        cb, cr = (b - yn) / F(2 * (1 - KB)), (r - yn) / F(2 * (1 - KR))
+        m4 = lambda c: (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2]) * F(0.25)
+        q = lambda t: np.clip(np.rint(t), 0, 255).astype(np.uint8)
+        out.append((q(yn * F(219) + F(16)), q(m4(cb) * F(224) + F(128)), q(m4(cr) * F(224) + F(128))))
+    return out
+
+
+def main():
+    import bench
+    import seeded_init
+    from lvae.evaluation import yuv_evaluate
+    from lvae.utils.yuv import from_rgb01, read_yuv420, to_rgb01, write_yuv420
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--skip-eval', action='store_true')
+    ap.add_argument('--tag', type=str, default='')
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+
+    def once(fn):
+        t0 = time.perf_counter()
+        fn(); torch.cuda.synchronize(dev)
+        return time.perf_counter() - t0
+
+    def alternate(fns):
+        for _ in range(args.warmup):
+            for fn in fns.values():
+                once(fn)
+        ts = {k: [] for k in fns}
+        for _ in range(args.steps):
+            for k, fn in fns.items():
+                ts[k].append(once(fn))
+        return {k: dict(zip(('median', 'min', 'max'), (round(float(np.median(v)) * 1e3, 4), round(min(v) * 1e3, 4), round(max(v) * 1e3, 4))))
+                for k, v in ts.items()}
+
+    res = {'metric': 'yuv_io_ms', 'tag': args.tag, 'device': torch.cuda.get_device_name(0), 'steps': args.steps, 'warmup': args.warmup}
+    model = None if args.skip_eval else bench.build_model(dev)[0]
+    tmp = Path(tempfile.mkdtemp())
+    for name, (B, H, W) in WORKLOADS.items():
+        path = tmp / f'{name}.yuv'
+        rgb = [torch.from_numpy(seeded_init.synthetic_image_u8(H, W, seed=1000 + i)).permute(2, 0, 1).float().div(255) for i in range(B)]
+        write_yuv420(from_rgb01(rgb), path)
+        frames = read_yuv420(path, W, H)
+        sizes = [(H, W)] * B
+        box, row = {}, {}
+
+        def host_in():
+            box['a'] = host_to_rgb(frames, 64).to(dev)
+
+        def yuv_in():
+            box['b'] = to_rgb01(frames, div=64, device=dev)[0]
+        row.update(alternate({'host_in': host_in, 'yuv_in': yuv_in}))
+        row['in_max_abs_diff'] = float((box['a'] - box['b']).abs().max())
+        assert row['in_max_abs_diff'] <= 1e-6
+        row['host_in_over_yuv_in'] = round(row['host_in']['median'] / row['yuv_in']['median'], 2)
+        x = box['b']
+
+        def host_out():
+            box['c'] = host_to_yuv(x.cpu(), sizes)
+
+        def yuv_out():
+            box['d'] = [[p.cpu() for p in f.planes()] for f in from_rgb01(x, sizes)]
+        row.update(alternate({'host_out': host_out, 'yuv_out': yuv_out}))
+        row['out_max_byte_diff'] = max(int(np.abs(c.astype(np.int64) - d.numpy().astype(np.int64)).max()) for cs, ds in zip(box['c'], box['d']) for c, d in zip(cs, ds))
+        assert row['out_max_byte_diff'] <= 1
+        row['host_out_over_yuv_out'] = round(row['host_out']['median'] / row['yuv_out']['median'], 2)
+        if model is not None:
+            def eval_step():
+                box['e'] = yuv_evaluate(model, path, W, H, batch=B)
+
+            def eval_step_host():
+                fs = read_yuv420(path, W, H)
+                bodies = model.compress_batch(host_to_rgb(fs, 64).to(dev))
+                rec = host_to_yuv(model.decompress_batch(bodies).cpu(), sizes)
+                sse = [[int(((a.astype(np.int64) - b.numpy().astype(np.int64)) ** 2).sum()) for a, b in zip(r, (f.y, f.u, f.v))] for r, f in zip(rec, fs)]
+                box['f'] = (sse, [len(b) for b in bodies])
+            row.update(alternate({'eval_step': eval_step, 'eval_step_host': eval_step_host}))
+            row['eval_step_host_over_eval_step'] = round(row['eval_step_host']['median'] / row['eval_step']['median'], 2)
+        res[name] = row
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
