@@ -572,6 +572,46 @@ int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uint8_t* const
                 uint64_t* out, void* stream);
 /* The three entries above were added without a change to lvae_abi_version() (no existing signature changed). */
 
+/* ---- Planar YUV frames of 8, 10 or 12 bits at 4:2:0 / 4:2:2 / 4:4:4 (csrc/yuv_hbd_io.hip): the generalisation of the three entries above,
+ * which keep their behaviour; the conventions (HOST arrays of DEVICE plane addresses, hw, 16 frames per launch, fp32 side, alignment) are
+ * theirs.  depth: 8, 10 or 12.  A sample is a byte at depth 8 and otherwise a 16-bit word with the value in its LOW bits (yuv420p10le,
+ * yuv422p12le ...; P010-style layouts with the value in the high bits are not supported); every sample read is masked to `depth` bits.
+ * Row strides are in SAMPLES.  subsampling: LVAE_YUV_SUB_420: chroma planes of (h/2, w/2), h and w even; LVAE_YUV_SUB_422: (h, w/2), w even;
+ * LVAE_YUV_SUB_444: (h, w), any extent.  Planar only: u[b] and v[b] are separate planes.  siting: LVAE_YUV_SITING_CENTER: a chroma sample
+ * lies in the middle of the luma samples it covers (JPEG / MPEG-1); LVAE_YUV_SITING_LEFT: horizontally it lies ON the even luma column and
+ * vertically it stays centred (H.264 / HEVC chroma_sample_loc_type 0); siting has no effect on an axis that is not subsampled.
+ * matrix: LVAE_YUV_BT601 / LVAE_YUV_BT709 / LVAE_YUV_BT2020 (non-constant luminance, Kr, Kb = 0.2627, 0.0593; these entries only).
+ * range, with s = 2^(depth - 8): LVAE_YUV_LIMITED: Y = 16 s + 219 s y', C = 128 s + 224 s c; LVAE_YUV_FULL: Y = (2^depth - 1) y',
+ * C = 128 s + (2^depth - 1) c.  The colour parameters, depth and siting are the caller's: no stream or container records them.
+ * -22 before any HIP call: a null pointer (an entry of a plane array included), B <= 0, H or W <= 0, an extent that is 0, odd on a subsampled
+ * axis or beyond (H, W), a row stride below its plane's width, fp32 strides that do not hold (H, W), a depth other than 8, 10, 12, an
+ * unknown subsampling / siting / matrix / range / chroma.
+ *
+ * lvae_image_yuv_to_f32: as lvae_image_yuv420_to_f32 (the whole canvas, replicate padding).  Chroma at luma pixel (y, x), per SUBSAMPLED
+ * axis: LVAE_YUV_NEAREST: sample x/2; LVAE_YUV_BILINEAR, centre: 3/4 of sample x/2 and 1/4 of its neighbour on the pixel's side, clamped to
+ * the plane; left (horizontal axis only): column 2k takes sample k, column 2k + 1 takes (c[k] + c[min(k + 1, cw - 1)]) / 2 -- exact on
+ * integers.  Then, every operation rounded to fp32 on its own: y' = (Y - yoff) / yscale, c = (C - 128 s) / cscale, and R, G, B as in
+ * lvae_image_yuv420_to_f32; at depth 8, 4:2:0, centre siting the result has the bits of that entry's. */
+enum { LVAE_YUV_SUB_420 = 0, LVAE_YUV_SUB_422 = 1, LVAE_YUV_SUB_444 = 2 };
+enum { LVAE_YUV_SITING_CENTER = 0, LVAE_YUV_SITING_LEFT = 1 };
+enum { LVAE_YUV_BT2020 = 2 };
+int lvae_image_yuv_to_f32(const void* const* y, const void* const* u, const void* const* v, const long* y_row, const long* u_row,
+                          const long* v_row, const int* hw, int B, int depth, int subsampling, int siting, int matrix, int range, int chroma,
+                          float* dst, long dst_img, int H, int W, void* stream);
+/* lvae_image_f32_to_yuv: the inverse; src addressed as in lvae_image_f32_to_yuv420, y' / cb / cr per pixel as there.  Chroma samples from
+ * the per-pixel fp32 cb / cr, the order of the sums as written: centre 4:2:0 ((a + b) + (c + d)) * 0.25 over the 2x2 block; centre 4:2:2
+ * (a + b) * 0.5; left: per row h[k] = ((c[max(2k - 1, 0)] + c[2k + 1]) + (c[2k] + c[2k])) * 0.25, for 4:2:0 followed by (h_row0 + h_row1) * 0.5;
+ * 4:4:4: the pixel's own.  Codes: rint(y' * yscale + yoff), rint(c * cscale + 128 s), ties to even, clamped to 0 .. 2^depth - 1.  Nothing
+ * outside a plane's extent is written. */
+int lvae_image_f32_to_yuv(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int depth,
+                          int subsampling, int siting, int matrix, int range, void* const* y, void* const* u, void* const* v,
+                          const long* y_row, const long* u_row, const long* v_row, void* stream);
+/* lvae_sse_u16: lvae_sse_u8 for planes of 16-bit words (row strides in samples): exact for ANY 16-bit values -- sums are 64-bit integers
+ * from the lane on, one integer atomic per wave. */
+int lvae_sse_u16(const uint16_t* const* a, const long* a_row, const uint16_t* const* b, const long* b_row, const int* hw, int n,
+                 uint64_t* out, void* stream);
+/* These three were added without a change to lvae_abi_version() either. */
+
 /* ---- Tiled images (csrc/tile_stitch.hip; lvae/utils/tiling.py states the grid rule and the weights): a window of an (h, w) image from
  * the fp32 reconstructions of the tiles that cover it.  The tiles form a rows x cols grid of common extent (th, tw) with origins oy[rows],
  * ox[cols] (HOST arrays; they must be what the grid rule gives for (h, th, overlap) and (w, tw, overlap): origin k * (T - overlap) for

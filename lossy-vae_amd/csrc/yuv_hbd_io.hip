@@ -1,0 +1,454 @@
+// Planar YUV frames of 8, 10 or 12 bits at 4:2:0 / 4:2:2 / 4:4:4, with centre- or left-sited (co-sited) chroma, in and out of the codec on
+// the device, and the exact squared error of 16-bit planes.  include/lvae_hip.h (lvae_image_yuv_to_f32 / lvae_image_f32_to_yuv /
+// lvae_sse_u16) states the contract; lvae/utils/yuv.py states the two conversions as torch expressions (yuv_to_rgb_expr2 /
+// rgb_to_yuv_expr2), and the kernels here reproduce their bits.  As in yuv_io.hip -- whose 8-bit 4:2:0 kernels stay as they are; this file
+// is their generalisation, kept apart so that their code does not change -- floating-point contraction is off for the whole file and
+// divisions are __fdiv_rn (the header of yuv_io.hip says why __fmul_rn / __fadd_rn do not serve).
+//
+// Samples of more than 8 bits are the low bits of 16-bit words (yuv420p10le ...); the kernels mask every sample to `depth` bits.  Row
+// strides are in samples.  Kernels are templates on the sample type, the two subsampling shifts and the siting, so a variant has no
+// branch on any of them.  yuv_to_f32: one lane owns 4 consecutive canvas pixels of one row (one 4- or 8-byte luma load where the address
+// allows, one float4 per RGB plane); the chroma filter runs on integers: per subsampled axis the weights are quarters, so 4 (or 16) times
+// the filtered value is an integer of at most 16 * 4095 and exact in any order.  f32_to_yuv: one lane owns a block of (2 or 1 rows) x 4
+// columns; left siting needs the column before the block, which is one more scalar load per row and plane.  sse_u16: one lane owns 8
+// consecutive samples of one row of both planes; 64-bit integer sums from the lane to the one atomic per wave.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "../../include/lvae_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int HBD_CHUNK = 16;                                // frames (plane pairs) per launch
+constexpr int HBD_WG = 256;
+
+// one frame: planes, row strides in samples, valid extent
+struct PlaneDesc { void *y, *u, *v; long yrow, urow, vrow; int h, w; };
+struct PlaneBatch { PlaneDesc d[HBD_CHUNK]; };
+
+// the fp32 constants of a conversion: the matrix (a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg, the literals of
+// lvae/utils/yuv.py), the range at this depth (all integers, exact) and the sample mask 2^depth - 1 (peak is the same number as a float)
+struct YuvParams { float kr, kg, kb, a, b, d, e, yo, ys, co, cs, peak; unsigned mask; };
+
+YuvParams yuv_params(int matrix, int range, int depth) {
+    YuvParams k = matrix == LVAE_YUV_BT601   ? YuvParams{0.299f, 0.587f, 0.114f, 1.402f, 1.772f, 0.344136286f, 0.714136286f}
+                  : matrix == LVAE_YUV_BT709 ? YuvParams{0.2126f, 0.7152f, 0.0722f, 1.5748f, 1.8556f, 0.187324273f, 0.468124273f}
+                                             : YuvParams{0.2627f, 0.678f, 0.0593f, 1.4746f, 1.8814f, 0.164553127f, 0.571353127f};
+    const float s = (float)(1 << (depth - 8)), peak = (float)((1 << depth) - 1);
+    const bool full = range == LVAE_YUV_FULL;
+    k.yo = full ? 0.0f : 16.0f * s;
+    k.ys = full ? peak : 219.0f * s;
+    k.co = 128.0f * s;
+    k.cs = full ? peak : 224.0f * s;
+    k.peak = peak;
+    k.mask = (1u << depth) - 1u;
+    return k;
+}
+
+__device__ __forceinline__ float clamp01(float x) {          // NaN -> 0: both comparisons are false for a NaN
+    x = x > 0.0f ? x : 0.0f;
+    return x < 1.0f ? x : 1.0f;
+}
+
+// 4 consecutive samples: one 4-byte (8-bit) or 8-byte (16-bit) access where the address allows, scalars where not
+template <typename T>
+__device__ __forceinline__ void load4(const T* __restrict__ p, unsigned mask, unsigned o[4]) {
+    if (((uintptr_t)p & (4 * sizeof(T) - 1)) == 0) {
+        if constexpr (sizeof(T) == 1) {
+            const uint32_t q = *(const uint32_t*)p;
+            o[0] = q & 255u; o[1] = (q >> 8) & 255u; o[2] = (q >> 16) & 255u; o[3] = q >> 24;
+        } else {
+            const uint2 q = *(const uint2*)p;
+            o[0] = q.x & 0xffffu; o[1] = q.x >> 16; o[2] = q.y & 0xffffu; o[3] = q.y >> 16;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = p[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] &= mask;
+}
+
+// the first n (1..4) of 4 codes to consecutive samples
+template <typename T>
+__device__ __forceinline__ void store4(T* __restrict__ p, const unsigned v[4], int n) {
+    if (n == 4 && ((uintptr_t)p & (4 * sizeof(T) - 1)) == 0) {
+        if constexpr (sizeof(T) == 1) *(uint32_t*)p = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        else *(uint2*)p = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+    } else {
+        for (int i = 0; i < n; ++i) p[i] = (T)v[i];
+    }
+}
+
+// SX, SY: the chroma planes are (h >> SY, w >> SX); LEFT: the chroma sample lies on the even luma column (SX only; vertically it is centred)
+template <typename T, int SX, int SY, int LEFT>
+__global__ __launch_bounds__(HBD_WG) void yuv_to_f32_kernel(PlaneBatch fb, float* __restrict__ dst, long dst_img, int H, int W, int quads,
+                                                            int vec_ok, YuvParams k, int bilinear) {
+    static_assert(SX || !SY, "4:4:0 is not a layout of this file");
+    const long idx = (long)blockIdx.x * HBD_WG + threadIdx.x;
+    if (idx >= (long)H * quads) return;
+    const int y = (int)(idx / quads), x0 = (int)(idx - (long)y * quads) * 4;
+    const PlaneDesc im = fb.d[blockIdx.y];
+    const unsigned m = k.mask;
+    const int ch = im.h >> SY, cw = im.w >> SX;
+    const int ys = min(y, im.h - 1);                         // rows below the extent repeat its last row
+    const int cy = ys >> SY;
+    // the second chroma row of the vertical filter: the neighbour on the pixel's side, clamped (nearest, or no vertical subsampling: cy itself)
+    const int cyb = (SY && bilinear) ? min(max(cy + ((ys & 1) ? 1 : -1), 0), ch - 1) : cy;
+    const T* __restrict__ yr = (const T*)im.y + (long)ys * im.yrow;
+    const T* __restrict__ ua = (const T*)im.u + (long)cy * im.urow;
+    const T* __restrict__ ub = (const T*)im.u + (long)cyb * im.urow;
+    const T* __restrict__ va = (const T*)im.v + (long)cy * im.vrow;
+    const T* __restrict__ vb = (const T*)im.v + (long)cyb * im.vrow;
+    // Y and CU, CV = (SX ? 4 : 1) * (SY ? 4 : 1) times the upsampled chroma, exact
+    unsigned Y[4], CU[4], CV[4];
+    if (x0 + 3 < im.w) {                                     // 4 valid pixels
+        load4(yr + x0, m, Y);
+        if constexpr (!SX) {
+            load4(ua + x0, m, CU);
+            load4(va + x0, m, CV);
+        } else {
+            const int c0 = x0 >> 1;                          // c0 + 1 <= cw - 1 because x0 + 3 <= w - 1
+            auto vert = [&](const T* __restrict__ a, const T* __restrict__ b, int c) -> unsigned {
+                const unsigned p = a[c] & m;
+                return SY ? 3u * p + (b[c] & m) : p;         // (nearest: b == a, 4 p)
+            };
+            const unsigned u1 = vert(ua, ub, c0), u2 = vert(ua, ub, c0 + 1), v1 = vert(va, vb, c0), v2 = vert(va, vb, c0 + 1);
+            if (bilinear) {
+                const int cp = min(c0 + 2, cw - 1);
+                const unsigned u3 = vert(ua, ub, cp), v3 = vert(va, vb, cp);
+                if constexpr (LEFT) {                        // column 2k: sample k; column 2k + 1: (c[k] + c[k + 1]) / 2
+                    CU[0] = 4u * u1; CU[1] = 2u * (u1 + u2); CU[2] = 4u * u2; CU[3] = 2u * (u2 + u3);
+                    CV[0] = 4u * v1; CV[1] = 2u * (v1 + v2); CV[2] = 4u * v2; CV[3] = 2u * (v2 + v3);
+                } else {                                     // 3/4 of the sample the pixel lies in, 1/4 of the neighbour on its side
+                    const int cm = max(c0 - 1, 0);
+                    const unsigned u0 = vert(ua, ub, cm), v0 = vert(va, vb, cm);
+                    CU[0] = 3u * u1 + u0; CU[1] = 3u * u1 + u2; CU[2] = 3u * u2 + u1; CU[3] = 3u * u2 + u3;
+                    CV[0] = 3u * v1 + v0; CV[1] = 3u * v1 + v2; CV[2] = 3u * v2 + v1; CV[3] = 3u * v2 + v3;
+                }
+            } else {
+                CU[0] = CU[1] = 4u * u1; CU[2] = CU[3] = 4u * u2;
+                CV[0] = CV[1] = 4u * v1; CV[2] = CV[3] = 4u * v2;
+            }
+        }
+    } else {                                                 // at or beyond the right edge: every pixel from its nearest valid one
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int xs = min(x0 + i, im.w - 1);
+            Y[i] = yr[xs] & m;
+            if constexpr (!SX) {
+                CU[i] = ua[xs] & m;
+                CV[i] = va[xs] & m;
+            } else {
+                const int cx = xs >> 1;
+                int cxb = cx;                                // the second tap and the weight of the first, in quarters
+                unsigned wa = 4u;
+                if (bilinear) {
+                    if (LEFT) {
+                        if (xs & 1) { cxb = min(cx + 1, cw - 1); wa = 2u; }
+                    } else {
+                        cxb = min(max(cx + ((xs & 1) ? 1 : -1), 0), cw - 1);
+                        wa = 3u;
+                    }
+                }
+                const unsigned wb = 4u - wa;
+                const unsigned pa = ua[cx] & m, pb = ua[cxb] & m, qa = va[cx] & m, qb = va[cxb] & m;
+                if (SY) {
+                    CU[i] = wa * (3u * pa + (ub[cx] & m)) + wb * (3u * pb + (ub[cxb] & m));
+                    CV[i] = wa * (3u * qa + (vb[cx] & m)) + wb * (3u * qb + (vb[cxb] & m));
+                } else {
+                    CU[i] = wa * pa + wb * pb;
+                    CV[i] = wa * qa + wb * qb;
+                }
+            }
+        }
+    }
+    constexpr float inv = 1.0f / (float)((SX ? 4 : 1) * (SY ? 4 : 1));
+    float o3[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float yn = __fdiv_rn((float)Y[i] - k.yo, k.ys);
+        const float cb = __fdiv_rn((float)CU[i] * inv - k.co, k.cs);   // C / 16 (/ 4) is exact
+        const float cr = __fdiv_rn((float)CV[i] * inv - k.co, k.cs);
+        o3[0][i] = clamp01(yn + k.a * cr);
+        o3[2][i] = clamp01(yn + k.b * cb);
+        o3[1][i] = clamp01((yn - k.d * cb) - k.e * cr);
+    }
+    float* o = dst + (long)blockIdx.y * dst_img + (long)y * W + x0;
+    const long plane = (long)H * W;
+    if (vec_ok) {                                            // W % 4 == 0: the quad is whole and 16-byte aligned
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(float4*)(o + c * plane) = make_float4(o3[c][0], o3[c][1], o3[c][2], o3[c][3]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (x0 + i < W) o[c * plane + i] = o3[c][i];
+    }
+}
+
+// rint(v), ties to even, clamped to 0..peak (v is finite: its inputs were clamped)
+__device__ __forceinline__ unsigned code_of(float v, float peak) {
+    v = rintf(v);
+    v = v > 0.0f ? v : 0.0f;
+    v = v < peak ? v : peak;
+    return (unsigned)(int)v;
+}
+
+// one pixel: clamped r, g, b -> y' and the two colour differences
+__device__ __forceinline__ void ycc(float r, float g, float b, const YuvParams& k, float& yn, float& cb, float& cr) {
+    const float R = clamp01(r), G = clamp01(g), B = clamp01(b);
+    yn = (k.kr * R + k.kg * G) + k.kb * B;
+    cb = __fdiv_rn(B - yn, k.b);
+    cr = __fdiv_rn(R - yn, k.a);
+}
+
+template <typename T, int SX, int SY, int LEFT>
+__global__ __launch_bounds__(HBD_WG) void f32_to_yuv_kernel(const float* __restrict__ src, long src_img, long src_plane, long src_row,
+                                                            PlaneBatch fb, int quads, int hblocks, int vec_ok, YuvParams k) {
+    static_assert(SX || !SY, "4:4:0 is not a layout of this file");
+    constexpr int R = SY ? 2 : 1;                            // rows of a block
+    const long idx = (long)blockIdx.x * HBD_WG + threadIdx.x;
+    if (idx >= (long)hblocks * quads) return;
+    const int by = (int)(idx / quads), x0 = (int)(idx - (long)by * quads) * 4;
+    const int y0 = by << SY;
+    const PlaneDesc im = fb.d[blockIdx.y];
+    if (y0 >= im.h || x0 >= im.w) return;                    // h (w) is even where subsampled: the block's R rows (a column pair) are inside
+    const int n = min(4, im.w - x0);                         // valid columns of this block (2 or 4 where SX)
+    const float* __restrict__ s = src + (long)blockIdx.y * src_img + (long)y0 * src_row + x0;
+    float p[3][R][4];
+    if (vec_ok && n == 4) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float4 f = *(const float4*)(s + c * src_plane + r * src_row);
+                p[c][r][0] = f.x; p[c][r][1] = f.y; p[c][r][2] = f.z; p[c][r][3] = f.w;
+            }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p[c][r][i] = i < n ? s[c * src_plane + r * src_row + i] : 0.0f;
+    }
+    unsigned Yc[R][4];
+    float cb[R][4], cr[R][4];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float yn;
+            ycc(p[0][r][i], p[1][r][i], p[2][r][i], k, yn, cb[r][i], cr[r][i]);
+            Yc[r][i] = code_of(yn * k.ys + k.yo, k.peak);
+        }
+#pragma unroll
+    for (int r = 0; r < R; ++r) store4((T*)im.y + (long)(y0 + r) * im.yrow + x0, Yc[r], n);
+    if constexpr (!SX) {                                     // 4:4:4: a chroma sample per pixel
+        unsigned Uc[4], Vc[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            Uc[i] = code_of(cb[0][i] * k.cs + k.co, k.peak);
+            Vc[i] = code_of(cr[0][i] * k.cs + k.co, k.peak);
+        }
+        store4((T*)im.u + (long)y0 * im.urow + x0, Uc, n);
+        store4((T*)im.v + (long)y0 * im.vrow + x0, Vc, n);
+    } else {
+        float pb[R], pr[R];                                  // left siting: the colour differences of column max(x0 - 1, 0), another lane's pixel
+        if constexpr (LEFT) {
+            const int off = x0 > 0 ? -1 : 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                float yn;
+                ycc(s[r * src_row + off], s[src_plane + r * src_row + off], s[2 * src_plane + r * src_row + off], k, yn, pb[r], pr[r]);
+            }
+        }
+        T* ou = (T*)im.u + (long)by * im.urow + (x0 >> 1);
+        T* ov = (T*)im.v + (long)by * im.vrow + (x0 >> 1);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float hu[R], hv[R];                              // the horizontal step per row
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if constexpr (LEFT) {                        // ((c[2k - 1] + c[2k + 1]) + (c[2k] + c[2k])) / 4, c[-1] = c[0]
+                    const float mu = j ? cb[r][1] : pb[r], mv = j ? cr[r][1] : pr[r];
+                    hu[r] = ((mu + cb[r][2 * j + 1]) + (cb[r][2 * j] + cb[r][2 * j])) * 0.25f;
+                    hv[r] = ((mv + cr[r][2 * j + 1]) + (cr[r][2 * j] + cr[r][2 * j])) * 0.25f;
+                } else {
+                    hu[r] = cb[r][2 * j] + cb[r][2 * j + 1];
+                    hv[r] = cr[r][2 * j] + cr[r][2 * j + 1];
+                }
+            }
+            float mu, mv;
+            if constexpr (LEFT) {
+                mu = SY ? (hu[0] + hu[R - 1]) * 0.5f : hu[0];
+                mv = SY ? (hv[0] + hv[R - 1]) * 0.5f : hv[0];
+            } else {
+                mu = SY ? (hu[0] + hu[R - 1]) * 0.25f : hu[0] * 0.5f;
+                mv = SY ? (hv[0] + hv[R - 1]) * 0.25f : hv[0] * 0.5f;
+            }
+            if (2 * j < n) {
+                ou[j] = (T)code_of(mu * k.cs + k.co, k.peak);
+                ov[j] = (T)code_of(mv * k.cs + k.co, k.peak);
+            }
+        }
+    }
+}
+
+struct SsePair { const uint16_t *a, *b; long arow, brow; int h, w; };
+struct SseBatch { SsePair d[HBD_CHUNK]; };
+
+__global__ __launch_bounds__(HBD_WG) void sse_u16_kernel(SseBatch pb, unsigned long long* __restrict__ out, int chunks) {
+    const SsePair pr = pb.d[blockIdx.y];
+    const long idx = (long)blockIdx.x * HBD_WG + threadIdx.x;
+    unsigned long long acc = 0;                              // 64 bits from the lane on: 8 * 65535^2 does not fit 32
+    const int y = (int)(idx / chunks), x0 = (int)(idx - (long)y * chunks) * 8;
+    if (y < pr.h && x0 < pr.w) {                             // (no early return: every lane takes part in the wave's sum below)
+        const uint16_t* __restrict__ a = pr.a + (long)y * pr.arow + x0;
+        const uint16_t* __restrict__ b = pr.b + (long)y * pr.brow + x0;
+        if (x0 + 7 < pr.w && (((uintptr_t)a | (uintptr_t)b) & 15) == 0) {
+            const uint4 va = *(const uint4*)a, vb = *(const uint4*)b;
+            const uint32_t wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int s = 0; s < 32; s += 16) {
+                    const unsigned p = (wa[j] >> s) & 0xffffu, q = (wb[j] >> s) & 0xffffu;
+                    const unsigned d = p > q ? p - q : q - p;
+                    acc += (unsigned long long)(d * d);      // 65535^2 < 2^32
+                }
+        } else {
+            const int n = min(8, pr.w - x0);
+            for (int i = 0; i < n; ++i) {
+                const unsigned p = a[i], q = b[i];
+                const unsigned d = p > q ? p - q : q - p;
+                acc += (unsigned long long)(d * d);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out + blockIdx.y, acc);
+}
+
+bool enums_ok(int depth, int subsampling, int siting, int matrix, int range) {
+    return (depth == 8 || depth == 10 || depth == 12) &&
+           (subsampling == LVAE_YUV_SUB_420 || subsampling == LVAE_YUV_SUB_422 || subsampling == LVAE_YUV_SUB_444) &&
+           (siting == LVAE_YUV_SITING_CENTER || siting == LVAE_YUV_SITING_LEFT) &&
+           (matrix == LVAE_YUV_BT601 || matrix == LVAE_YUV_BT709 || matrix == LVAE_YUV_BT2020) &&
+           (range == LVAE_YUV_LIMITED || range == LVAE_YUV_FULL);
+}
+
+// The frames' descriptors are valid: planes non-null, extents positive, even where subsampled and inside (H, W), rows that hold their plane's width
+bool frames_ok(const void* const* y, const void* const* u, const void* const* v, const long* y_row, const long* u_row, const long* v_row,
+               const int* hw, int B, int sx, int sy, int H, int W) {
+    if (!y || !u || !v || !y_row || !u_row || !v_row || !hw) return false;
+    for (int b = 0; b < B; ++b) {
+        const int h = hw[2 * b], w = hw[2 * b + 1];
+        if (h <= 0 || w <= 0 || (h & sy) || (w & sx) || h > H || w > W) return false;
+        if (!y[b] || !u[b] || !v[b] || y_row[b] < w || u_row[b] < (w >> sx) || v_row[b] < (w >> sx)) return false;
+    }
+    return true;
+}
+
+PlaneBatch plane_batch(const void* const* y, const void* const* u, const void* const* v, const long* y_row, const long* u_row,
+                       const long* v_row, const int* hw, int b0, int n) {
+    PlaneBatch fb = {};
+    for (int i = 0; i < n; ++i) {
+        const int b = b0 + i;
+        fb.d[i] = {const_cast<void*>(y[b]), const_cast<void*>(u[b]), const_cast<void*>(v[b]), y_row[b], u_row[b], v_row[b], hw[2 * b], hw[2 * b + 1]};
+    }
+    return fb;
+}
+
+// the variant of KERNEL for (depth, subsampling, siting) -- siting has no effect without horizontal subsampling
+#define HBD_PICK(KERNEL, depth, sub, left)                                                                                              \
+    ((depth) == 8 ? ((sub) == LVAE_YUV_SUB_444   ? KERNEL<uint8_t, 0, 0, 0>                                                             \
+                     : (sub) == LVAE_YUV_SUB_422 ? ((left) ? KERNEL<uint8_t, 1, 0, 1> : KERNEL<uint8_t, 1, 0, 0>)                       \
+                                                 : ((left) ? KERNEL<uint8_t, 1, 1, 1> : KERNEL<uint8_t, 1, 1, 0>))                      \
+                  : ((sub) == LVAE_YUV_SUB_444   ? KERNEL<uint16_t, 0, 0, 0>                                                            \
+                     : (sub) == LVAE_YUV_SUB_422 ? ((left) ? KERNEL<uint16_t, 1, 0, 1> : KERNEL<uint16_t, 1, 0, 0>)                     \
+                                                 : ((left) ? KERNEL<uint16_t, 1, 1, 1> : KERNEL<uint16_t, 1, 1, 0>)))
+
+}  // namespace
+
+extern "C" int lvae_image_yuv_to_f32(const void* const* y, const void* const* u, const void* const* v, const long* y_row, const long* u_row,
+                                     const long* v_row, const int* hw, int B, int depth, int subsampling, int siting, int matrix, int range,
+                                     int chroma, float* dst, long dst_img, int H, int W, void* stream) {
+    if (!dst || B <= 0 || H <= 0 || W <= 0 || !enums_ok(depth, subsampling, siting, matrix, range) ||
+        (chroma != LVAE_YUV_NEAREST && chroma != LVAE_YUV_BILINEAR))
+        return -22;
+    const int sx = subsampling != LVAE_YUV_SUB_444, sy = subsampling == LVAE_YUV_SUB_420;
+    const int quads = (W + 3) / 4;
+    if ((long)H * quads > (long)INT_MAX || (B > 1 && dst_img < 3L * H * W)) return -22;
+    if (!frames_ok(y, u, v, y_row, u_row, v_row, hw, B, sx, sy, H, W)) return -22;
+    const int vec_ok = W % 4 == 0 && dst_img % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+    const unsigned gx = (unsigned)(((long)H * quads + HBD_WG - 1) / HBD_WG);
+    const YuvParams k = yuv_params(matrix, range, depth);
+    auto kernel = HBD_PICK(yuv_to_f32_kernel, depth, subsampling, siting == LVAE_YUV_SITING_LEFT);
+    for (int b0 = 0; b0 < B; b0 += HBD_CHUNK) {
+        const int n = B - b0 < HBD_CHUNK ? B - b0 : HBD_CHUNK;
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)n), dim3(HBD_WG), 0, (hipStream_t)stream, plane_batch(y, u, v, y_row, u_row, v_row, hw, b0, n),
+                           dst + (long)b0 * dst_img, dst_img, H, W, quads, vec_ok, k, chroma == LVAE_YUV_BILINEAR);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_image_f32_to_yuv(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int depth,
+                                     int subsampling, int siting, int matrix, int range, void* const* y, void* const* u, void* const* v,
+                                     const long* y_row, const long* u_row, const long* v_row, void* stream) {
+    if (!src || B <= 0 || H <= 0 || W <= 0 || !enums_ok(depth, subsampling, siting, matrix, range)) return -22;
+    if (src_row < W || src_plane < (long)(H - 1) * src_row + W || (B > 1 && src_img < 2 * src_plane + (long)(H - 1) * src_row + W)) return -22;
+    const int sx = subsampling != LVAE_YUV_SUB_444, sy = subsampling == LVAE_YUV_SUB_420;
+    if (!frames_ok(y, u, v, y_row, u_row, v_row, hw, B, sx, sy, H, W)) return -22;
+    int hmax = 0, wmax = 0;
+    for (int b = 0; b < B; ++b) {
+        hmax = hw[2 * b] > hmax ? hw[2 * b] : hmax;
+        wmax = hw[2 * b + 1] > wmax ? hw[2 * b + 1] : wmax;
+    }
+    const int quads = (wmax + 3) / 4, hblocks = hmax >> sy;
+    if ((long)hblocks * quads > (long)INT_MAX) return -22;
+    const int vec_ok = src_img % 4 == 0 && src_plane % 4 == 0 && src_row % 4 == 0 && ((uintptr_t)src & 15) == 0;
+    const unsigned gx = (unsigned)(((long)hblocks * quads + HBD_WG - 1) / HBD_WG);
+    const YuvParams k = yuv_params(matrix, range, depth);
+    auto kernel = HBD_PICK(f32_to_yuv_kernel, depth, subsampling, siting == LVAE_YUV_SITING_LEFT);
+    for (int b0 = 0; b0 < B; b0 += HBD_CHUNK) {
+        const int n = B - b0 < HBD_CHUNK ? B - b0 : HBD_CHUNK;
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)n), dim3(HBD_WG), 0, (hipStream_t)stream, src + (long)b0 * src_img, src_img, src_plane,
+                           src_row, plane_batch(y, u, v, y_row, u_row, v_row, hw, b0, n), quads, hblocks, vec_ok, k);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_sse_u16(const uint16_t* const* a, const long* a_row, const uint16_t* const* b, const long* b_row, const int* hw, int n,
+                            uint64_t* out, void* stream) {
+    if (!a || !a_row || !b || !b_row || !hw || !out || n <= 0) return -22;
+    int hmax = 0, wmax = 0;
+    for (int k = 0; k < n; ++k) {
+        const int h = hw[2 * k], w = hw[2 * k + 1];
+        if (!a[k] || !b[k] || h <= 0 || w <= 0 || a_row[k] < w || b_row[k] < w) return -22;
+        hmax = h > hmax ? h : hmax;
+        wmax = w > wmax ? w : wmax;
+    }
+    const int chunks = (wmax - 1) / 8 + 1;                   // one grid shape for every launch of the call: the largest plane's
+    const long most = (long)hmax * chunks;
+    if (most > (long)INT_MAX) return -22;
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t) * (size_t)n, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    const unsigned gx = (unsigned)((most + HBD_WG - 1) / HBD_WG);
+    for (int k0 = 0; k0 < n; k0 += HBD_CHUNK) {
+        const int m = n - k0 < HBD_CHUNK ? n - k0 : HBD_CHUNK;
+        SseBatch pb = {};
+        for (int i = 0; i < m; ++i) {
+            const int k = k0 + i;
+            pb.d[i] = {a[k], b[k], a_row[k], b_row[k], hw[2 * k], hw[2 * k + 1]};
+        }
+        hipLaunchKernelGGL(sse_u16_kernel, dim3(gx, (unsigned)m), dim3(HBD_WG), 0, (hipStream_t)stream, pb, (unsigned long long*)out + k0, chunks);
+    }
+    return (int)hipGetLastError();
+}

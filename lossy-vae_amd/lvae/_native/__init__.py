@@ -75,6 +75,8 @@ STATUS_RANGE, STATUS_NONFINITE_PRIOR, STATUS_NONFINITE_LATENT, STATUS_NONFINITE_
 EPI_BIAS, EPI_BIAS_GELU, EPI_GAMMA_RES, EPI_RES = 0, 1, 2, 3
 ST_ROWMAJOR, ST_SHUFFLE, ST_IMAGE = 0, 2, 3
 YUV_FORMATS, YUV_MATRICES, YUV_RANGES, YUV_CHROMA = ('i420', 'nv12'), ('bt601', 'bt709'), ('limited', 'full'), ('nearest', 'bilinear')   # LVAE_YUV_*: a name's code is its index
+YUV_SUBSAMPLINGS, YUV_SITINGS, YUV_MATRICES2 = ('420', '422', '444'), ('center', 'left'), ('bt601', 'bt709', 'bt2020')   # LVAE_YUV_SUB_* / LVAE_YUV_SITING_* / the matrices of lvae_image_yuv_to_f32 / lvae_image_f32_to_yuv
+YUV_DEPTHS = (8, 10, 12)
 EVAL_CHUNKS = 256               # LVAE_EVAL_CHUNKS: lvae_rd_image_f32 / lvae_pixel_nll_f32 take ws = double[B][EVAL_CHUNKS][2]
 
 _vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
@@ -140,6 +142,9 @@ SIGNATURES = {
     'lvae_image_yuv420_to_f32': (_i, [_vp] * 7 + [_i] * 5 + [_vp, _l, _i, _i, _vp]),
     'lvae_image_f32_to_yuv420': (_i, [_vp, _l, _l, _l, _i, _i, _vp] + [_i] * 4 + [_vp] * 7),
     'lvae_sse_u8': (_i, [_vp] * 5 + [_i, _vp, _vp]),
+    'lvae_image_yuv_to_f32': (_i, [_vp] * 7 + [_i] * 7 + [_vp, _l, _i, _i, _vp]),
+    'lvae_image_f32_to_yuv': (_i, [_vp, _l, _l, _l, _i, _i, _vp] + [_i] * 6 + [_vp] * 7),
+    'lvae_sse_u16': (_i, [_vp] * 5 + [_i, _vp, _vp]),
     'lvae_tile_stitch': (_i, [_vp, _l, _l, _vp, _vp] + [_i] * 11 + [_vp, _l, _l, _i, _vp, _sz, _vp]),
     'lvae_tile_stitch_workspace_bytes': (_sz, [_i, _i]),
 }

@@ -139,32 +139,49 @@ def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=No
 
 
 @torch.no_grad()
-def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, **colour):
+def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, depth=8, subsampling='420', siting='center',
+                 **colour):
     """A raw 8-bit 4:2:0 file coded frame by frame (an image codec as an intra-frame coder) -> dict of means over its frames: 'bpp'
     (8 * len(blob) / (h * w)) and the keys of lvae.metrics.psnr_yuv420 ('mse-y' ... 'psnr-yuv'), computed between the file's bytes and
     decompress_yuv420's.  colour: matrix / range / chroma of compress_yuv420 (matrix and range also go to decompress_yuv420).  Every frame
     is uploaded once, as the 1.5 bytes per pixel the file holds; conversion, coding, reconstruction and the squared errors stay on the
-    device, and three integers per frame come back.  Frames are coded `batch` at a time; lmb: as in compress_yuv420."""
-    from .metrics import PSNR_YUV_KEYS, psnr_yuv420
-    from .utils.yuv import read_yuv420
+    device, and three integers per frame come back.  Frames are coded `batch` at a time; lmb: as in compress_yuv420.
+    depth / subsampling / siting: with any value other than the defaults (8, '420', 'center') the file is a planar one of that depth and
+    subsampling (utils.yuv.read_yuv; fmt must stay 'i420'), coded by compress_yuv / decompress_yuv with that siting and measured by
+    lvae.metrics.psnr_yuv, whose key 'psnr-avg' joins the result; matrix may then be 'bt2020'."""
+    from .metrics import PSNR_YUV_KEYS, PSNR_YUV_KEYS2, psnr_yuv, psnr_yuv420
+    from .utils.yuv import read_yuv, read_yuv420
     unknown = set(colour) - {'matrix', 'range', 'chroma'}
     if unknown:
         raise TypeError(f'yuv_evaluate: unexpected arguments {sorted(unknown)}')
     dev = next(model.parameters()).device
-    frames = [f.to(dev, non_blocking=True) for f in read_yuv420(yuv_path, width, height, fmt, frames=max_frames)]
     dec = {k: v for k, v in colour.items() if k != 'chroma'}
+    general = (depth, subsampling, siting) != (8, '420', 'center')
+    if general:
+        if fmt != 'i420':
+            raise ValueError(f'yuv_evaluate: depth / subsampling / siting apply to planar files, got fmt={fmt!r}')
+        frames = read_yuv(yuv_path, width, height, subsampling, depth, frames=max_frames)
+        compress = lambda chunk, **enc: model.compress_yuv(chunk, siting=siting, **enc)
+        decompress = lambda blobs: model.decompress_yuv(blobs, depth=depth, subsampling=subsampling, siting=siting, **dec)
+        measure, keys = psnr_yuv, PSNR_YUV_KEYS2
+    else:
+        frames = read_yuv420(yuv_path, width, height, fmt, frames=max_frames)
+        compress = model.compress_yuv420
+        decompress = lambda blobs: model.decompress_yuv420(blobs, fmt=fmt, **dec)
+        measure, keys = psnr_yuv420, PSNR_YUV_KEYS
+    frames = [f.to(dev, non_blocking=True) for f in frames]
     rows, step = [], max(1, int(batch))
     for o in range(0, len(frames), step):
         chunk = frames[o:o + step]
         enc = dict(colour)
         if lmb is not None:                    # a number, or one lambda per frame of the file
             enc['lmb'] = lmb if isinstance(lmb, (int, float)) else list(lmb)[o:o + step]
-        blobs = model.compress_yuv420(chunk, **enc)
-        recs = model.decompress_yuv420(blobs, fmt=fmt, **dec)
-        for blob, stats in zip(blobs, psnr_yuv420(chunk, recs)):
+        blobs = compress(chunk, **enc)
+        recs = decompress(blobs)
+        for blob, stats in zip(blobs, measure(chunk, recs)):
             rows.append(dict(stats, bpp=float(8 * len(blob) / float(height * width))))
     out = {}
-    for k in ('bpp',) + PSNR_YUV_KEYS:
+    for k in ('bpp',) + keys:
         acc = 0.0
         for r in rows:                         # frame order: the means do not depend on `batch`
             acc += r[k]

@@ -87,6 +87,76 @@ def psnr_yuv420(ref_frames, rec_frames):
     return out
 
 
+PSNR_YUV_KEYS2 = PSNR_YUV_KEYS + ('psnr-avg',)
+
+
+def sse_u16(pairs):
+    """sse_u8 for planes of 16-bit codes: [(a, b)] pairs of equally shaped 2-D torch.int16 planes, read as UNSIGNED 16-bit words -> their
+    sums of squared differences as Python ints, exact for any 16-bit values.  If a plane is on a GPU: ONE lvae_sse_u16 launch for all pairs
+    (64-bit integer sums on the device, one word per pair comes back); CPU planes: numpy int64."""
+    for a, b in pairs:
+        if a.dtype != torch.int16 or b.dtype != torch.int16 or a.dim() != 2 or a.shape != b.shape or a.numel() == 0:
+            raise ValueError(f'sse_u16: expected two equally shaped, non-empty 2-D int16 planes, got {tuple(a.shape)} and {tuple(b.shape)}')
+    devs = {p.device for ab in pairs for p in ab if p.is_cuda}
+    if len(devs) > 1:
+        raise ValueError(f'sse_u16: planes on several GPUs {sorted(map(str, devs))}')
+    if not devs:
+        out = []
+        for a, b in pairs:
+            d = a.contiguous().numpy().view('uint16').astype('int64') - b.contiguous().numpy().view('uint16').astype('int64')
+            out.append(int((d * d).sum()))
+        return out
+    from . import _native
+    device, n = devs.pop(), len(pairs)
+    plane = lambda p: (p if p.stride(1) == 1 and p.stride(0) >= p.shape[1] else p.contiguous())
+    a = [plane(p.to(device, non_blocking=True)) for p, _ in pairs]
+    b = [plane(p.to(device, non_blocking=True)) for _, p in pairs]
+    ptr = lambda ps: (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
+    row = lambda ps: (ctypes.c_long * n)(*[p.stride(0) for p in ps])          # in samples
+    hw = (ctypes.c_int * (2 * n))(*[int(v) for p in a for v in p.shape])
+    out = torch.empty(n, dtype=torch.int64, device=device)            # (the sums stay far below 2^63: 65535^2 per sample)
+    with torch.cuda.device(device):
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _native.check(_native.lib().lvae_sse_u16(ptr(a), row(a), ptr(b), row(b), hw, n, out.data_ptr(), st), 'sse_u16')
+    return [int(v) for v in out.cpu().tolist()]
+
+
+def psnr_yuv(ref_frames, rec_frames):
+    """PSNR of utils.yuv.YuvFrame lists (or two frames) of any depth and subsampling: per frame a dict {'mse-y', 'mse-u', 'mse-v', 'psnr-y',
+    'psnr-u', 'psnr-v', 'psnr-yuv', 'psnr-avg'} of floats.  mse = the plane's exact sum of squared code differences (sse_u8 / sse_u16) / its
+    sample count, in float64; psnr = 10 log10(peak^2 / mse), inf for identical planes, with peak = 255 * 2^(depth - 8) -- 1020 at 10 bits,
+    4080 at 12: the convention of the HM / VTM reference software, NOT 2^depth - 1.  psnr-yuv = (6 psnr-y + psnr-u + psnr-v) / 8, HM's
+    weighting for 4:2:0; psnr-avg is the PSNR of the pooled error, (sse-y + sse-u + sse-v) / (all three sample counts): the meaningful single
+    number for 4:2:2 and 4:4:4, where 6:1:1 does not reflect the sample counts."""
+    from .utils.yuv import YuvFrame
+    if isinstance(ref_frames, YuvFrame):
+        return psnr_yuv([ref_frames], [rec_frames])[0]
+    ref, rec = list(ref_frames), list(rec_frames)
+    if len(ref) != len(rec) or not ref:
+        raise ValueError(f'psnr_yuv: {len(ref)} reference and {len(rec)} reconstructed frames')
+    for i, (a, b) in enumerate(zip(ref, rec)):
+        if (a.size, a.depth, a.subsampling) != (b.size, b.depth, b.subsampling):
+            raise ValueError(f'psnr_yuv: frame {i} is {a.size} {a.depth}-bit {a.subsampling} against {b.size} {b.depth}-bit {b.subsampling}')
+    if any(a.depth != ref[0].depth for a in ref):
+        raise ValueError('psnr_yuv: the frames of one call share a depth')
+    depth = ref[0].depth
+    sse = (sse_u8 if depth == 8 else sse_u16)([(getattr(a, p), getattr(b, p)) for a, b in zip(ref, rec) for p in 'yuv'])
+    peak2 = (255.0 * (1 << (depth - 8))) ** 2
+    db = lambda mse: float(10 * math.log10(peak2 / mse)) if mse > 0 else math.inf
+    out = []
+    for i, a in enumerate(ref):
+        row, total, count = {}, 0, 0
+        for j, p in enumerate('yuv'):
+            mse = sse[3 * i + j] / float(getattr(a, p).numel())
+            row['mse-' + p] = mse
+            row['psnr-' + p] = db(mse)
+            total, count = total + sse[3 * i + j], count + getattr(a, p).numel()
+        row['psnr-yuv'] = (6 * row['psnr-y'] + row['psnr-u'] + row['psnr-v']) / 8
+        row['psnr-avg'] = db(total / float(count))
+        out.append({k: row[k] for k in PSNR_YUV_KEYS2})
+    return out
+
+
 def ms_ssim_db(v):
     """MS-SSIM on the decibel scale result tables use: -10 log10(1 - v)."""
     if torch.is_tensor(v):

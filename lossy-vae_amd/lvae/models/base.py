@@ -596,7 +596,7 @@ class CodecBase(nn.Module):
         return self._compress_byte_batch(U8Batch(images, self.max_stride, self._dummy.device), lmb, 'compress_images')
 
     def _compress_byte_batch(self, batch, lmb, who):
-        """compress_batch on a batch of 8-bit inputs (utils.image.U8Batch, utils.yuv.Yuv420Batch: `.shape`, `.sizes`, `.device`, `.fill`)
+        """compress_batch on a batch of 8-bit inputs (utils.image.U8Batch, utils.yuv.Yuv420Batch / YuvBatch: `.shape`, `.sizes`, `.device`, `.fill`)
         -> the models' containers, one per input."""
         _, _, H, W = batch.shape
         d = self.max_stride
@@ -641,6 +641,32 @@ class CodecBase(nn.Module):
         2x2 chroma mean, round-half-even).  matrix / range: the stream does not record them; pass what the encoder was given."""
         from ..utils.yuv import from_rgb01
         return self._decompress_blobs(blobs, lambda x, sizes: from_rgb01(x, sizes, fmt=fmt, matrix=matrix, range=range))
+
+    # ---- the same for planar frames of 8 / 10 / 12 bits at 4:2:0 / 4:2:2 / 4:4:4 with centre- or left-sited chroma (csrc/yuv_hbd_io.hip)
+    @torch.no_grad()
+    def compress_yuv(self, frames, lmb=None, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
+        """compress_yuv420 for a list of utils.yuv.YuvFrame that share depth and subsampling and whose sizes PADDED to multiples of
+        max_stride agree -> list of bytes, element i being the model's own container: the file compress_file would write for the RGB image
+        utils.yuv.to_rgb01_any gives for frame i.  matrix: 'bt601' | 'bt709' | 'bt2020'; siting: 'center' | 'left' (H.264 / HEVC co-sited
+        chroma).  The planes go to the device as their file holds them (1 or 2 bytes per sample).  Neither the colour parameters nor depth,
+        subsampling and siting are stored in the stream: decompress_yuv has to be given the encoder's."""
+        from ..utils.yuv import YuvBatch
+        return self._compress_byte_batch(YuvBatch(frames, self.max_stride, self._dummy.device, matrix, range, chroma, siting), lmb, 'compress_yuv')
+
+    @torch.no_grad()
+    def decompress_yuv(self, blobs, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited'):
+        """compress_yuv (or compress_images / compress_file) bytes -> list of utils.yuv.YuvFrame of `depth` and `subsampling` on the
+        model's device, each cropped to the size in its header and converted on the device (utils.yuv.from_rgb01_any).  A depth above 8
+        keeps precision of the fp32 reconstruction that 8-bit codes drop.  ValueError: a header's size does not fit the subsampling.
+        depth / siting / matrix / range: the stream does not record them; pass what the encoder was given."""
+        from ..utils.yuv import _check2, _extent_ok, from_rgb01_any
+        _check2(depth, subsampling, siting, matrix, range)
+        for i, b in enumerate(blobs):
+            h, w = self._unpack_blob(b)[1]
+            if not _extent_ok(h, w, subsampling):
+                raise ValueError(f'decompress_yuv: blob {i} holds a {h} x {w} image, which does not fit subsampling {subsampling}')
+        conv = lambda x, sizes: from_rgb01_any(x, sizes, depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range)
+        return self._decompress_blobs(blobs, conv)
 
     @torch.no_grad()
     def decompress_images(self, blobs):

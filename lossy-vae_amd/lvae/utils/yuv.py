@@ -1,15 +1,21 @@
-"""8-bit YUV 4:2:0 frames in and out of the codec: planar I420 / semi-planar NV12 bytes <-> the fp32 NCHW RGB tensors in [0, 1] the
-models code, and raw .yuv files.
+"""YUV frames in and out of the codec: planes of raw video <-> the fp32 NCHW RGB tensors in [0, 1] the models code, and raw .yuv files.
 
-This file DEFINES the two conversions, as torch expressions on CPU tensors (`yuv_to_rgb_expr`, `rgb_to_yuv_expr`): fp32 throughout, the
-constants below as fp32 values, every operation rounded on its own, divisions IEEE.  On the GPU the conversions are the HIP kernels of
-csrc/yuv_io.hip (`lvae_image_yuv420_to_f32`, `lvae_image_f32_to_yuv420`), which reproduce the expressions' bits: a frame is uploaded as
-the 1.5 bytes per pixel its file held, upsampled, converted and replicate-padded where the encoder reads it, and a reconstruction becomes
-bytes on the device before it is copied back.  The same split as utils.image.to_float01 / to_u8.
+Two generations live here.  The first is the 8-bit 4:2:0 path (`Yuv420Frame`: planar I420 / semi-planar NV12 bytes, centre-sited chroma,
+BT.601 / BT.709; `yuv_to_rgb_expr`, `rgb_to_yuv_expr`, `to_rgb01`, `from_rgb01`, `read_yuv420`, `write_yuv420`), which keeps its behaviour
+and its bits.  The second generalises it (`YuvFrame`: planar, 8 / 10 / 12 bits, 4:2:0 / 4:2:2 / 4:4:4, chroma sited in the centre or on
+the left (co-sited, H.264 / HEVC chroma_sample_loc_type 0), BT.601 / BT.709 / BT.2020 non-constant luminance; `yuv_to_rgb_expr2`,
+`rgb_to_yuv_expr2`, `to_rgb01_any`, `from_rgb01_any`, `read_yuv`, `write_yuv`); at 8 bits, 4:2:0, centre siting it gives the bits of the first.
 
-Conventions: ITU-R BT.601 / BT.709 matrices (Kr, Kb = 0.299, 0.114 / 0.2126, 0.0722), limited (Y 16..235, C 16..240) or full (0..255)
-range, chroma sited in the CENTRE of its 2x2 luma block (JPEG / MPEG-1).  Co-sited chroma (MPEG-2 'left'), 4:2:2 / 4:4:4 and more than
-8 bits are not supported.  The colour parameters are the caller's on both sides: no stream or container stores them.
+This file DEFINES the conversions, as torch expressions on CPU tensors: fp32 throughout, the constants below as fp32 values, every
+operation rounded on its own, divisions IEEE.  On the GPU the conversions are the HIP kernels of csrc/yuv_io.hip and csrc/yuv_hbd_io.hip,
+which reproduce the expressions' bits: a frame is uploaded as the bytes its file held (1 or 2 per sample), upsampled, converted and
+replicate-padded where the encoder reads it, and a reconstruction becomes codes on the device before it is copied back.  The same split
+as utils.image.to_float01 / to_u8.
+
+Samples of more than 8 bits are 16-bit little-endian words with the value in the LOW bits (yuv420p10le, yuv422p12le: what ffmpeg rawvideo
+and HM / VTM read and write), held as torch.int16.  Not supported: semi-planar high-bit-depth layouts with the value in the high bits
+(P010 and kin), 16-bit depth, chroma sitings other than centre / left.  The colour parameters, the depth and the siting are the caller's
+on both sides: no stream or container stores them.
 """
 import ctypes
 import os
@@ -21,9 +27,11 @@ import torch.nn.functional as F
 from .image import _canvas
 
 from .._native import YUV_CHROMA as CHROMA, YUV_FORMATS as FORMATS, YUV_MATRICES as MATRICES, YUV_RANGES as RANGES   # index = LVAE_YUV_* code
+from .._native import YUV_DEPTHS as DEPTHS, YUV_MATRICES2 as MATRICES2, YUV_SITINGS as SITINGS, YUV_SUBSAMPLINGS as SUBSAMPLINGS
 # per matrix: Kr, Kg, Kb, a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg -- the literals of csrc/yuv_io.hip
 COEF = {'bt601': (0.299, 0.587, 0.114, 1.402, 1.772, 0.344136286, 0.714136286),
-        'bt709': (0.2126, 0.7152, 0.0722, 1.5748, 1.8556, 0.187324273, 0.468124273)}
+        'bt709': (0.2126, 0.7152, 0.0722, 1.5748, 1.8556, 0.187324273, 0.468124273),
+        'bt2020': (0.2627, 0.678, 0.0593, 1.4746, 1.8814, 0.164553127, 0.571353127)}    # YuvFrame path only (MATRICES2; csrc/yuv_hbd_io.hip)
 SCALES = {'limited': (16.0, 219.0, 224.0), 'full': (0.0, 255.0, 255.0)}       # luma offset, luma scale, chroma scale
 
 
@@ -308,5 +316,331 @@ def from_rgb01(x, sizes=None, fmt='i420', matrix='bt709', range='limited'):
         _native.check(_native.lib().lvae_image_f32_to_yuv420(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[6], B,
                                                              FORMATS.index(fmt), MATRICES.index(matrix), RANGES.index(range), *args[:6], st),
                       'image_f32_to_yuv420')
+    del keep
+    return outs
+
+
+# =============================================================================================== 8 / 10 / 12 bits, 4:2:0 / 4:2:2 / 4:4:4
+SHIFTS = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}       # subsampling -> (horizontal, vertical) shift of the chroma planes
+
+
+def _check2(depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', chroma='bilinear'):
+    for v, known, what in ((depth, DEPTHS, 'depth'), (subsampling, SUBSAMPLINGS, 'subsampling'), (siting, SITINGS, 'siting'),
+                           (matrix, MATRICES2, 'matrix'), (range, RANGES, 'range'), (chroma, CHROMA, 'chroma')):
+        if v not in known:
+            raise ValueError(f'{what} is one of {known}, got {v!r}')
+
+
+def _extent_ok(h, w, subsampling):
+    sx, sy = SHIFTS[subsampling]
+    return h > 0 and w > 0 and h % (1 << sy) == 0 and w % (1 << sx) == 0
+
+
+class YuvFrame:
+    """One planar frame of `depth` 8 | 10 | 12 bits at `subsampling` '420' | '422' | '444': planes y (h, w) and u, v of (h/2, w/2), (h, w/2)
+    or (h, w) on one device -- torch.uint8 at depth 8, torch.int16 above it: the 16 bits of the container with the value in the LOW bits,
+    as in yuv420p10le / yuv422p12le.  numpy arrays become CPU tensors (uint16 arrays are reinterpreted, not copied).  Both sides are even
+    for 4:2:0, the width for 4:2:2.  A CPU frame with a code outside 0 .. 2^depth - 1 raises ValueError; frames on a device are not scanned:
+    the kernels mask every sample they read to `depth` bits (as does the defining expression)."""
+
+    def __init__(self, y, u, v, depth=8, subsampling='420'):
+        _check2(depth, subsampling)
+
+        def t(a):
+            if isinstance(a, torch.Tensor):
+                return a
+            a = np.asarray(a)
+            return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a)
+        y, u, v = t(y), t(u), t(v)
+        dtype = torch.uint8 if depth == 8 else torch.int16
+        if y.dim() != 2 or y.dtype != dtype:
+            raise ValueError(f'y is an (h, w) {dtype} plane at depth {depth}, got {tuple(y.shape)} {y.dtype}')
+        h, w = int(y.shape[0]), int(y.shape[1])
+        if not _extent_ok(h, w, subsampling):
+            raise ValueError(f'a {subsampling} frame has positive sides, even where the chroma is subsampled, got {h} x {w}')
+        sx, sy = SHIFTS[subsampling]
+        cs = (h >> sy, w >> sx)
+        if any(p.dtype != dtype or tuple(p.shape) != cs or p.device != y.device for p in (u, v)):
+            raise ValueError(f'u and v are {cs} {dtype} planes on the device of y')
+        if depth > 8 and y.device.type == 'cpu':
+            for name, p in zip('yuv', (y, u, v)):
+                if int(p.min()) < 0 or int(p.max()) > (1 << depth) - 1:
+                    raise ValueError(f'plane {name} holds codes outside 0 .. {(1 << depth) - 1} (the value belongs in the low {depth} bits)')
+        self.y, self.u, self.v, self.depth, self.subsampling, self.h, self.w = y, u, v, depth, subsampling, h, w
+
+    @property
+    def device(self):
+        return self.y.device
+
+    @property
+    def size(self):
+        return (self.h, self.w)
+
+    def planes(self):
+        """The planes in file order: (y, u, v)."""
+        return (self.y, self.u, self.v)
+
+    def to(self, device, non_blocking=False):
+        if torch.device(device) == self.device:
+            return self
+        fr = YuvFrame.__new__(YuvFrame)                      # (the planes were checked when this frame was made)
+        fr.__dict__.update(self.__dict__)
+        fr.y, fr.u, fr.v = (p.to(device, non_blocking=non_blocking) for p in self.planes())
+        return fr
+
+    def cpu(self):
+        return self.to('cpu')
+
+
+def frame_bytes2(width, height, subsampling='420', depth=8):
+    sx, sy = SHIFTS[subsampling]
+    return (width * height + 2 * (width >> sx) * (height >> sy)) * (1 if depth == 8 else 2)
+
+
+def read_yuv(path, width, height, subsampling='420', depth=8, frames=None):
+    """A raw planar .yuv file of `width` x `height` frames (yuv420p, yuv422p10le, yuv444p12le ...) -> list of YuvFrame on the CPU (all of
+    them, or the first `frames`).  As read_yuv420: ONE buffer, pinned when a GPU is there, the planes views of it.  ValueError: sides that do
+    not fit the subsampling, a file size that is not a whole number of frames, an unknown depth / subsampling, a code beyond the depth."""
+    _check2(depth, subsampling)
+    if not _extent_ok(height, width, subsampling):
+        raise ValueError(f'read_yuv: {width} x {height} does not fit subsampling {subsampling}')
+    per = frame_bytes2(width, height, subsampling, depth)
+    size = os.path.getsize(path)
+    if size == 0 or size % per:
+        raise ValueError(f'read_yuv: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
+    n = size // per if frames is None else min(int(frames), size // per)
+    if n <= 0:
+        raise ValueError(f'read_yuv: frames={frames}')
+    buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    with open(path, 'rb') as f:
+        got = f.readinto(buf.numpy())
+    if got != n * per:
+        raise ValueError(f'read_yuv: short read of {path}')
+    sx, sy = SHIFTS[subsampling]
+    bps = 1 if depth == 8 else 2
+    ny, nc = width * height * bps, (width >> sx) * (height >> sy) * bps
+
+    def plane(b, h, w):
+        return (b if depth == 8 else b.view(torch.int16)).view(h, w)
+    out = []
+    for i in range(n):
+        fr = buf[i * per:(i + 1) * per]
+        out.append(YuvFrame(plane(fr[:ny], height, width), plane(fr[ny:ny + nc], height >> sy, width >> sx),
+                            plane(fr[ny + nc:], height >> sy, width >> sx), depth, subsampling))
+    return out
+
+
+def write_yuv(frames, path, append=False):
+    """Write YuvFrames (any device) to a raw planar .yuv file, one after the other; 16-bit samples little-endian."""
+    with open(path, 'ab' if append else 'wb') as f:
+        for fr in frames:
+            for p in fr.planes():
+                a = p.cpu().contiguous().numpy()
+                f.write((a if a.dtype == np.uint8 else a.astype('<i2', copy=False)).tobytes())
+
+
+# ----------------------------------------------------------------------------------------------- the defining expressions (CPU, fp32)
+def _scales2(depth, range):
+    """fp32 luma offset, luma scale, chroma offset, chroma scale and the largest code (all integers: exact)."""
+    s, peak = float(1 << (depth - 8)), float((1 << depth) - 1)
+    vals = (16.0 * s, 219.0 * s, 128.0 * s, 224.0 * s) if range == 'limited' else (0.0, peak, 128.0 * s, peak)
+    return tuple(_f32(k) for k in vals) + (peak,)
+
+
+def _codes_f32(p, depth):
+    """A plane's codes as fp32 (exact); 16-bit containers are masked to `depth` bits, as the kernels do."""
+    return p.to(torch.float32) if p.dtype == torch.uint8 else (p.to(torch.int32) & ((1 << depth) - 1)).to(torch.float32)
+
+
+def _upsample_axis(c, dim, chroma, left):
+    """fp32 chroma, one subsampled axis doubled.  'nearest': sample x >> 1.  'bilinear', centre: 3/4 of the sample a pixel lies in and 1/4 of
+    the neighbour on the pixel's side; left: position 2k takes sample k, position 2k + 1 takes (c[k] + c[k + 1]) / 2.  Indices are clamped
+    at the plane's edges; the weights are dyadic and the codes small integers: exact in fp32."""
+    if chroma == 'nearest':
+        return c.repeat_interleave(2, dim)
+    n = c.shape[dim]
+    i = torch.arange(n)
+    nxt = c.index_select(dim, (i + 1).clamp(max=n - 1))
+    if left:
+        even, odd = c, (c + nxt) * 0.5
+    else:
+        prev = c.index_select(dim, (i - 1).clamp(min=0))
+        even, odd = c * 0.75 + prev * 0.25, c * 0.75 + nxt * 0.25
+    return torch.stack([even, odd], dim + 1).flatten(dim, dim + 1)
+
+
+def _upsample2(c, depth, subsampling, siting, chroma):
+    sx, sy = SHIFTS[subsampling]
+    c = _codes_f32(c, depth)
+    if sy:
+        c = _upsample_axis(c, 0, chroma, False)              # vertically the chroma is centred for both sitings
+    if sx:
+        c = _upsample_axis(c, 1, chroma, siting == 'left')
+    return c
+
+
+def yuv_to_rgb_expr2(y, u, v, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', chroma='bilinear'):
+    """THE DEFINITION of lvae_image_yuv_to_f32 inside a frame's extent: the planes of a YuvFrame on the CPU -> (3, h, w) fp32 RGB in
+    [0, 1].  At depth 8, '420', 'center' and the matrices of yuv_to_rgb_expr it is that expression, bit for bit."""
+    _check2(depth, subsampling, siting, matrix, range, chroma)
+    _, _, _, a, b, d, e = (_f32(k) for k in COEF[matrix])
+    yo, ys, co, cs, _ = _scales2(depth, range)
+    yn = (_codes_f32(y, depth) - yo) / ys
+    cb = (_upsample2(u, depth, subsampling, siting, chroma) - co) / cs
+    cr = (_upsample2(v, depth, subsampling, siting, chroma) - co) / cs
+    r = yn + a * cr
+    bl = yn + b * cb
+    g = (yn - d * cb) - e * cr
+    return torch.stack([r, g, bl]).clamp(0, 1)
+
+
+def _downsample2(c, subsampling, siting):
+    """Per-pixel fp32 colour differences (h, w) -> the chroma plane's; the order of the sums is part of the definition."""
+    sx, sy = SHIFTS[subsampling]
+    if not sx:
+        return c
+    if siting == 'left':
+        k = torch.arange(c.shape[1] // 2)
+        prev = c.index_select(1, (2 * k - 1).clamp(min=0))
+        h = ((prev + c[:, 1::2]) + (c[:, 0::2] + c[:, 0::2])) * 0.25
+        return (h[0::2] + h[1::2]) * 0.5 if sy else h
+    if sy:
+        return ((c[0::2, 0::2] + c[0::2, 1::2]) + (c[1::2, 0::2] + c[1::2, 1::2])) * 0.25
+    return (c[:, 0::2] + c[:, 1::2]) * 0.5
+
+
+def rgb_to_yuv_expr2(x, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited'):
+    """THE DEFINITION of lvae_image_f32_to_yuv: (3, h, w) fp32 RGB on the CPU (sides that fit the subsampling) -> planes y, u, v of codes
+    (uint8 at depth 8, int16 above).  Values are clamped to [0, 1] first and a NaN counts as 0; codes are rint (ties to even) of
+    value * scale + offset, clamped to 0 .. 2^depth - 1."""
+    _check2(depth, subsampling, siting, matrix, range)
+    kr, kg, kb, a, b, _, _ = (_f32(k) for k in COEF[matrix])
+    yo, ys, co, cs, peak = _scales2(depth, range)
+    x = x.to(torch.float32)
+    x = torch.where(x > 0, x, torch.zeros((), dtype=torch.float32))
+    x = torch.where(x < 1, x, torch.ones((), dtype=torch.float32))
+    r, g, bl = x[0], x[1], x[2]
+    yn = (kr * r + kg * g) + kb * bl
+    cb, cr = (bl - yn) / b, (r - yn) / a
+    code = lambda t: torch.round(t).clamp(0, peak).to(torch.uint8 if depth == 8 else torch.int16)
+    return (code(yn * ys + yo), code(_downsample2(cb, subsampling, siting) * cs + co), code(_downsample2(cr, subsampling, siting) * cs + co))
+
+
+# ----------------------------------------------------------------------------------------------- batches and the kernel path
+def _as_frame2(f):
+    if not isinstance(f, YuvFrame):
+        raise ValueError(f'expected a YuvFrame, got {type(f).__name__}')
+    return f
+
+
+def _plane_args2(frames):
+    """Host arrays of plane addresses / row strides IN SAMPLES of device frames of one depth and subsampling, as lvae_image_yuv_to_f32 /
+    lvae_image_f32_to_yuv take them; the second item keeps alive what had to be made contiguous."""
+    n = len(frames)
+    rows_ok = lambda p: p.stride(1) == 1 and p.stride(0) >= p.shape[1]
+    ps = [[p if rows_ok(p) else p.contiguous() for p in (getattr(f, k) for f in frames)] for k in 'yuv']
+    ptr = lambda q: (ctypes.c_void_p * n)(*[p.data_ptr() for p in q])
+    row = lambda q: (ctypes.c_long * n)(*[p.stride(0) for p in q])
+    hw = (ctypes.c_int * (2 * n))(*[v for f in frames for v in f.size])
+    return (ptr(ps[0]), ptr(ps[1]), ptr(ps[2]), row(ps[0]), row(ps[1]), row(ps[2]), hw), ps
+
+
+class YuvBatch:
+    """B YuvFrames of one depth and subsampling on one device that share a canvas (H, W) >= their own sizes, with the parameters of their
+    conversion: what CodecBase.compress_yuv hands to compress_batch as `u8=` (the Yuv420Batch of this path).  `shape` is the fp32 tensor's;
+    `fill(dst, start, n)` converts frames start .. start + n straight into `dst` -- an (n, 3, H, W) fp32 view of an encode plan's input --
+    with one launch on the current stream."""
+
+    def __init__(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
+        fs = [_as_frame2(f) for f in frames]
+        if not fs:
+            raise ValueError('no frames')
+        self.depth, self.subsampling = fs[0].depth, fs[0].subsampling
+        if any((f.depth, f.subsampling) != (self.depth, self.subsampling) for f in fs):
+            raise ValueError('the frames of one call share depth and subsampling')
+        _check2(self.depth, self.subsampling, siting, matrix, range, chroma)
+        self.sizes = [f.size for f in fs]
+        H, W = _canvas(self.sizes, div)
+        self.shape = (len(fs), 3, H, W)
+        self.device = torch.device(device)
+        self.matrix, self.range, self.chroma, self.siting = matrix, range, chroma, siting
+        self.frames = [f.to(self.device, non_blocking=True) for f in fs]      # the file's bytes cross the bus, unpadded
+
+    def fill(self, dst, start=0, n=None):
+        from .. import _native
+        n = len(self.frames) - start if n is None else n
+        _, _, H, W = self.shape
+        assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
+        args, keep = _plane_args2(self.frames[start:start + n])
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _native.check(_native.lib().lvae_image_yuv_to_f32(
+                *args, n, self.depth, SUBSAMPLINGS.index(self.subsampling), SITINGS.index(self.siting), MATRICES2.index(self.matrix),
+                RANGES.index(self.range), CHROMA.index(self.chroma), dst.data_ptr(), dst.stride(0) if n > 1 else 3 * H * W, H, W, st),
+                'image_yuv_to_f32')
+        del keep
+
+
+def to_rgb01_any(frames, div=1, device=None, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
+    """to_rgb01 for a list of YuvFrame of one depth and subsampling -> ((B, 3, H, W) fp32 RGB in [0, 1], [(h, w)]).  siting: 'center' |
+    'left' (where the chroma samples lie horizontally; see the module docstring); matrix also 'bt2020'.  CPU frames with device=None: the
+    defining expression on the host.  Otherwise one upload of each frame's bytes and one kernel launch for the batch."""
+    fs = [_as_frame2(f) for f in frames]
+    if not fs:
+        raise ValueError('no frames')
+    if device is None and all(f.device.type == 'cpu' for f in fs):
+        if any((f.depth, f.subsampling) != (fs[0].depth, fs[0].subsampling) for f in fs):
+            raise ValueError('the frames of one call share depth and subsampling')
+        _check2(fs[0].depth, fs[0].subsampling, siting, matrix, range, chroma)
+        sizes = [f.size for f in fs]
+        H, W = _canvas(sizes, div)
+        out = []
+        for f in fs:
+            x = yuv_to_rgb_expr2(f.y, f.u, f.v, f.depth, f.subsampling, siting, matrix, range, chroma)
+            out.append(F.pad(x.unsqueeze(0), (0, W - f.w, 0, H - f.h), mode='replicate')[0] if f.size != (H, W) else x)
+        return torch.stack(out), sizes
+    if device is None:
+        device = next(f.device for f in fs if f.device.type != 'cpu')
+    batch = YuvBatch(fs, div, device, matrix, range, chroma, siting)
+    out = torch.empty(batch.shape, dtype=torch.float32, device=batch.device)
+    batch.fill(out)
+    return out, batch.sizes
+
+
+def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited'):
+    """from_rgb01 for YuvFrames: fp32 RGB images in [0, 1] -> a list of YuvFrame of `depth` and `subsampling` on the same device, the
+    chroma sampled for `siting`.  x, sizes: as in from_rgb01; extents that do not fit the subsampling raise ValueError.  Device tensors: one
+    kernel launch for the batch on the current stream; CPU tensors: the defining expression."""
+    from .views import items, strided_batch
+    _check2(depth, subsampling, siting, matrix, range)
+    xs = items(x, 'x')
+    if sizes is not None:
+        if len(sizes) != len(xs):
+            raise ValueError(f'from_rgb01_any: {len(sizes)} sizes for {len(xs)} images')
+        xs = [v[:, :h, :w] for v, (h, w) in zip(xs, sizes)]
+    if not xs or any(v.shape[0] != 3 or v.shape[1] == 0 or v.shape[2] == 0 for v in xs):
+        raise ValueError('from_rgb01_any: expected 3-channel, non-empty images')
+    if any(not _extent_ok(int(v.shape[1]), int(v.shape[2]), subsampling) for v in xs):
+        raise ValueError(f'from_rgb01_any: sizes {[tuple(v.shape[1:]) for v in xs]} do not fit subsampling {subsampling}')
+    device = xs[0].device
+    if device.type == 'cpu':
+        return [YuvFrame(*rgb_to_yuv_expr2(v, depth, subsampling, siting, matrix, range), depth, subsampling) for v in xs]
+    from .. import _native
+    B = len(xs)
+    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
+    hmax, wmax = max(h for h, _ in hw), max(w for _, w in hw)
+    sx, sy = SHIFTS[subsampling]
+    with torch.cuda.device(device):
+        keep, px, (s_img, s_plane, s_row) = strided_batch(xs, hmax, wmax, device)
+        span = (hmax - 1) * s_row + wmax             # views whose common strides do not hold the largest extent are packed instead
+        if s_row < wmax or s_plane < span or (B > 1 and s_img < 2 * s_plane + span):
+            keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in xs], hmax, wmax, device)
+        new = lambda *s: torch.empty(*s, dtype=torch.uint8 if depth == 8 else torch.int16, device=device)
+        outs = [YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling) for h, w in hw]
+        args, _ = _plane_args2(outs)
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _native.check(_native.lib().lvae_image_f32_to_yuv(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[6], B, depth,
+                                                          SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix),
+                                                          RANGES.index(range), *args[:6], st), 'image_f32_to_yuv')
     del keep
     return outs

@@ -9,6 +9,8 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py region BITS/ CROPS/ --box 100 200 512 512          # y0 x0 h w of every tiled file, nothing else decoded
     python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 1920 1080 [--format nv12] [--frames N]   # raw 8-bit 4:2:0: one .bits per frame
     python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv [--format nv12]
+    python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 1920 1080 --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]
+    python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]   # yuv420p10le ...
 
 Images whose sizes padded to the model's stride agree are coded as batches of up to --batch (lvae.evaluation.batch_same_size).  A .bits
 file is what compress_file writes; decode names every PNG after its .bits file.  --synthetic (on decode: seeded weights only) needs no
@@ -16,7 +18,10 @@ checkpoint on disk.  With --tile every image is coded on its own as a tiled cont
 --batch at a time, whatever the image's size); decode recognises such files by their magic, region decodes only the tiles a box touches.
 encode-yuv / decode-yuv code the frames of a raw .yuv file as an intra-frame coder (CodecBase.compress_yuv420 / decompress_yuv420): frame
 k becomes BITS/frame<k>.bits, a file compress_file could have written; --matrix / --range / --chroma are NOT stored, give decode-yuv the
-same --matrix and --range.  With --synthetic N, encode-yuv first writes N seeded frames of --size to IN.yuv."""
+same --matrix and --range.  With --synthetic N, encode-yuv first writes N seeded frames of --size to IN.yuv.  --depth 10 | 12,
+--subsampling 422 | 444, --siting left or --matrix bt2020 select planar files with 16-bit little-endian samples above 8 bits
+(CodecBase.compress_yuv / decompress_yuv); none of them is stored either: decode-yuv needs the encoder's --depth and --siting too (it may
+ask for another depth or subsampling on purpose: the reconstruction is fp32)."""
 import argparse
 import os
 import sys
@@ -79,34 +84,44 @@ def decode(model, src, dst, batch, box=None):
     print(f'decoded {len(paths) + len(tiled)} files')
 
 
-def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour):
-    from lvae.utils.yuv import read_yuv420
-    fs = read_yuv420(src, size[0], size[1], fmt, frames=frames)
+def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None):
+    from lvae.utils.yuv import read_yuv, read_yuv420
+    if layout is None:
+        fs, compress = read_yuv420(src, size[0], size[1], fmt, frames=frames), model.compress_yuv420
+    else:
+        fs = read_yuv(src, size[0], size[1], layout['subsampling'], layout['depth'], frames=frames)
+        compress = lambda chunk, **kw: model.compress_yuv(chunk, siting=layout['siting'], **kw)
     total = 0
     for o in range(0, len(fs), batch):
-        blobs = model.compress_yuv420(fs[o:o + batch], **colour, **({'lmb': lmb} if lmb is not None else {}))
+        blobs = compress(fs[o:o + batch], **colour, **({'lmb': lmb} if lmb is not None else {}))
         for k, blob in enumerate(blobs, o):
             (Path(dst) / f'frame{k:05d}.bits').write_bytes(blob)
             total += len(blob)
     print(f'encoded {len(fs)} frames -> {total} bytes')
 
 
-def decode_yuv(model, src, dst, fmt, batch, colour):
-    from lvae.utils.yuv import write_yuv420
+def decode_yuv(model, src, dst, fmt, batch, colour, layout=None):
+    from lvae.utils.yuv import write_yuv, write_yuv420
     paths = sorted(Path(src).glob('*.bits'))
     for o in range(0, len(paths), batch):
-        frames = model.decompress_yuv420([p.read_bytes() for p in paths[o:o + batch]], fmt=fmt, matrix=colour['matrix'], range=colour['range'])
-        write_yuv420(frames, dst, append=o > 0)
+        blobs = [p.read_bytes() for p in paths[o:o + batch]]
+        if layout is None:
+            write_yuv420(model.decompress_yuv420(blobs, fmt=fmt, matrix=colour['matrix'], range=colour['range']), dst, append=o > 0)
+        else:
+            write_yuv(model.decompress_yuv(blobs, matrix=colour['matrix'], range=colour['range'], **layout), dst, append=o > 0)
     print(f'decoded {len(paths)} frames')
 
 
-def synthetic_yuv(path, n, size, fmt, colour):
+def synthetic_yuv(path, n, size, fmt, colour, layout=None):
     """N seeded frames of size (w, h) as a raw .yuv file: seeded RGB images through the defining host conversion."""
     import seeded_init
-    from lvae.utils.yuv import from_rgb01, write_yuv420
+    from lvae.utils.yuv import from_rgb01, from_rgb01_any, write_yuv, write_yuv420
     w, h = size
     rgb = [torch.from_numpy(seeded_init.synthetic_image_u8(h, w, 300 + i)).permute(2, 0, 1).float().div(255) for i in range(n)]
-    write_yuv420(from_rgb01(rgb, fmt=fmt, matrix=colour['matrix'], range=colour['range']), path)
+    if layout is None:
+        write_yuv420(from_rgb01(rgb, fmt=fmt, matrix=colour['matrix'], range=colour['range']), path)
+    else:
+        write_yuv(from_rgb01_any(rgb, matrix=colour['matrix'], range=colour['range'], **layout), path)
 
 
 @torch.no_grad()
@@ -126,23 +141,31 @@ def main():
     ap.add_argument('--size', type=int, nargs=2, default=None, metavar=('W', 'H'), help='encode-yuv: the frame size of the raw file')
     ap.add_argument('--format', type=str, default='i420', choices=['i420', 'nv12'], help='encode-yuv / decode-yuv: the plane layout of the raw file')
     ap.add_argument('--frames', type=int, default=None, help='encode-yuv: code only the first N frames')
-    ap.add_argument('--matrix', type=str, default='bt709', choices=['bt601', 'bt709'])
+    ap.add_argument('--matrix', type=str, default='bt709', choices=['bt601', 'bt709', 'bt2020'])
+    ap.add_argument('--depth', type=int, default=8, choices=[8, 10, 12], help='encode-yuv / decode-yuv: bits per sample (above 8: 16-bit little-endian words)')
+    ap.add_argument('--subsampling', type=str, default='420', choices=['420', '422', '444'], help='encode-yuv / decode-yuv: the chroma subsampling')
+    ap.add_argument('--siting', type=str, default='center', choices=['center', 'left'], help="encode-yuv / decode-yuv: where the chroma samples lie; 'left' is H.264 / HEVC co-sited chroma")
     ap.add_argument('--range', type=str, default='limited', choices=['limited', 'full'])
     ap.add_argument('--chroma', type=str, default='bilinear', choices=['nearest', 'bilinear'], help='encode-yuv: the chroma upsampling filter')
     args = ap.parse_args()
     if args.command in ('encode-yuv', 'decode-yuv'):
         colour = dict(matrix=args.matrix, range=args.range, chroma=args.chroma)
+        layout = None                                        # the 8-bit 4:2:0 centre-sited path unless one option asks for more
+        if (args.depth, args.subsampling, args.siting) != (8, '420', 'center') or args.matrix == 'bt2020':
+            if args.format != 'i420':
+                ap.error('--depth / --subsampling / --siting / --matrix bt2020 apply to planar files (--format i420)')
+            layout = dict(depth=args.depth, subsampling=args.subsampling, siting=args.siting)
         if args.command == 'encode-yuv':
             if args.size is None:
                 ap.error('encode-yuv needs --size W H')
             os.makedirs(args.dst, exist_ok=True)
             if args.synthetic:
-                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour)
+                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour, layout)
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            encode_yuv(model, args.src, args.dst, args.size, args.format, args.frames, args.lmb, args.batch, colour)
+            encode_yuv(model, args.src, args.dst, args.size, args.format, args.frames, args.lmb, args.batch, colour, layout)
         else:
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            decode_yuv(model, args.src, args.dst, args.format, args.batch, colour)
+            decode_yuv(model, args.src, args.dst, args.format, args.batch, colour, layout)
         return
     os.makedirs(args.dst, exist_ok=True)
     if args.synthetic and args.command == 'encode':

@@ -2,7 +2,9 @@
 (B, 3, H, W) tensor at 12 bytes per pixel, upload it) against the byte path (upload 1.5 bytes per pixel, lvae_image_yuv420_to_f32 /
 lvae_image_f32_to_yuv420 on the device), and one evaluation step (lvae.evaluation.yuv_evaluate) against the same step with the
 conversions and the squared errors on the host.  Workloads: 8 frames of 512 x 768 and 2 of 1080 x 1920 (which pad to 1088 x 1920); seeded
-synthetic frames, BT.709 limited range, bilinear chroma.
+synthetic frames, BT.709 limited range, bilinear chroma.  Rows (a) - (c) are repeated for planar 10-bit frames (utils.yuv.YuvFrame, centre
+siting; to_rgb01_any / from_rgb01_any, lvae_image_yuv_to_f32 / lvae_image_f32_to_yuv): 2 frames of 1080 x 1920 at 4:2:0 and 8 of 512 x 768 at
+4:4:4, against the same numpy host conversion on 16-bit samples.
   (a) host_in  : numpy fp32 conversion + edge padding to multiples of 64, torch.from_numpy(...).to(device)
   (b) yuv_in   : to_rgb01(frames, div=64, device)             -- frames as read_yuv420 leaves them (views of one pinned buffer)
   (c) host_out : x.cpu(), then the numpy fp32 forward conversion to I420 bytes
@@ -28,6 +30,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 WORKLOADS = {'b8_512x768': (8, 512, 768), 'b2_1080x1920': (2, 1080, 1920)}
+HBD_WORKLOADS = {'b2_1080x1920_10bit_420': (2, 1080, 1920, 10, '420'), 'b8_512x768_10bit_444': (8, 512, 768, 10, '444')}
 KR, KB = 0.2126, 0.0722
 KG = 1 - KR - KB
 F = np.float32
@@ -71,11 +74,40 @@ def host_to_yuv(x, sizes):
     return out
 
 
+def host_to_rgb_hbd(frames, div):
+    """host_to_rgb for planar frames of more than 8 bits (16-bit samples), 4:2:0 or 4:4:4, centre siting."""
+    out = []
+    for f in frames:
+        s = F(1 << (f.depth - 8))
+        y, u, v = f.y.numpy(), f.u.numpy(), f.v.numpy()
+        up = _up if f.subsampling == '420' else (lambda c: c.astype(F))
+        yn = (y.astype(F) - F(16) * s) / (F(219) * s)
+        cb, cr = (up(u) - F(128) * s) / (F(224) * s), (up(v) - F(128) * s) / (F(224) * s)
+        rgb = np.stack([yn + F(2 * (1 - KR)) * cr, yn - F(2 * KB * (1 - KB) / KG) * cb - F(2 * KR * (1 - KR) / KG) * cr, yn + F(2 * (1 - KB)) * cb])
+        np.clip(rgb, 0, 1, out=rgb)
+        h, w = y.shape
+        out.append(np.pad(rgb, ((0, 0), (0, -h % div), (0, -w % div)), mode='edge'))
+    return torch.from_numpy(np.stack(out))
+
+
+def host_to_yuv_hbd(x, sizes, depth, sub):
+    """host_to_yuv with codes of `depth` bits in 16-bit arrays, 4:2:0 (2x2 mean) or 4:4:4."""
+    out, s = [], F(1 << (depth - 8))
+    for xi, (h, w) in zip(x.numpy(), sizes):
+        r, g, b = np.clip(np.nan_to_num(xi[:, :h, :w]), 0, 1)
+        yn = F(KR) * r + F(KG) * g + F(KB) * b
+        cb, cr = (b - yn) / F(2 * (1 - KB)), (r - yn) / F(2 * (1 - KR))
+        m4 = (lambda c: (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2]) * F(0.25)) if sub == '420' else (lambda c: c)
+        q = lambda t: np.clip(np.rint(t), 0, (1 << depth) - 1).astype(np.int16)
+        out.append((q(yn * (F(219) * s) + F(16) * s), q(m4(cb) * (F(224) * s) + F(128) * s), q(m4(cr) * (F(224) * s) + F(128) * s)))
+    return out
+
+
 def main():
     import bench
     import seeded_init
     from lvae.evaluation import yuv_evaluate
-    from lvae.utils.yuv import from_rgb01, read_yuv420, to_rgb01, write_yuv420
+    from lvae.utils.yuv import from_rgb01, from_rgb01_any, read_yuv, read_yuv420, to_rgb01, to_rgb01_any, write_yuv, write_yuv420
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
@@ -143,6 +175,35 @@ def main():
                 box['f'] = (sse, [len(b) for b in bodies])
             row.update(alternate({'eval_step': eval_step, 'eval_step_host': eval_step_host}))
             row['eval_step_host_over_eval_step'] = round(row['eval_step_host']['median'] / row['eval_step']['median'], 2)
+        res[name] = row
+    for name, (B, H, W, depth, sub) in HBD_WORKLOADS.items():
+        path = tmp / f'{name}.yuv'
+        rgb = [torch.from_numpy(seeded_init.synthetic_image_u8(H, W, seed=1000 + i)).permute(2, 0, 1).float().div(255) for i in range(B)]
+        write_yuv(from_rgb01_any(rgb, depth=depth, subsampling=sub), path)
+        frames = read_yuv(path, W, H, sub, depth)
+        sizes = [(H, W)] * B
+        box, row = {}, {}
+
+        def host_in():
+            box['a'] = host_to_rgb_hbd(frames, 64).to(dev)
+
+        def yuv_in():
+            box['b'] = to_rgb01_any(frames, div=64, device=dev)[0]
+        row.update(alternate({'host_in': host_in, 'yuv_in': yuv_in}))
+        row['in_max_abs_diff'] = float((box['a'] - box['b']).abs().max())
+        assert row['in_max_abs_diff'] <= 1e-6
+        row['host_in_over_yuv_in'] = round(row['host_in']['median'] / row['yuv_in']['median'], 2)
+        x = box['b']
+
+        def host_out():
+            box['c'] = host_to_yuv_hbd(x.cpu(), sizes, depth, sub)
+
+        def yuv_out():
+            box['d'] = [[p.cpu() for p in f.planes()] for f in from_rgb01_any(x, sizes, depth=depth, subsampling=sub)]
+        row.update(alternate({'host_out': host_out, 'yuv_out': yuv_out}))
+        row['out_max_code_diff'] = max(int(np.abs(c.astype(np.int64) - d.numpy().astype(np.int64)).max()) for cs, ds in zip(box['c'], box['d']) for c, d in zip(cs, ds))
+        assert row['out_max_code_diff'] <= 1
+        row['host_out_over_yuv_out'] = round(row['host_out']['median'] / row['yuv_out']['median'], 2)
         res[name] = row
     print(json.dumps(res))
 
