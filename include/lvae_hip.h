@@ -575,7 +575,7 @@ int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uint8_t* const
 /* ---- Planar YUV frames of 8, 10 or 12 bits at 4:2:0 / 4:2:2 / 4:4:4 (csrc/yuv_hbd_io.hip): the generalisation of the three entries above,
  * which keep their behaviour; the conventions (HOST arrays of DEVICE plane addresses, hw, 16 frames per launch, fp32 side, alignment) are
  * theirs.  depth: 8, 10 or 12.  A sample is a byte at depth 8 and otherwise a 16-bit word with the value in its LOW bits (yuv420p10le,
- * yuv422p12le ...; P010-style layouts with the value in the high bits are not supported); every sample read is masked to `depth` bits.
+ * yuv422p12le ...; P010-style layouts with the value in the high bits: the two entries further down); every sample read is masked to `depth` bits.
  * Row strides are in SAMPLES.  subsampling: LVAE_YUV_SUB_420: chroma planes of (h/2, w/2), h and w even; LVAE_YUV_SUB_422: (h, w/2), w even;
  * LVAE_YUV_SUB_444: (h, w), any extent.  Planar only: u[b] and v[b] are separate planes.  siting: LVAE_YUV_SITING_CENTER: a chroma sample
  * lies in the middle of the luma samples it covers (JPEG / MPEG-1); LVAE_YUV_SITING_LEFT: horizontally it lies ON the even luma column and
@@ -611,6 +611,27 @@ int lvae_image_f32_to_yuv(const float* src, long src_img, long src_plane, long s
 int lvae_sse_u16(const uint16_t* const* a, const long* a_row, const uint16_t* const* b, const long* b_row, const int* hw, int n,
                  uint64_t* out, void* stream);
 /* These three were added without a change to lvae_abi_version() either. */
+
+/* ---- Semi-planar frames of 10 or 12 bits at 4:2:0 / 4:2:2 (P010, P012, P210, P212: what hardware video decoders deliver; the SP variants of
+ * csrc/yuv_hbd_io.hip), with the conventions of the two planar entries above.  A frame is a luma plane y[b] of (h, w) 16-bit words and ONE
+ * chroma plane uv[b] of (h/2, w/2) (LVAE_YUV_SUB_420) or (h, w/2) (LVAE_YUV_SUB_422) chroma pixels, a chroma pixel being two neighbouring words,
+ * U then V: a UV row of cw chroma pixels has 2 cw samples.  Row strides are in SAMPLES (uv_row >= w).  A sample's code is the HIGH `depth`
+ * bits of its word: word >> (16 - depth) on input, whatever the low bits hold; code << (16 - depth) on output, low bits zero.  depth: 10 or
+ * 12; siting, matrix, range, chroma: as above; w is even, and h for 4:2:0.  LVAE_YUV_LAYOUT_* names the two plane layouts for callers (the
+ * sequence container of lvae/utils/yuvseq.py records one); no entry takes it.
+ * The contract is bit equality with the planar path: lvae_image_yuvsp_to_f32 gives what lvae_image_yuv_to_f32 gives for the deinterleaved,
+ * shifted planes (replicate padding included), and lvae_image_f32_to_yuvsp writes the interleaved, shifted codes of lvae_image_f32_to_yuv.
+ * The U and V of a chroma pixel leave as one 4-byte store (two chroma pixels as one 8-byte store) where the address allows; nothing
+ * outside a plane's extent is written.
+ * -22 before any HIP call: as above, with a depth other than 10 / 12 or a subsampling other than 4:2:0 / 4:2:2 among the unsupported values.
+ * Added without a change to lvae_abi_version(). */
+enum { LVAE_YUV_LAYOUT_PLANAR = 0, LVAE_YUV_LAYOUT_SEMIPLANAR = 1 };
+int lvae_image_yuvsp_to_f32(const uint16_t* const* y, const uint16_t* const* uv, const long* y_row, const long* uv_row, const int* hw, int B,
+                            int depth, int subsampling, int siting, int matrix, int range, int chroma, float* dst, long dst_img, int H, int W,
+                            void* stream);
+int lvae_image_f32_to_yuvsp(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int depth,
+                            int subsampling, int siting, int matrix, int range, uint16_t* const* y, uint16_t* const* uv, const long* y_row,
+                            const long* uv_row, void* stream);
 
 /* ---- Tiled images (csrc/tile_stitch.hip; lvae/utils/tiling.py states the grid rule and the weights): a window of an (h, w) image from
  * the fp32 reconstructions of the tiles that cover it.  The tiles form a rows x cols grid of common extent (th, tw) with origins oy[rows],

@@ -12,6 +12,12 @@
 // the filtered value is an integer of at most 16 * 4095 and exact in any order.  f32_to_yuv: one lane owns a block of (2 or 1 rows) x 4
 // columns; left siting needs the column before the block, which is one more scalar load per row and plane.  sse_u16: one lane owns 8
 // consecutive samples of one row of both planes; 64-bit integer sums from the lane to the one atomic per wave.
+//
+// Semi-planar frames of 10 / 12 bits (P010, P012, P210, P212: lvae_image_yuvsp_to_f32 / lvae_image_f32_to_yuvsp) are one more template
+// parameter, SP, of the same two kernels: a sample's code is the HIGH `depth` bits of its word (word >> (16 - depth) in, code << (16 - depth)
+// out) and a chroma pixel is two neighbouring words, U then V, of one plane.  The host passes the UV plane as u, the same plane one sample
+// on as v, and the UV row stride for both, so the only new addressing is the chroma column c at sample 2c.  A lane's two chroma pixels are
+// 4 consecutive words: one 8-byte access where the address allows.  The arithmetic is the planar variants', hence so are the bits.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -31,7 +37,8 @@ struct PlaneBatch { PlaneDesc d[HBD_CHUNK]; };
 
 // the fp32 constants of a conversion: the matrix (a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg, the literals of
 // lvae/utils/yuv.py), the range at this depth (all integers, exact) and the sample mask 2^depth - 1 (peak is the same number as a float)
-struct YuvParams { float kr, kg, kb, a, b, d, e, yo, ys, co, cs, peak; unsigned mask; };
+// -- and, for the semi-planar variants, the position 16 - depth of a code inside its word
+struct YuvParams { float kr, kg, kb, a, b, d, e, yo, ys, co, cs, peak; unsigned mask, shift; };
 
 YuvParams yuv_params(int matrix, int range, int depth) {
     YuvParams k = matrix == LVAE_YUV_BT601   ? YuvParams{0.299f, 0.587f, 0.114f, 1.402f, 1.772f, 0.344136286f, 0.714136286f}
@@ -45,6 +52,7 @@ YuvParams yuv_params(int matrix, int range, int depth) {
     k.cs = full ? peak : 224.0f * s;
     k.peak = peak;
     k.mask = (1u << depth) - 1u;
+    k.shift = 16u - (unsigned)depth;                         // (read by the SP variants only, whose depth is 10 or 12)
     return k;
 }
 
@@ -54,8 +62,9 @@ __device__ __forceinline__ float clamp01(float x) {          // NaN -> 0: both c
 }
 
 // 4 consecutive samples: one 4-byte (8-bit) or 8-byte (16-bit) access where the address allows, scalars where not
-template <typename T>
-__device__ __forceinline__ void load4(const T* __restrict__ p, unsigned mask, unsigned o[4]) {
+// (SP: the code is the word's high bits)
+template <typename T, int SP = 0>
+__device__ __forceinline__ void load4(const T* __restrict__ p, const YuvParams& k, unsigned o[4]) {
     if (((uintptr_t)p & (4 * sizeof(T) - 1)) == 0) {
         if constexpr (sizeof(T) == 1) {
             const uint32_t q = *(const uint32_t*)p;
@@ -69,7 +78,7 @@ __device__ __forceinline__ void load4(const T* __restrict__ p, unsigned mask, un
         for (int i = 0; i < 4; ++i) o[i] = p[i];
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] &= mask;
+    for (int i = 0; i < 4; ++i) o[i] = (SP ? o[i] >> k.shift : o[i]) & k.mask;
 }
 
 // the first n (1..4) of 4 codes to consecutive samples
@@ -83,17 +92,32 @@ __device__ __forceinline__ void store4(T* __restrict__ p, const unsigned v[4], i
     }
 }
 
-// SX, SY: the chroma planes are (h >> SY, w >> SX); LEFT: the chroma sample lies on the even luma column (SX only; vertically it is centred)
-template <typename T, int SX, int SY, int LEFT>
+// Semi-planar chroma: the first n (2 or 4) of the words U V U V -- 8 bytes at once, or a chroma pixel's U and V as one dword, where the address allows
+__device__ __forceinline__ void store_uv(uint16_t* __restrict__ p, const unsigned v[4], int n) {
+    if (n == 4 && ((uintptr_t)p & 7) == 0) {
+        *(uint2*)p = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+    } else if (((uintptr_t)p & 3) == 0) {
+        *(uint32_t*)p = v[0] | (v[1] << 16);
+        if (n == 4) *(uint32_t*)(p + 2) = v[2] | (v[3] << 16);
+    } else {
+        for (int i = 0; i < n; ++i) p[i] = (uint16_t)v[i];
+    }
+}
+
+// SX, SY: the chroma planes are (h >> SY, w >> SX); LEFT: the chroma sample lies on the even luma column (SX only; vertically it is centred);
+// SP: semi-planar words (the head of the file)
+template <typename T, int SX, int SY, int LEFT, int SP = 0>
 __global__ __launch_bounds__(HBD_WG) void yuv_to_f32_kernel(PlaneBatch fb, float* __restrict__ dst, long dst_img, int H, int W, int quads,
                                                             int vec_ok, YuvParams k, int bilinear) {
     static_assert(SX || !SY, "4:4:0 is not a layout of this file");
+    static_assert(!SP || (SX && sizeof(T) == 2), "semi-planar frames are 16-bit words at 4:2:0 / 4:2:2");
+    constexpr int CS = SP ? 2 : 1;                           // samples from one chroma column to the next
     const long idx = (long)blockIdx.x * HBD_WG + threadIdx.x;
     if (idx >= (long)H * quads) return;
     const int y = (int)(idx / quads), x0 = (int)(idx - (long)y * quads) * 4;
     const PlaneDesc im = fb.d[blockIdx.y];
-    const unsigned m = k.mask;
     const int ch = im.h >> SY, cw = im.w >> SX;
+    auto code = [&](unsigned word) -> unsigned { return (SP ? word >> k.shift : word) & k.mask; };
     const int ys = min(y, im.h - 1);                         // rows below the extent repeat its last row
     const int cy = ys >> SY;
     // the second chroma row of the vertical filter: the neighbour on the pixel's side, clamped (nearest, or no vertical subsampling: cy itself)
@@ -106,17 +130,26 @@ __global__ __launch_bounds__(HBD_WG) void yuv_to_f32_kernel(PlaneBatch fb, float
     // Y and CU, CV = (SX ? 4 : 1) * (SY ? 4 : 1) times the upsampled chroma, exact
     unsigned Y[4], CU[4], CV[4];
     if (x0 + 3 < im.w) {                                     // 4 valid pixels
-        load4(yr + x0, m, Y);
+        load4<T, SP>(yr + x0, k, Y);
         if constexpr (!SX) {
-            load4(ua + x0, m, CU);
-            load4(va + x0, m, CV);
+            load4(ua + x0, k, CU);
+            load4(va + x0, k, CV);
         } else {
             const int c0 = x0 >> 1;                          // c0 + 1 <= cw - 1 because x0 + 3 <= w - 1
             auto vert = [&](const T* __restrict__ a, const T* __restrict__ b, int c) -> unsigned {
-                const unsigned p = a[c] & m;
-                return SY ? 3u * p + (b[c] & m) : p;         // (nearest: b == a, 4 p)
+                const unsigned p = code(a[c * CS]);
+                return SY ? 3u * p + code(b[c * CS]) : p;    // (nearest: b == a, 4 p)
             };
-            const unsigned u1 = vert(ua, ub, c0), u2 = vert(ua, ub, c0 + 1), v1 = vert(va, vb, c0), v2 = vert(va, vb, c0 + 1);
+            unsigned u1, u2, v1, v2;
+            if constexpr (SP) {                              // U V U V of columns c0, c0 + 1: 4 consecutive words per chroma row
+                unsigned qa[4], qb[4];
+                load4<T, 1>(ua + 2 * c0, k, qa);
+                if constexpr (SY) load4<T, 1>(ub + 2 * c0, k, qb);
+                auto vert4 = [&](int i) -> unsigned { return SY ? 3u * qa[i] + qb[i] : qa[i]; };
+                u1 = vert4(0); v1 = vert4(1); u2 = vert4(2); v2 = vert4(3);
+            } else {
+                u1 = vert(ua, ub, c0); u2 = vert(ua, ub, c0 + 1); v1 = vert(va, vb, c0); v2 = vert(va, vb, c0 + 1);
+            }
             if (bilinear) {
                 const int cp = min(c0 + 2, cw - 1);
                 const unsigned u3 = vert(ua, ub, cp), v3 = vert(va, vb, cp);
@@ -138,27 +171,27 @@ __global__ __launch_bounds__(HBD_WG) void yuv_to_f32_kernel(PlaneBatch fb, float
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int xs = min(x0 + i, im.w - 1);
-            Y[i] = yr[xs] & m;
+            Y[i] = code(yr[xs]);
             if constexpr (!SX) {
-                CU[i] = ua[xs] & m;
-                CV[i] = va[xs] & m;
+                CU[i] = code(ua[xs]);
+                CV[i] = code(va[xs]);
             } else {
-                const int cx = xs >> 1;
+                const int cx = (xs >> 1) * CS;               // in samples, as cxb
                 int cxb = cx;                                // the second tap and the weight of the first, in quarters
                 unsigned wa = 4u;
                 if (bilinear) {
                     if (LEFT) {
-                        if (xs & 1) { cxb = min(cx + 1, cw - 1); wa = 2u; }
+                        if (xs & 1) { cxb = min((xs >> 1) + 1, cw - 1) * CS; wa = 2u; }
                     } else {
-                        cxb = min(max(cx + ((xs & 1) ? 1 : -1), 0), cw - 1);
+                        cxb = min(max((xs >> 1) + ((xs & 1) ? 1 : -1), 0), cw - 1) * CS;
                         wa = 3u;
                     }
                 }
                 const unsigned wb = 4u - wa;
-                const unsigned pa = ua[cx] & m, pb = ua[cxb] & m, qa = va[cx] & m, qb = va[cxb] & m;
+                const unsigned pa = code(ua[cx]), pb = code(ua[cxb]), qa = code(va[cx]), qb = code(va[cxb]);
                 if (SY) {
-                    CU[i] = wa * (3u * pa + (ub[cx] & m)) + wb * (3u * pb + (ub[cxb] & m));
-                    CV[i] = wa * (3u * qa + (vb[cx] & m)) + wb * (3u * qb + (vb[cxb] & m));
+                    CU[i] = wa * (3u * pa + code(ub[cx])) + wb * (3u * pb + code(ub[cxb]));
+                    CV[i] = wa * (3u * qa + code(vb[cx])) + wb * (3u * qb + code(vb[cxb]));
                 } else {
                     CU[i] = wa * pa + wb * pb;
                     CV[i] = wa * qa + wb * qb;
@@ -207,10 +240,11 @@ __device__ __forceinline__ void ycc(float r, float g, float b, const YuvParams& 
     cr = __fdiv_rn(R - yn, k.a);
 }
 
-template <typename T, int SX, int SY, int LEFT>
+template <typename T, int SX, int SY, int LEFT, int SP = 0>
 __global__ __launch_bounds__(HBD_WG) void f32_to_yuv_kernel(const float* __restrict__ src, long src_img, long src_plane, long src_row,
                                                             PlaneBatch fb, int quads, int hblocks, int vec_ok, YuvParams k) {
     static_assert(SX || !SY, "4:4:0 is not a layout of this file");
+    static_assert(!SP || (SX && sizeof(T) == 2), "semi-planar frames are 16-bit words at 4:2:0 / 4:2:2");
     constexpr int R = SY ? 2 : 1;                            // rows of a block
     const long idx = (long)blockIdx.x * HBD_WG + threadIdx.x;
     if (idx >= (long)hblocks * quads) return;
@@ -246,6 +280,7 @@ __global__ __launch_bounds__(HBD_WG) void f32_to_yuv_kernel(const float* __restr
             float yn;
             ycc(p[0][r][i], p[1][r][i], p[2][r][i], k, yn, cb[r][i], cr[r][i]);
             Yc[r][i] = code_of(yn * k.ys + k.yo, k.peak);
+            if constexpr (SP) Yc[r][i] <<= k.shift;
         }
 #pragma unroll
     for (int r = 0; r < R; ++r) store4((T*)im.y + (long)(y0 + r) * im.yrow + x0, Yc[r], n);
@@ -268,8 +303,9 @@ __global__ __launch_bounds__(HBD_WG) void f32_to_yuv_kernel(const float* __restr
                 ycc(s[r * src_row + off], s[src_plane + r * src_row + off], s[2 * src_plane + r * src_row + off], k, yn, pb[r], pr[r]);
             }
         }
-        T* ou = (T*)im.u + (long)by * im.urow + (x0 >> 1);
-        T* ov = (T*)im.v + (long)by * im.vrow + (x0 >> 1);
+        [[maybe_unused]] T* ou = (T*)im.u + (long)by * im.urow + (x0 >> 1);
+        [[maybe_unused]] T* ov = (T*)im.v + (long)by * im.vrow + (x0 >> 1);
+        [[maybe_unused]] unsigned UV[4];                                      // SP: the words U V U V of the block's two chroma pixels
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             float hu[R], hv[R];                              // the horizontal step per row
@@ -292,11 +328,15 @@ __global__ __launch_bounds__(HBD_WG) void f32_to_yuv_kernel(const float* __restr
                 mu = SY ? (hu[0] + hu[R - 1]) * 0.25f : hu[0] * 0.5f;
                 mv = SY ? (hv[0] + hv[R - 1]) * 0.25f : hv[0] * 0.5f;
             }
-            if (2 * j < n) {
+            if constexpr (SP) {
+                UV[2 * j] = code_of(mu * k.cs + k.co, k.peak) << k.shift;
+                UV[2 * j + 1] = code_of(mv * k.cs + k.co, k.peak) << k.shift;
+            } else if (2 * j < n) {
                 ou[j] = (T)code_of(mu * k.cs + k.co, k.peak);
                 ov[j] = (T)code_of(mv * k.cs + k.co, k.peak);
             }
         }
+        if constexpr (SP) store_uv((T*)im.u + (long)by * im.urow + x0, UV, n);   // n (2 or 4) columns are n words of the UV row
     }
 }
 
@@ -375,6 +415,35 @@ PlaneBatch plane_batch(const void* const* y, const void* const* u, const void* c
                      : (sub) == LVAE_YUV_SUB_422 ? ((left) ? KERNEL<uint16_t, 1, 0, 1> : KERNEL<uint16_t, 1, 0, 0>)                     \
                                                  : ((left) ? KERNEL<uint16_t, 1, 1, 1> : KERNEL<uint16_t, 1, 1, 0>)))
 
+// Semi-planar: depth 10 / 12 at 4:2:0 / 4:2:2; per frame a luma plane and one UV plane whose rows hold 2 * (w / 2) = w samples
+bool sp_frames_ok(const void* const* y, const void* const* uv, const long* y_row, const long* uv_row, const int* hw, int B, int depth,
+                  int subsampling, int H, int W) {
+    if ((depth != 10 && depth != 12) || (subsampling != LVAE_YUV_SUB_420 && subsampling != LVAE_YUV_SUB_422)) return false;
+    if (!y || !uv || !y_row || !uv_row || !hw) return false;
+    const int sy = subsampling == LVAE_YUV_SUB_420;
+    for (int b = 0; b < B; ++b) {
+        const int h = hw[2 * b], w = hw[2 * b + 1];
+        if (h <= 0 || w <= 0 || (h & sy) || (w & 1) || h > H || w > W) return false;
+        if (!y[b] || !uv[b] || y_row[b] < w || uv_row[b] < w) return false;
+    }
+    return true;
+}
+
+// u = the UV plane, v = the same plane one sample on, both with the UV row stride: what the SP variants index with column * 2
+PlaneBatch sp_plane_batch(const void* const* y, const void* const* uv, const long* y_row, const long* uv_row, const int* hw, int b0, int n) {
+    PlaneBatch fb = {};
+    for (int i = 0; i < n; ++i) {
+        const int b = b0 + i;
+        uint16_t* c = (uint16_t*)const_cast<void*>(uv[b]);
+        fb.d[i] = {const_cast<void*>(y[b]), c, c + 1, y_row[b], uv_row[b], uv_row[b], hw[2 * b], hw[2 * b + 1]};
+    }
+    return fb;
+}
+
+#define HBD_PICK_SP(KERNEL, sub, left)                                                                                                  \
+    ((sub) == LVAE_YUV_SUB_422 ? ((left) ? KERNEL<uint16_t, 1, 0, 1, 1> : KERNEL<uint16_t, 1, 0, 0, 1>)                                 \
+                               : ((left) ? KERNEL<uint16_t, 1, 1, 1, 1> : KERNEL<uint16_t, 1, 1, 0, 1>))
+
 }  // namespace
 
 extern "C" int lvae_image_yuv_to_f32(const void* const* y, const void* const* u, const void* const* v, const long* y_row, const long* u_row,
@@ -421,6 +490,54 @@ extern "C" int lvae_image_f32_to_yuv(const float* src, long src_img, long src_pl
         const int n = B - b0 < HBD_CHUNK ? B - b0 : HBD_CHUNK;
         hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)n), dim3(HBD_WG), 0, (hipStream_t)stream, src + (long)b0 * src_img, src_img, src_plane,
                            src_row, plane_batch(y, u, v, y_row, u_row, v_row, hw, b0, n), quads, hblocks, vec_ok, k);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_image_yuvsp_to_f32(const uint16_t* const* y, const uint16_t* const* uv, const long* y_row, const long* uv_row, const int* hw,
+                                       int B, int depth, int subsampling, int siting, int matrix, int range, int chroma, float* dst, long dst_img,
+                                       int H, int W, void* stream) {
+    if (!dst || B <= 0 || H <= 0 || W <= 0 || !enums_ok(depth, subsampling, siting, matrix, range) ||
+        (chroma != LVAE_YUV_NEAREST && chroma != LVAE_YUV_BILINEAR))
+        return -22;
+    const int quads = (W + 3) / 4;
+    if ((long)H * quads > (long)INT_MAX || (B > 1 && dst_img < 3L * H * W)) return -22;
+    if (!sp_frames_ok((const void* const*)y, (const void* const*)uv, y_row, uv_row, hw, B, depth, subsampling, H, W)) return -22;
+    const int vec_ok = W % 4 == 0 && dst_img % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+    const unsigned gx = (unsigned)(((long)H * quads + HBD_WG - 1) / HBD_WG);
+    const YuvParams k = yuv_params(matrix, range, depth);
+    auto kernel = HBD_PICK_SP(yuv_to_f32_kernel, subsampling, siting == LVAE_YUV_SITING_LEFT);
+    for (int b0 = 0; b0 < B; b0 += HBD_CHUNK) {
+        const int n = B - b0 < HBD_CHUNK ? B - b0 : HBD_CHUNK;
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)n), dim3(HBD_WG), 0, (hipStream_t)stream,
+                           sp_plane_batch((const void* const*)y, (const void* const*)uv, y_row, uv_row, hw, b0, n), dst + (long)b0 * dst_img, dst_img,
+                           H, W, quads, vec_ok, k, chroma == LVAE_YUV_BILINEAR);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_image_f32_to_yuvsp(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int depth,
+                                       int subsampling, int siting, int matrix, int range, uint16_t* const* y, uint16_t* const* uv,
+                                       const long* y_row, const long* uv_row, void* stream) {
+    if (!src || B <= 0 || H <= 0 || W <= 0 || !enums_ok(depth, subsampling, siting, matrix, range)) return -22;
+    if (src_row < W || src_plane < (long)(H - 1) * src_row + W || (B > 1 && src_img < 2 * src_plane + (long)(H - 1) * src_row + W)) return -22;
+    if (!sp_frames_ok((const void* const*)y, (const void* const*)uv, y_row, uv_row, hw, B, depth, subsampling, H, W)) return -22;
+    int hmax = 0, wmax = 0;
+    for (int b = 0; b < B; ++b) {
+        hmax = hw[2 * b] > hmax ? hw[2 * b] : hmax;
+        wmax = hw[2 * b + 1] > wmax ? hw[2 * b + 1] : wmax;
+    }
+    const int quads = (wmax + 3) / 4, hblocks = hmax >> (subsampling == LVAE_YUV_SUB_420);
+    if ((long)hblocks * quads > (long)INT_MAX) return -22;
+    const int vec_ok = src_img % 4 == 0 && src_plane % 4 == 0 && src_row % 4 == 0 && ((uintptr_t)src & 15) == 0;
+    const unsigned gx = (unsigned)(((long)hblocks * quads + HBD_WG - 1) / HBD_WG);
+    const YuvParams k = yuv_params(matrix, range, depth);
+    auto kernel = HBD_PICK_SP(f32_to_yuv_kernel, subsampling, siting == LVAE_YUV_SITING_LEFT);
+    for (int b0 = 0; b0 < B; b0 += HBD_CHUNK) {
+        const int n = B - b0 < HBD_CHUNK ? B - b0 : HBD_CHUNK;
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)n), dim3(HBD_WG), 0, (hipStream_t)stream, src + (long)b0 * src_img, src_img, src_plane,
+                           src_row, sp_plane_batch((const void* const*)y, (const void* const*)uv, y_row, uv_row, hw, b0, n), quads, hblocks,
+                           vec_ok, k);
     }
     return (int)hipGetLastError();
 }

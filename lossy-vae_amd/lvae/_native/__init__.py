@@ -77,6 +77,7 @@ ST_ROWMAJOR, ST_SHUFFLE, ST_IMAGE = 0, 2, 3
 YUV_FORMATS, YUV_MATRICES, YUV_RANGES, YUV_CHROMA = ('i420', 'nv12'), ('bt601', 'bt709'), ('limited', 'full'), ('nearest', 'bilinear')   # LVAE_YUV_*: a name's code is its index
 YUV_SUBSAMPLINGS, YUV_SITINGS, YUV_MATRICES2 = ('420', '422', '444'), ('center', 'left'), ('bt601', 'bt709', 'bt2020')   # LVAE_YUV_SUB_* / LVAE_YUV_SITING_* / the matrices of lvae_image_yuv_to_f32 / lvae_image_f32_to_yuv
 YUV_DEPTHS = (8, 10, 12)
+YUV_LAYOUTS = ('planar', 'semiplanar')                  # LVAE_YUV_LAYOUT_*
 EVAL_CHUNKS = 256               # LVAE_EVAL_CHUNKS: lvae_rd_image_f32 / lvae_pixel_nll_f32 take ws = double[B][EVAL_CHUNKS][2]
 
 _vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
@@ -144,6 +145,8 @@ SIGNATURES = {
     'lvae_sse_u8': (_i, [_vp] * 5 + [_i, _vp, _vp]),
     'lvae_image_yuv_to_f32': (_i, [_vp] * 7 + [_i] * 7 + [_vp, _l, _i, _i, _vp]),
     'lvae_image_f32_to_yuv': (_i, [_vp, _l, _l, _l, _i, _i, _vp] + [_i] * 6 + [_vp] * 7),
+    'lvae_image_yuvsp_to_f32': (_i, [_vp] * 5 + [_i] * 7 + [_vp, _l, _i, _i, _vp]),
+    'lvae_image_f32_to_yuvsp': (_i, [_vp, _l, _l, _l, _i, _i, _vp] + [_i] * 6 + [_vp] * 5),
     'lvae_sse_u16': (_i, [_vp] * 5 + [_i, _vp, _vp]),
     'lvae_tile_stitch': (_i, [_vp, _l, _l, _vp, _vp] + [_i] * 11 + [_vp, _l, _l, _i, _vp, _sz, _vp]),
     'lvae_tile_stitch_workspace_bytes': (_sz, [_i, _i]),

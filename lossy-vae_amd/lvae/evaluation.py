@@ -140,7 +140,7 @@ def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=No
 
 @torch.no_grad()
 def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, depth=8, subsampling='420', siting='center',
-                 **colour):
+                 layout='planar', **colour):
     """A raw 8-bit 4:2:0 file coded frame by frame (an image codec as an intra-frame coder) -> dict of means over its frames: 'bpp'
     (8 * len(blob) / (h * w)) and the keys of lvae.metrics.psnr_yuv420 ('mse-y' ... 'psnr-yuv'), computed between the file's bytes and
     decompress_yuv420's.  colour: matrix / range / chroma of compress_yuv420 (matrix and range also go to decompress_yuv420).  Every frame
@@ -148,21 +148,28 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
     device, and three integers per frame come back.  Frames are coded `batch` at a time; lmb: as in compress_yuv420.
     depth / subsampling / siting: with any value other than the defaults (8, '420', 'center') the file is a planar one of that depth and
     subsampling (utils.yuv.read_yuv; fmt must stay 'i420'), coded by compress_yuv / decompress_yuv with that siting and measured by
-    lvae.metrics.psnr_yuv, whose key 'psnr-avg' joins the result; matrix may then be 'bt2020'."""
+    lvae.metrics.psnr_yuv, whose key 'psnr-avg' joins the result; matrix may then be 'bt2020'.  layout 'semiplanar': a P010 / P012 / P210 /
+    P212 file (utils.yuv.read_yuv_sp; depth 10 | 12, subsampling '420' | '422'), coded and reconstructed in that layout and measured on its
+    codes."""
     from .metrics import PSNR_YUV_KEYS, PSNR_YUV_KEYS2, psnr_yuv, psnr_yuv420
-    from .utils.yuv import read_yuv, read_yuv420
+    from .utils.yuv import read_yuv, read_yuv420, read_yuv_sp
+    if layout not in ('planar', 'semiplanar'):
+        raise ValueError(f"yuv_evaluate: layout is 'planar' or 'semiplanar', got {layout!r}")
     unknown = set(colour) - {'matrix', 'range', 'chroma'}
     if unknown:
         raise TypeError(f'yuv_evaluate: unexpected arguments {sorted(unknown)}')
     dev = next(model.parameters()).device
     dec = {k: v for k, v in colour.items() if k != 'chroma'}
-    general = (depth, subsampling, siting) != (8, '420', 'center')
+    general = (depth, subsampling, siting) != (8, '420', 'center') or layout == 'semiplanar'
     if general:
         if fmt != 'i420':
             raise ValueError(f'yuv_evaluate: depth / subsampling / siting apply to planar files, got fmt={fmt!r}')
-        frames = read_yuv(yuv_path, width, height, subsampling, depth, frames=max_frames)
+        if layout == 'semiplanar':
+            frames = read_yuv_sp(yuv_path, width, height, depth, subsampling, frames=max_frames)
+        else:
+            frames = read_yuv(yuv_path, width, height, subsampling, depth, frames=max_frames)
         compress = lambda chunk, **enc: model.compress_yuv(chunk, siting=siting, **enc)
-        decompress = lambda blobs: model.decompress_yuv(blobs, depth=depth, subsampling=subsampling, siting=siting, **dec)
+        decompress = lambda blobs: model.decompress_yuv(blobs, depth=depth, subsampling=subsampling, siting=siting, layout=layout, **dec)
         measure, keys = psnr_yuv, PSNR_YUV_KEYS2
     else:
         frames = read_yuv420(yuv_path, width, height, fmt, frames=max_frames)

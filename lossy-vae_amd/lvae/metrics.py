@@ -122,16 +122,17 @@ def sse_u16(pairs):
 
 
 def psnr_yuv(ref_frames, rec_frames):
-    """PSNR of utils.yuv.YuvFrame lists (or two frames) of any depth and subsampling: per frame a dict {'mse-y', 'mse-u', 'mse-v', 'psnr-y',
+    """PSNR of utils.yuv.YuvFrame / YuvSpFrame lists (or two frames) of any depth and subsampling: per frame a dict {'mse-y', 'mse-u', 'mse-v', 'psnr-y',
     'psnr-u', 'psnr-v', 'psnr-yuv', 'psnr-avg'} of floats.  mse = the plane's exact sum of squared code differences (sse_u8 / sse_u16) / its
     sample count, in float64; psnr = 10 log10(peak^2 / mse), inf for identical planes, with peak = 255 * 2^(depth - 8) -- 1020 at 10 bits,
     4080 at 12: the convention of the HM / VTM reference software, NOT 2^depth - 1.  psnr-yuv = (6 psnr-y + psnr-u + psnr-v) / 8, HM's
     weighting for 4:2:0; psnr-avg is the PSNR of the pooled error, (sse-y + sse-u + sse-v) / (all three sample counts): the meaningful single
     number for 4:2:2 and 4:4:4, where 6:1:1 does not reflect the sample counts."""
-    from .utils.yuv import YuvFrame
-    if isinstance(ref_frames, YuvFrame):
+    from .utils.yuv import YuvFrame, YuvSpFrame
+    if isinstance(ref_frames, (YuvFrame, YuvSpFrame)):
         return psnr_yuv([ref_frames], [rec_frames])[0]
-    ref, rec = list(ref_frames), list(rec_frames)
+    planar = lambda f: f.to_planar() if isinstance(f, YuvSpFrame) else f       # semi-planar (P010 ...) frames: compared as their codes
+    ref, rec = [planar(f) for f in ref_frames], [planar(f) for f in rec_frames]
     if len(ref) != len(rec) or not ref:
         raise ValueError(f'psnr_yuv: {len(ref)} reference and {len(rec)} reconstructed frames')
     for i, (a, b) in enumerate(zip(ref, rec)):

@@ -649,24 +649,143 @@ class CodecBase(nn.Module):
         max_stride agree -> list of bytes, element i being the model's own container: the file compress_file would write for the RGB image
         utils.yuv.to_rgb01_any gives for frame i.  matrix: 'bt601' | 'bt709' | 'bt2020'; siting: 'center' | 'left' (H.264 / HEVC co-sited
         chroma).  The planes go to the device as their file holds them (1 or 2 bytes per sample).  Neither the colour parameters nor depth,
-        subsampling and siting are stored in the stream: decompress_yuv has to be given the encoder's."""
-        from ..utils.yuv import YuvBatch
-        return self._compress_byte_batch(YuvBatch(frames, self.max_stride, self._dummy.device, matrix, range, chroma, siting), lmb, 'compress_yuv')
+        subsampling and siting are stored in the stream: decompress_yuv has to be given the encoder's (compress_yuv_sequence stores them).
+        A list of utils.yuv.YuvSpFrame (P010 / P012 / P210 / P212) is taken as well: its two planes are uploaded as they are and each
+        pipeline group's plan input is filled by lvae_image_yuvsp_to_f32, so the blobs are byte for byte those of the frames' to_planar().
+        Planar and semi-planar frames may not be mixed in one call."""
+        from ..utils.yuv import YuvBatch, YuvSpBatch, YuvSpFrame
+        frames = list(frames)
+        sp = [isinstance(f, YuvSpFrame) for f in frames]
+        if any(sp) and not all(sp):
+            raise ValueError('compress_yuv: planar and semi-planar frames may not be mixed in one call')
+        batch = (YuvSpBatch if any(sp) else YuvBatch)(frames, self.max_stride, self._dummy.device, matrix, range, chroma, siting)
+        return self._compress_byte_batch(batch, lmb, 'compress_yuv')
 
     @torch.no_grad()
-    def decompress_yuv(self, blobs, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited'):
+    def decompress_yuv(self, blobs, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar'):
         """compress_yuv (or compress_images / compress_file) bytes -> list of utils.yuv.YuvFrame of `depth` and `subsampling` on the
         model's device, each cropped to the size in its header and converted on the device (utils.yuv.from_rgb01_any).  A depth above 8
         keeps precision of the fp32 reconstruction that 8-bit codes drop.  ValueError: a header's size does not fit the subsampling.
-        depth / siting / matrix / range: the stream does not record them; pass what the encoder was given."""
-        from ..utils.yuv import _check2, _extent_ok, from_rgb01_any
+        depth / siting / matrix / range: the stream does not record them; pass what the encoder was given.  layout 'semiplanar' (depth
+        10 | 12, subsampling '420' | '422'): utils.yuv.YuvSpFrames holding the same codes, written in that layout by the kernel."""
+        from ..utils.yuv import SP_DEPTHS, SP_SUBSAMPLINGS, _check2, _extent_ok, from_rgb01_any
         _check2(depth, subsampling, siting, matrix, range)
+        if layout not in ('planar', 'semiplanar') or (layout == 'semiplanar' and (depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS)):
+            raise ValueError(f"decompress_yuv: layout is 'planar' or -- at {SP_DEPTHS} bits and {SP_SUBSAMPLINGS} -- 'semiplanar', got {layout!r} "
+                             f'at {depth} bits and {subsampling}')
         for i, b in enumerate(blobs):
             h, w = self._unpack_blob(b)[1]
             if not _extent_ok(h, w, subsampling):
                 raise ValueError(f'decompress_yuv: blob {i} holds a {h} x {w} image, which does not fit subsampling {subsampling}')
-        conv = lambda x, sizes: from_rgb01_any(x, sizes, depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range)
+        conv = lambda x, sizes: from_rgb01_any(x, sizes, depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range,
+                                               layout=layout)
         return self._decompress_blobs(blobs, conv)
+
+    # ---- self-describing YUV sequences (lvae/utils/yuvseq.py: the `LVYS` container around the frames' unchanged blobs)
+    @property
+    def _registry_name(self):
+        """The name get_model built this model under (the class's name for a model built by hand): what a sequence container records."""
+        return getattr(self, 'model_name', None) or type(self).__name__
+
+    @torch.no_grad()
+    def compress_yuv_sequence(self, frames_or_path, width=None, height=None, depth=8, subsampling='420', layout='planar', siting='center',
+                              matrix='bt709', range='limited', chroma='bilinear', frames=None, lmb=None, max_batch=8):
+        """A sequence of frames -> the bytes of one self-describing container (utils.yuvseq.pack_sequence).  frames_or_path: a list of
+        frames of ONE kind and size -- utils.yuv.YuvFrame, YuvSpFrame or Yuv420Frame; depth, subsampling and layout are then the frames' --
+        or the path of a raw file of `width` x `height` frames of `depth`, `subsampling` and `layout` ('planar' | 'semiplanar' | 'i420' |
+        'nv12'), of which `max_batch` at a time are read, uploaded and coded (all of them, or the first `frames`).  Frame k's blob is
+        compress_yuv([frame k], ...)[0] (compress_yuv420 for 'i420' / 'nv12'), whatever max_batch: batch rows are bit-equal to single calls.
+        lmb: None, one value or -- variable-rate models -- one value per frame.  The header records size, depth, subsampling, siting,
+        matrix, range, chroma, the layout, this model's registry name and its GEMM precision: decompress_yuv_sequence needs nothing else."""
+        from ..utils import yuv, yuvseq
+        if lmb is not None and not self.variable_rate:
+            raise ValueError(f'{type(self).__name__} is a fixed-rate model: it takes no lmb')
+        if isinstance(frames_or_path, (str, os.PathLike)):
+            if width is None or height is None:
+                raise ValueError('compress_yuv_sequence: a raw file needs width and height')
+            yuvseq.check_layout(layout, depth, subsampling, siting, matrix)
+            path, limit = frames_or_path, None if frames is None else int(frames)
+            if layout in ('i420', 'nv12'):
+                per = yuv.frame_bytes(width, height)
+                read = lambda start, n: yuv.read_yuv420(path, width, height, layout, frames=n, start=start)
+            else:
+                per = yuv.frame_bytes2(width, height, subsampling, depth)
+                read = ((lambda start, n: yuv.read_yuv_sp(path, width, height, depth, subsampling, frames=n, start=start)) if layout == 'semiplanar'
+                        else (lambda start, n: yuv.read_yuv(path, width, height, subsampling, depth, frames=n, start=start)))
+            size = os.path.getsize(path)
+            if size == 0 or size % per:
+                raise ValueError(f'compress_yuv_sequence: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
+            total = size // per if limit is None else min(limit, size // per)
+            source = lambda start, n: read(start, min(n, total - start)) if start < total else []
+        else:
+            source = list(frames_or_path)
+            if not source:
+                raise ValueError('compress_yuv_sequence: no frames')
+            f0 = source[0]
+            if any(type(f) is not type(f0) or f.size != f0.size for f in source):
+                raise ValueError('compress_yuv_sequence: the frames of a sequence share one kind and one size')
+            if isinstance(f0, yuv.Yuv420Frame):
+                if any(f.fmt != f0.fmt for f in source):
+                    raise ValueError('compress_yuv_sequence: the frames of a sequence share one plane layout')
+                depth, subsampling, layout = 8, '420', f0.fmt
+            elif isinstance(f0, (yuv.YuvFrame, yuv.YuvSpFrame)):
+                depth, subsampling, layout = f0.depth, f0.subsampling, 'semiplanar' if isinstance(f0, yuv.YuvSpFrame) else 'planar'
+            else:
+                raise ValueError(f'compress_yuv_sequence: expected frames of utils.yuv, got {type(f0).__name__}')
+            (height, width) = f0.size
+            yuvseq.check_layout(layout, depth, subsampling, siting, matrix)
+        if layout in ('i420', 'nv12'):
+            compress = lambda chunk, **kw: self.compress_yuv420(chunk, matrix=matrix, range=range, chroma=chroma, **kw)
+        else:
+            compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
+        blobs = yuvseq.code_sequence(compress, source, max_batch, lmb)
+        meta = dict(width=width, height=height, depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range, chroma=chroma,
+                    layout=layout, model=self._registry_name, gemm=self._prec)
+        return yuvseq.pack_sequence(meta, blobs)
+
+    def yuv_sequence_info(self, blob):
+        """utils.yuvseq.yuv_sequence_info (header parsing only, no GPU) plus 'lmb': the frames' lambdas from their blobs' own headers on
+        variable-rate models (as tiled_info), else None."""
+        from ..utils import yuvseq
+        info = yuvseq.yuv_sequence_info(blob)
+        info['lmb'] = [self._blob_lmb(yuvseq.frame_blob(blob, info, k)) for k in range(info['frames'])] if self.variable_rate else None
+        return info
+
+    @torch.no_grad()
+    def decompress_yuv_sequence(self, blob, frames=None, layout=None, out_path=None, max_batch=8):
+        """A compress_yuv_sequence container -> its frames on the model's device, with NO colour parameter: size, depth, subsampling, siting,
+        matrix and range come from the header.  frames: None (all), a range or a list of indexes -- only those blobs are read, through the
+        length table, and decoded, `max_batch` at a time.  layout: None = the source's; 'planar' (YuvFrame), 'semiplanar' (YuvSpFrame) or,
+        for 8-bit 4:2:0 centre-sited sequences, 'i420' / 'nv12' (Yuv420Frame).  out_path: write the frames to that raw file instead and
+        return their number.  ValueError: a malformed container (utils.yuvseq.yuv_sequence_info), a header whose model name or GEMM
+        precision is not this model's (both names are in the message; set_gemm_precision selects the arithmetic), a layout the header's
+        parameters do not have."""
+        from ..utils import yuv, yuvseq
+        info = yuvseq.yuv_sequence_info(blob)
+        if info['model'] != self._registry_name:
+            raise ValueError(f"decompress_yuv_sequence: the sequence was written by model {info['model']!r}, this model is {self._registry_name!r}")
+        if info['gemm'] != self._prec:
+            raise ValueError(f"decompress_yuv_sequence: the sequence was written under GEMM precision {info['gemm']!r}, this model runs "
+                             f"{self._prec!r}; call set_gemm_precision({info['gemm']!r}) first")
+        layout = info['layout'] if layout is None else layout
+        depth, sub, siting, matrix, rng = (info[k] for k in ('depth', 'subsampling', 'siting', 'matrix', 'range'))
+        yuvseq.check_layout(layout, depth, sub, siting, matrix)
+        if layout in ('i420', 'nv12'):
+            decode, write = (lambda bl: self.decompress_yuv420(bl, fmt=layout, matrix=matrix, range=rng)), yuv.write_yuv420
+        else:
+            decode = lambda bl: self.decompress_yuv(bl, depth=depth, subsampling=sub, siting=siting, matrix=matrix, range=rng, layout=layout)
+            write = yuv.write_yuv_sp if layout == 'semiplanar' else yuv.write_yuv
+        idxs, step, out = yuvseq.frame_indexes(info, frames), max(1, int(max_batch)), []
+        for o in range(0, len(idxs), step):
+            got = decode([yuvseq.frame_blob(blob, info, k) for k in idxs[o:o + step]])
+            for f in got:
+                if f.size != (info['height'], info['width']):
+                    raise ValueError(f"YUV sequence container: a frame holds {f.size[1]} x {f.size[0]} pixels, the header says {info['width']} x {info['height']}")
+            if out_path is None:
+                out += got
+            else:
+                write(got, out_path, append=o > 0)
+        return out if out_path is None else len(idxs)
 
     @torch.no_grad()
     def decompress_images(self, blobs):

@@ -14,4 +14,9 @@ def register_model(func):
 
 
 def get_model(name, *args, **kwargs):
-    return _all_models[name](*args, **kwargs)
+    model = _all_models[name](*args, **kwargs)
+    try:
+        model.model_name = name          # what a YUV sequence container records (CodecBase.compress_yuv_sequence)
+    except AttributeError:
+        pass
+    return model

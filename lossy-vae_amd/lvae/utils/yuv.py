@@ -13,9 +13,13 @@ replicate-padded where the encoder reads it, and a reconstruction becomes codes 
 as utils.image.to_float01 / to_u8.
 
 Samples of more than 8 bits are 16-bit little-endian words with the value in the LOW bits (yuv420p10le, yuv422p12le: what ffmpeg rawvideo
-and HM / VTM read and write), held as torch.int16.  Not supported: semi-planar high-bit-depth layouts with the value in the high bits
-(P010 and kin), 16-bit depth, chroma sitings other than centre / left.  The colour parameters, the depth and the siting are the caller's
-on both sides: no stream or container stores them.
+and HM / VTM read and write), held as torch.int16.  The frames hardware video decoders deliver are a third kind, `YuvSpFrame`: semi-planar,
+10 / 12 bits at 4:2:0 / 4:2:2 (P010, P012, P210, P212), a luma plane and ONE plane of interleaved U V words with the value in the HIGH bits
+(`read_yuv_sp`, `write_yuv_sp`, `YuvSpBatch`; `YuvSpFrame.to_planar` / `YuvFrame.to_semiplanar` state the layout as torch ops).  Their
+conversion IS the planar one -- the SP variants of csrc/yuv_hbd_io.hip give the bits the planar kernels give for the deinterleaved, shifted
+planes -- so yuv_to_rgb_expr2 / rgb_to_yuv_expr2 define it too.  Not supported: 16-bit depth (P016), chroma sitings other than centre / left,
+8-bit semi-planar 4:2:2 / 4:4:4 (NV16 / NV24).  The colour parameters, the depth and the siting are the caller's on both sides: no stream
+stores them; the sequence container of utils/yuvseq.py does.
 """
 import ctypes
 import os
@@ -28,6 +32,7 @@ from .image import _canvas
 
 from .._native import YUV_CHROMA as CHROMA, YUV_FORMATS as FORMATS, YUV_MATRICES as MATRICES, YUV_RANGES as RANGES   # index = LVAE_YUV_* code
 from .._native import YUV_DEPTHS as DEPTHS, YUV_MATRICES2 as MATRICES2, YUV_SITINGS as SITINGS, YUV_SUBSAMPLINGS as SUBSAMPLINGS
+from .._native import YUV_LAYOUTS as LAYOUTS                 # LVAE_YUV_LAYOUT_*
 # per matrix: Kr, Kg, Kb, a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg -- the literals of csrc/yuv_io.hip
 COEF = {'bt601': (0.299, 0.587, 0.114, 1.402, 1.772, 0.344136286, 0.714136286),
         'bt709': (0.2126, 0.7152, 0.0722, 1.5748, 1.8556, 0.187324273, 0.468124273),
@@ -98,8 +103,8 @@ def frame_bytes(width, height):
     return width * height * 3 // 2
 
 
-def read_yuv420(path, width, height, fmt='i420', frames=None):
-    """A raw .yuv file of `width` x `height` 8-bit 4:2:0 frames -> list of Yuv420Frame on the CPU (all of them, or the first `frames`).
+def read_yuv420(path, width, height, fmt='i420', frames=None, start=0):
+    """A raw .yuv file of `width` x `height` 8-bit 4:2:0 frames -> list of Yuv420Frame on the CPU (all of them, or the first `frames`; from frame `start` on).
     The file is read into ONE buffer -- pinned when a GPU is there, so a frame's upload is an asynchronous copy -- and the planes are
     views of it.  ValueError: odd or non-positive sides, a file size that is not a whole number of frames, an unknown fmt."""
     _check('bt709', 'limited', fmt=fmt)
@@ -109,11 +114,12 @@ def read_yuv420(path, width, height, fmt='i420', frames=None):
     size = os.path.getsize(path)
     if size == 0 or size % per:
         raise ValueError(f'read_yuv420: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
-    n = size // per if frames is None else min(int(frames), size // per)
-    if n <= 0:
-        raise ValueError(f'read_yuv420: frames={frames}')
+    n = size // per - int(start) if frames is None else min(int(frames), size // per - int(start))
+    if n <= 0 or start < 0:
+        raise ValueError(f'read_yuv420: frames={frames}, start={start} of {size // per}')
     buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
     with open(path, 'rb') as f:
+        f.seek(int(start) * per)
         got = f.readinto(buf.numpy())
     if got != n * per:
         raise ValueError(f'read_yuv420: short read of {path}')
@@ -391,15 +397,24 @@ class YuvFrame:
     def cpu(self):
         return self.to('cpu')
 
+    def to_semiplanar(self):
+        """The same codes as a YuvSpFrame (depth 10 | 12, '420' | '422'): word = code << (16 - depth), U and V interleaved.  Plain torch ops
+        on the frame's device: a copy."""
+        if self.depth not in SP_DEPTHS or self.subsampling not in SP_SUBSAMPLINGS:
+            raise ValueError(f'semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {self.depth} bits at {self.subsampling}')
+        mask, sh = (1 << self.depth) - 1, 16 - self.depth
+        word = lambda p: ((p.to(torch.int32) & mask) << sh).to(torch.int16)
+        return YuvSpFrame(word(self.y), torch.stack([word(self.u), word(self.v)], -1).flatten(1), self.depth, self.subsampling)
+
 
 def frame_bytes2(width, height, subsampling='420', depth=8):
     sx, sy = SHIFTS[subsampling]
     return (width * height + 2 * (width >> sx) * (height >> sy)) * (1 if depth == 8 else 2)
 
 
-def read_yuv(path, width, height, subsampling='420', depth=8, frames=None):
+def read_yuv(path, width, height, subsampling='420', depth=8, frames=None, start=0):
     """A raw planar .yuv file of `width` x `height` frames (yuv420p, yuv422p10le, yuv444p12le ...) -> list of YuvFrame on the CPU (all of
-    them, or the first `frames`).  As read_yuv420: ONE buffer, pinned when a GPU is there, the planes views of it.  ValueError: sides that do
+    them, or the first `frames`; from frame `start` on).  As read_yuv420: ONE buffer, pinned when a GPU is there, the planes views of it.  ValueError: sides that do
     not fit the subsampling, a file size that is not a whole number of frames, an unknown depth / subsampling, a code beyond the depth."""
     _check2(depth, subsampling)
     if not _extent_ok(height, width, subsampling):
@@ -408,11 +423,12 @@ def read_yuv(path, width, height, subsampling='420', depth=8, frames=None):
     size = os.path.getsize(path)
     if size == 0 or size % per:
         raise ValueError(f'read_yuv: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
-    n = size // per if frames is None else min(int(frames), size // per)
-    if n <= 0:
-        raise ValueError(f'read_yuv: frames={frames}')
+    n = size // per - int(start) if frames is None else min(int(frames), size // per - int(start))
+    if n <= 0 or start < 0:
+        raise ValueError(f'read_yuv: frames={frames}, start={start} of {size // per}')
     buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
     with open(path, 'rb') as f:
+        f.seek(int(start) * per)
         got = f.readinto(buf.numpy())
     if got != n * per:
         raise ValueError(f'read_yuv: short read of {path}')
@@ -437,6 +453,103 @@ def write_yuv(frames, path, append=False):
             for p in fr.planes():
                 a = p.cpu().contiguous().numpy()
                 f.write((a if a.dtype == np.uint8 else a.astype('<i2', copy=False)).tobytes())
+
+
+# ----------------------------------------------------------------------------------------------- semi-planar 10 / 12 bits: P010 and kin
+SP_DEPTHS, SP_SUBSAMPLINGS = (10, 12), ('420', '422')
+SP_LAYOUTS = {'p010': (10, '420'), 'p012': (12, '420'), 'p210': (10, '422'), 'p212': (12, '422')}       # name -> (depth, subsampling)
+
+
+class YuvSpFrame:
+    """One semi-planar frame of `depth` 10 | 12 bits at `subsampling` '420' | '422' (P010 / P012 / P210 / P212): a luma plane y (h, w) and a
+    chroma plane uv of (h/2 | h, w/2) chroma pixels, each two neighbouring words U, V -- given as (ch, 2 cw) or (ch, cw, 2) and kept as
+    (ch, 2 cw) -- torch.int16 on one device: the 16 bits of the container with the value in the HIGH bits, code = word >> (16 - depth).
+    The low bits are ignored, whatever they hold.  numpy uint16 arrays are reinterpreted, not copied.  w is even, and h for 4:2:0."""
+
+    def __init__(self, y, uv, depth=10, subsampling='420'):
+        if depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS:
+            raise ValueError(f'semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth!r} bits at {subsampling!r}')
+
+        def t(a):
+            if isinstance(a, torch.Tensor):
+                return a
+            a = np.asarray(a)
+            return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a)
+        y, uv = t(y), t(uv)
+        if y.dim() != 2 or y.dtype != torch.int16:
+            raise ValueError(f'y is an (h, w) torch.int16 plane, got {tuple(y.shape)} {y.dtype}')
+        h, w = int(y.shape[0]), int(y.shape[1])
+        if not _extent_ok(h, w, subsampling):
+            raise ValueError(f'a {subsampling} frame has positive sides, even where the chroma is subsampled, got {h} x {w}')
+        ch = h >> SHIFTS[subsampling][1]
+        if uv.dtype != torch.int16 or tuple(uv.shape) not in ((ch, w), (ch, w // 2, 2)) or uv.device != y.device:
+            raise ValueError(f'uv is a ({ch}, {w}) or ({ch}, {w // 2}, 2) torch.int16 plane on the device of y, got {tuple(uv.shape)} {uv.dtype}')
+        self.y, self.uv, self.depth, self.subsampling, self.h, self.w = y, uv.flatten(1) if uv.dim() == 3 else uv, depth, subsampling, h, w
+
+    @property
+    def device(self):
+        return self.y.device
+
+    @property
+    def size(self):
+        return (self.h, self.w)
+
+    def planes(self):
+        """The planes in file order: (y, uv)."""
+        return (self.y, self.uv)
+
+    def to(self, device, non_blocking=False):
+        if torch.device(device) == self.device:
+            return self
+        return YuvSpFrame(self.y.to(device, non_blocking=non_blocking), self.uv.to(device, non_blocking=non_blocking), self.depth, self.subsampling)
+
+    def cpu(self):
+        return self.to('cpu')
+
+    def to_planar(self):
+        """The same codes as a YuvFrame: code = word >> (16 - depth) (the word read as unsigned), U and V deinterleaved.  Plain torch ops on
+        the frame's device: a copy."""
+        sh = 16 - self.depth
+        code = lambda p: ((p.to(torch.int32) & 0xffff) >> sh).to(torch.int16)
+        uv = self.uv.unflatten(1, (self.w // 2, 2))
+        return YuvFrame(code(self.y), code(uv[..., 0]), code(uv[..., 1]), self.depth, self.subsampling)
+
+
+def read_yuv_sp(path, width, height, depth=10, subsampling='420', frames=None, start=0):
+    """A raw P010 / P012 / P210 / P212 file of `width` x `height` frames (per frame the Y plane, then the UV plane, little-endian words) ->
+    list of YuvSpFrame on the CPU (all of them, or the first `frames`; from frame `start` on).  As read_yuv: ONE buffer, pinned when a GPU is there, the planes
+    views of it.  ValueError: sides that do not fit, a file size that is not a whole number of frames, an unsupported depth / subsampling."""
+    if depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS:
+        raise ValueError(f'read_yuv_sp: semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth!r} bits at {subsampling!r}')
+    if not _extent_ok(height, width, subsampling):
+        raise ValueError(f'read_yuv_sp: {width} x {height} does not fit subsampling {subsampling}')
+    per = frame_bytes2(width, height, subsampling, depth)    # as many samples as the planar layout
+    size = os.path.getsize(path)
+    if size == 0 or size % per:
+        raise ValueError(f'read_yuv_sp: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
+    n = size // per - int(start) if frames is None else min(int(frames), size // per - int(start))
+    if n <= 0 or start < 0:
+        raise ValueError(f'read_yuv_sp: frames={frames}, start={start} of {size // per}')
+    buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    with open(path, 'rb') as f:
+        f.seek(int(start) * per)
+        got = f.readinto(buf.numpy())
+    if got != n * per:
+        raise ValueError(f'read_yuv_sp: short read of {path}')
+    ny, ch = 2 * width * height, height >> SHIFTS[subsampling][1]
+    out = []
+    for i in range(n):
+        fr = buf[i * per:(i + 1) * per]
+        out.append(YuvSpFrame(fr[:ny].view(torch.int16).view(height, width), fr[ny:].view(torch.int16).view(ch, width), depth, subsampling))
+    return out
+
+
+def write_yuv_sp(frames, path, append=False):
+    """Write YuvSpFrames (any device) to a raw P010-family file, one after the other: Y plane, UV plane, little-endian words."""
+    with open(path, 'ab' if append else 'wb') as f:
+        for fr in frames:
+            for p in fr.planes():
+                f.write(p.cpu().contiguous().numpy().astype('<i2', copy=False).tobytes())
 
 
 # ----------------------------------------------------------------------------------------------- the defining expressions (CPU, fp32)
@@ -551,8 +664,13 @@ class YuvBatch:
     `fill(dst, start, n)` converts frames start .. start + n straight into `dst` -- an (n, 3, H, W) fp32 view of an encode plan's input --
     with one launch on the current stream."""
 
+    frame_type = YuvFrame
+
     def __init__(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
-        fs = [_as_frame2(f) for f in frames]
+        fs = list(frames)
+        for f in fs:
+            if not isinstance(f, self.frame_type):
+                raise ValueError(f'expected a {self.frame_type.__name__}, got {type(f).__name__}')
         if not fs:
             raise ValueError('no frames')
         self.depth, self.subsampling = fs[0].depth, fs[0].subsampling
@@ -581,10 +699,51 @@ class YuvBatch:
         del keep
 
 
+def _plane_args_sp(frames):
+    """_plane_args2 for YuvSpFrames, as lvae_image_yuvsp_to_f32 / lvae_image_f32_to_yuvsp take them: (y, uv, y_row, uv_row, hw)."""
+    n = len(frames)
+    rows_ok = lambda p: p.stride(1) == 1 and p.stride(0) >= p.shape[1]
+    ps = [[p if rows_ok(p) else p.contiguous() for p in (getattr(f, k) for f in frames)] for k in ('y', 'uv')]
+    ptr = lambda q: (ctypes.c_void_p * n)(*[p.data_ptr() for p in q])
+    row = lambda q: (ctypes.c_long * n)(*[p.stride(0) for p in q])
+    hw = (ctypes.c_int * (2 * n))(*[v for f in frames for v in f.size])
+    return (ptr(ps[0]), ptr(ps[1]), row(ps[0]), row(ps[1]), hw), ps
+
+
+class YuvSpBatch(YuvBatch):
+    """YuvBatch for YuvSpFrames: the two planes of every frame go to the device as the file holds them, and `fill` is one
+    lvae_image_yuvsp_to_f32 launch -- no deinterleaved or shifted copy exists anywhere."""
+    frame_type = YuvSpFrame
+
+    def fill(self, dst, start=0, n=None):
+        from .. import _native
+        n = len(self.frames) - start if n is None else n
+        _, _, H, W = self.shape
+        assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
+        args, keep = _plane_args_sp(self.frames[start:start + n])
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _native.check(_native.lib().lvae_image_yuvsp_to_f32(
+                *args, n, self.depth, SUBSAMPLINGS.index(self.subsampling), SITINGS.index(self.siting), MATRICES2.index(self.matrix),
+                RANGES.index(self.range), CHROMA.index(self.chroma), dst.data_ptr(), dst.stride(0) if n > 1 else 3 * H * W, H, W, st),
+                'image_yuvsp_to_f32')
+        del keep
+
+
 def to_rgb01_any(frames, div=1, device=None, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
     """to_rgb01 for a list of YuvFrame of one depth and subsampling -> ((B, 3, H, W) fp32 RGB in [0, 1], [(h, w)]).  siting: 'center' |
     'left' (where the chroma samples lie horizontally; see the module docstring); matrix also 'bt2020'.  CPU frames with device=None: the
-    defining expression on the host.  Otherwise one upload of each frame's bytes and one kernel launch for the batch."""
+    defining expression on the host.  Otherwise one upload of each frame's bytes and one kernel launch for the batch.  A list of
+    YuvSpFrame is taken too: on the host through to_planar (the definition), on the device by its own kernel."""
+    frames = list(frames)
+    if frames and all(isinstance(f, YuvSpFrame) for f in frames):
+        if device is None and all(f.device.type == 'cpu' for f in frames):
+            return to_rgb01_any([f.to_planar() for f in frames], div, None, matrix, range, chroma, siting)
+        batch = YuvSpBatch(frames, div, next(f.device for f in frames if f.device.type != 'cpu') if device is None else device,
+                           matrix, range, chroma, siting)
+        out = torch.empty(batch.shape, dtype=torch.float32, device=batch.device)
+        batch.fill(out)
+        return out, batch.sizes
     fs = [_as_frame2(f) for f in frames]
     if not fs:
         raise ValueError('no frames')
@@ -607,12 +766,18 @@ def to_rgb01_any(frames, div=1, device=None, matrix='bt709', range='limited', ch
     return out, batch.sizes
 
 
-def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited'):
+def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar'):
     """from_rgb01 for YuvFrames: fp32 RGB images in [0, 1] -> a list of YuvFrame of `depth` and `subsampling` on the same device, the
     chroma sampled for `siting`.  x, sizes: as in from_rgb01; extents that do not fit the subsampling raise ValueError.  Device tensors: one
-    kernel launch for the batch on the current stream; CPU tensors: the defining expression."""
+    kernel launch for the batch on the current stream; CPU tensors: the defining expression.  layout 'semiplanar' (depth 10 | 12, '420' |
+    '422'): a list of YuvSpFrame holding the same codes, written by lvae_image_f32_to_yuvsp (CPU: to_semiplanar of the expression's frame)."""
     from .views import items, strided_batch
     _check2(depth, subsampling, siting, matrix, range)
+    if layout not in LAYOUTS:
+        raise ValueError(f'layout is one of {LAYOUTS}, got {layout!r}')
+    sp = layout == 'semiplanar'
+    if sp and (depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS):
+        raise ValueError(f'semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth} bits at {subsampling}')
     xs = items(x, 'x')
     if sizes is not None:
         if len(sizes) != len(xs):
@@ -624,7 +789,8 @@ def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', m
         raise ValueError(f'from_rgb01_any: sizes {[tuple(v.shape[1:]) for v in xs]} do not fit subsampling {subsampling}')
     device = xs[0].device
     if device.type == 'cpu':
-        return [YuvFrame(*rgb_to_yuv_expr2(v, depth, subsampling, siting, matrix, range), depth, subsampling) for v in xs]
+        outs = [YuvFrame(*rgb_to_yuv_expr2(v, depth, subsampling, siting, matrix, range), depth, subsampling) for v in xs]
+        return [f.to_semiplanar() for f in outs] if sp else outs
     from .. import _native
     B = len(xs)
     hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
@@ -636,9 +802,17 @@ def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', m
         if s_row < wmax or s_plane < span or (B > 1 and s_img < 2 * s_plane + span):
             keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in xs], hmax, wmax, device)
         new = lambda *s: torch.empty(*s, dtype=torch.uint8 if depth == 8 else torch.int16, device=device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        codes = (depth, SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix), RANGES.index(range))
+        if sp:
+            outs = [YuvSpFrame(new(h, w), new(h >> sy, w), depth, subsampling) for h, w in hw]
+            args, _ = _plane_args_sp(outs)
+            _native.check(_native.lib().lvae_image_f32_to_yuvsp(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[4], B, *codes,
+                                                                *args[:4], st), 'image_f32_to_yuvsp')
+            del keep
+            return outs
         outs = [YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling) for h, w in hw]
         args, _ = _plane_args2(outs)
-        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         _native.check(_native.lib().lvae_image_f32_to_yuv(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[6], B, depth,
                                                           SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix),
                                                           RANGES.index(range), *args[:6], st), 'image_f32_to_yuv')

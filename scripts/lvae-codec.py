@@ -11,6 +11,8 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv [--format nv12]
     python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 1920 1080 --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]
     python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]   # yuv420p10le ...
+    python scripts/lvae-codec.py encode-yuv IN.yuv OUT.lvys --size 1920 1080 --container [--layout p010] [--siting left] [--matrix bt2020]
+    python scripts/lvae-codec.py decode-yuv IN.lvys OUT.yuv [--layout p010]          # no colour flags: the container holds them
 
 Images whose sizes padded to the model's stride agree are coded as batches of up to --batch (lvae.evaluation.batch_same_size).  A .bits
 file is what compress_file writes; decode names every PNG after its .bits file.  --synthetic (on decode: seeded weights only) needs no
@@ -21,7 +23,11 @@ k becomes BITS/frame<k>.bits, a file compress_file could have written; --matrix 
 same --matrix and --range.  With --synthetic N, encode-yuv first writes N seeded frames of --size to IN.yuv.  --depth 10 | 12,
 --subsampling 422 | 444, --siting left or --matrix bt2020 select planar files with 16-bit little-endian samples above 8 bits
 (CodecBase.compress_yuv / decompress_yuv); none of them is stored either: decode-yuv needs the encoder's --depth and --siting too (it may
-ask for another depth or subsampling on purpose: the reconstruction is fp32)."""
+ask for another depth or subsampling on purpose: the reconstruction is fp32).  --layout p010 | p012 | p210 | p212: the raw file is
+semi-planar with the value in the high bits (what hardware decoders deliver); the name gives depth and subsampling.  --container:
+encode-yuv writes ONE self-describing file (CodecBase.compress_yuv_sequence, the LVYS container of lvae/utils/yuvseq.py) instead of a
+folder; decode-yuv recognises it by its magic, takes every parameter from its header and writes the source's layout unless --layout
+/ --format asks for another."""
 import argparse
 import os
 import sys
@@ -84,12 +90,33 @@ def decode(model, src, dst, batch, box=None):
     print(f'decoded {len(paths) + len(tiled)} files')
 
 
-def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None):
-    from lvae.utils.yuv import read_yuv, read_yuv420
+def _is_sequence(path):
+    from lvae.utils.yuvseq import MAGIC
+    if not os.path.isfile(path):
+        return False
+    with open(path, 'rb') as f:
+        return f.read(4) == MAGIC
+
+
+def encode_yuv_container(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False):
+    kw = dict(depth=8, subsampling='420', siting='center', layout=fmt) if layout is None else dict(layout, layout='semiplanar' if sp else 'planar')
+    blob = model.compress_yuv_sequence(src, size[0], size[1], frames=frames, lmb=lmb, max_batch=batch, **kw, **colour)
+    Path(dst).write_bytes(blob)
+    print(f'encoded {model.yuv_sequence_info(blob)["frames"]} frames -> {len(blob)} bytes')
+
+
+def decode_yuv_container(model, src, dst, batch, layout=None):
+    n = model.decompress_yuv_sequence(Path(src).read_bytes(), layout=layout, out_path=dst, max_batch=batch)
+    print(f'decoded {n} frames')
+
+
+def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False):
+    from lvae.utils.yuv import read_yuv, read_yuv420, read_yuv_sp
     if layout is None:
         fs, compress = read_yuv420(src, size[0], size[1], fmt, frames=frames), model.compress_yuv420
     else:
-        fs = read_yuv(src, size[0], size[1], layout['subsampling'], layout['depth'], frames=frames)
+        fs = (read_yuv_sp(src, size[0], size[1], layout['depth'], layout['subsampling'], frames=frames) if sp
+              else read_yuv(src, size[0], size[1], layout['subsampling'], layout['depth'], frames=frames))
         compress = lambda chunk, **kw: model.compress_yuv(chunk, siting=layout['siting'], **kw)
     total = 0
     for o in range(0, len(fs), batch):
@@ -100,26 +127,30 @@ def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=No
     print(f'encoded {len(fs)} frames -> {total} bytes')
 
 
-def decode_yuv(model, src, dst, fmt, batch, colour, layout=None):
-    from lvae.utils.yuv import write_yuv, write_yuv420
+def decode_yuv(model, src, dst, fmt, batch, colour, layout=None, sp=False):
+    from lvae.utils.yuv import write_yuv, write_yuv420, write_yuv_sp
     paths = sorted(Path(src).glob('*.bits'))
     for o in range(0, len(paths), batch):
         blobs = [p.read_bytes() for p in paths[o:o + batch]]
         if layout is None:
             write_yuv420(model.decompress_yuv420(blobs, fmt=fmt, matrix=colour['matrix'], range=colour['range']), dst, append=o > 0)
+        elif sp:
+            write_yuv_sp(model.decompress_yuv(blobs, matrix=colour['matrix'], range=colour['range'], layout='semiplanar', **layout), dst, append=o > 0)
         else:
             write_yuv(model.decompress_yuv(blobs, matrix=colour['matrix'], range=colour['range'], **layout), dst, append=o > 0)
     print(f'decoded {len(paths)} frames')
 
 
-def synthetic_yuv(path, n, size, fmt, colour, layout=None):
+def synthetic_yuv(path, n, size, fmt, colour, layout=None, sp=False):
     """N seeded frames of size (w, h) as a raw .yuv file: seeded RGB images through the defining host conversion."""
     import seeded_init
-    from lvae.utils.yuv import from_rgb01, from_rgb01_any, write_yuv, write_yuv420
+    from lvae.utils.yuv import from_rgb01, from_rgb01_any, write_yuv, write_yuv420, write_yuv_sp
     w, h = size
     rgb = [torch.from_numpy(seeded_init.synthetic_image_u8(h, w, 300 + i)).permute(2, 0, 1).float().div(255) for i in range(n)]
     if layout is None:
         write_yuv420(from_rgb01(rgb, fmt=fmt, matrix=colour['matrix'], range=colour['range']), path)
+    elif sp:
+        write_yuv_sp(from_rgb01_any(rgb, matrix=colour['matrix'], range=colour['range'], layout='semiplanar', **layout), path)
     else:
         write_yuv(from_rgb01_any(rgb, matrix=colour['matrix'], range=colour['range'], **layout), path)
 
@@ -147,9 +178,23 @@ def main():
     ap.add_argument('--siting', type=str, default='center', choices=['center', 'left'], help="encode-yuv / decode-yuv: where the chroma samples lie; 'left' is H.264 / HEVC co-sited chroma")
     ap.add_argument('--range', type=str, default='limited', choices=['limited', 'full'])
     ap.add_argument('--chroma', type=str, default='bilinear', choices=['nearest', 'bilinear'], help='encode-yuv: the chroma upsampling filter')
+    ap.add_argument('--layout', type=str, default=None, choices=['p010', 'p012', 'p210', 'p212'],
+                    help='encode-yuv / decode-yuv: the raw file is semi-planar with the value in the high bits; sets --depth and --subsampling')
+    ap.add_argument('--container', action='store_true', help='encode-yuv: write one self-describing .lvys file to DST instead of a folder of .bits files')
     args = ap.parse_args()
     if args.command in ('encode-yuv', 'decode-yuv'):
+        if args.command == 'decode-yuv' and _is_sequence(args.src):      # every parameter comes from the container's header
+            model = load_model(args.model, args.synthetic, torch.device(args.device))
+            decode_yuv_container(model, args.src, args.dst, args.batch,
+                                 'semiplanar' if args.layout else args.format if args.format != 'i420' else None)
+            return
         colour = dict(matrix=args.matrix, range=args.range, chroma=args.chroma)
+        sp = args.layout is not None
+        if sp:
+            from lvae.utils.yuv import SP_LAYOUTS
+            if args.format != 'i420':
+                ap.error('--layout and --format nv12 exclude each other')
+            args.depth, args.subsampling = SP_LAYOUTS[args.layout]
         layout = None                                        # the 8-bit 4:2:0 centre-sited path unless one option asks for more
         if (args.depth, args.subsampling, args.siting) != (8, '420', 'center') or args.matrix == 'bt2020':
             if args.format != 'i420':
@@ -158,14 +203,16 @@ def main():
         if args.command == 'encode-yuv':
             if args.size is None:
                 ap.error('encode-yuv needs --size W H')
-            os.makedirs(args.dst, exist_ok=True)
+            if not args.container:
+                os.makedirs(args.dst, exist_ok=True)
             if args.synthetic:
-                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour, layout)
+                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour, layout, sp)
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            encode_yuv(model, args.src, args.dst, args.size, args.format, args.frames, args.lmb, args.batch, colour, layout)
+            (encode_yuv_container if args.container else encode_yuv)(model, args.src, args.dst, args.size, args.format, args.frames, args.lmb,
+                                                                     args.batch, colour, layout, sp)
         else:
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            decode_yuv(model, args.src, args.dst, args.format, args.batch, colour, layout)
+            decode_yuv(model, args.src, args.dst, args.format, args.batch, colour, layout, sp)
         return
     os.makedirs(args.dst, exist_ok=True)
     if args.synthetic and args.command == 'encode':

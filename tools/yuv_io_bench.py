@@ -4,13 +4,20 @@ lvae_image_f32_to_yuv420 on the device), and one evaluation step (lvae.evaluatio
 conversions and the squared errors on the host.  Workloads: 8 frames of 512 x 768 and 2 of 1080 x 1920 (which pad to 1088 x 1920); seeded
 synthetic frames, BT.709 limited range, bilinear chroma.  Rows (a) - (c) are repeated for planar 10-bit frames (utils.yuv.YuvFrame, centre
 siting; to_rgb01_any / from_rgb01_any, lvae_image_yuv_to_f32 / lvae_image_f32_to_yuv): 2 frames of 1080 x 1920 at 4:2:0 and 8 of 512 x 768 at
-4:4:4, against the same numpy host conversion on 16-bit samples.
+4:4:4, against the same numpy host conversion on 16-bit samples.  The last rows are 2 frames of 1080 x 1920 P010 (utils.yuv.YuvSpFrame:
+semi-planar, the value in the high bits), measured against what a user had before the semi-planar kernels: numpy deinterleave and shift
+to planar YuvFrames, then the planar upload and kernel -- and, on the way out, the planar kernel, the copies and a numpy interleave and shift.
   (a) host_in  : numpy fp32 conversion + edge padding to multiples of 64, torch.from_numpy(...).to(device)
   (b) yuv_in   : to_rgb01(frames, div=64, device)             -- frames as read_yuv420 leaves them (views of one pinned buffer)
   (c) host_out : x.cpu(), then the numpy fp32 forward conversion to I420 bytes
       yuv_out  : from_rgb01(x) + one device-to-host copy per plane
   (d) eval_step     : yuv_evaluate(model, file, ...) with qarv_base (bench.py's seeded model)
       eval_step_host: the same frames through host_in -> compress_batch -> decompress_batch -> host_out, numpy int64 squared errors
+  (e) planar_in : numpy deinterleave + shift of the P010 planes, then to_rgb01_any on the planar frames
+      sp_in     : to_rgb01_any on the P010 frames as read_yuv_sp leaves them (lvae_image_yuvsp_to_f32)
+      planar_out: from_rgb01_any(x) + one device-to-host copy per plane, then numpy shift + interleave to P010 words
+      sp_out    : from_rgb01_any(x, layout='semiplanar') + one device-to-host copy per plane (lvae_image_f32_to_yuvsp)
+      Both sides of (e) give the same bits (asserted).
 The variants of a group alternate step by step in one process, the device synchronised after every call; medians, min, max in ms.  The
 numpy conversions follow the same formulas as lvae/utils/yuv.py but are not bit-identical to it (numpy may contract nothing either, yet
 its chroma filter is written in floats); the outputs are compared within 1e-6 / one byte.  One JSON line.
@@ -30,6 +37,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 WORKLOADS = {'b8_512x768': (8, 512, 768), 'b2_1080x1920': (2, 1080, 1920)}
+SP_WORKLOADS = {'b2_1080x1920_p010': (2, 1080, 1920, 10, '420')}
 HBD_WORKLOADS = {'b2_1080x1920_10bit_420': (2, 1080, 1920, 10, '420'), 'b8_512x768_10bit_444': (8, 512, 768, 10, '444')}
 KR, KB = 0.2126, 0.0722
 KG = 1 - KR - KB
@@ -107,7 +115,8 @@ def main():
     import bench
     import seeded_init
     from lvae.evaluation import yuv_evaluate
-    from lvae.utils.yuv import from_rgb01, from_rgb01_any, read_yuv, read_yuv420, to_rgb01, to_rgb01_any, write_yuv, write_yuv420
+    from lvae.utils.yuv import (YuvFrame, from_rgb01, from_rgb01_any, read_yuv, read_yuv420, read_yuv_sp, to_rgb01, to_rgb01_any, write_yuv,
+                                write_yuv420, write_yuv_sp)
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
@@ -204,6 +213,43 @@ def main():
         row['out_max_code_diff'] = max(int(np.abs(c.astype(np.int64) - d.numpy().astype(np.int64)).max()) for cs, ds in zip(box['c'], box['d']) for c, d in zip(cs, ds))
         assert row['out_max_code_diff'] <= 1
         row['host_out_over_yuv_out'] = round(row['host_out']['median'] / row['yuv_out']['median'], 2)
+        res[name] = row
+    for name, (B, H, W, depth, sub) in SP_WORKLOADS.items():
+        path = tmp / f'{name}.yuv'
+        rgb = [torch.from_numpy(seeded_init.synthetic_image_u8(H, W, seed=1000 + i)).permute(2, 0, 1).float().div(255) for i in range(B)]
+        write_yuv_sp(from_rgb01_any(rgb, depth=depth, subsampling=sub, layout='semiplanar'), path)
+        frames = read_yuv_sp(path, W, H, depth, sub)
+        sizes, sh = [(H, W)] * B, 16 - depth
+        box, row = {}, {}
+
+        def host_planar(f):
+            y, uv = f.y.numpy().view(np.uint16), f.uv.numpy().view(np.uint16)
+            return YuvFrame(y >> sh, np.ascontiguousarray(uv[:, 0::2]) >> sh, np.ascontiguousarray(uv[:, 1::2]) >> sh, depth, sub)
+
+        def planar_in():
+            box['a'] = to_rgb01_any([host_planar(f) for f in frames], div=64, device=dev)[0]
+
+        def sp_in():
+            box['b'] = to_rgb01_any(frames, div=64, device=dev)[0]
+        row.update(alternate({'planar_in': planar_in, 'sp_in': sp_in}))
+        assert torch.equal(box['a'], box['b'])
+        row['planar_in_over_sp_in'] = round(row['planar_in']['median'] / row['sp_in']['median'], 2)
+        x = box['b']
+
+        def planar_out():
+            out = []
+            for f in from_rgb01_any(x, sizes, depth=depth, subsampling=sub):
+                y, u, v = (p.cpu().numpy().view(np.uint16) for p in f.planes())
+                uv = np.empty((u.shape[0], 2 * u.shape[1]), np.uint16)
+                uv[:, 0::2], uv[:, 1::2] = u << sh, v << sh
+                out.append((y << sh, uv))
+            box['c'] = out
+
+        def sp_out():
+            box['d'] = [[p.cpu() for p in f.planes()] for f in from_rgb01_any(x, sizes, depth=depth, subsampling=sub, layout='semiplanar')]
+        row.update(alternate({'planar_out': planar_out, 'sp_out': sp_out}))
+        assert all(np.array_equal(c, d.numpy().view(np.uint16)) for cs, ds in zip(box['c'], box['d']) for c, d in zip(cs, ds))
+        row['planar_out_over_sp_out'] = round(row['planar_out']['median'] / row['sp_out']['median'], 2)
         res[name] = row
     print(json.dumps(res))
 
