@@ -660,6 +660,44 @@ int lvae_tile_stitch(const float* const* tiles, long tile_plane, long tile_row, 
 /* Bytes of scratch lvae_tile_stitch needs; 0 when rows or cols <= 0. */
 size_t lvae_tile_stitch_workspace_bytes(int rows, int cols);
 
+/* ---- Reduced-resolution coding: a separable, antialiased resampler (csrc/resample.hip; lvae/utils/resample.py states the window rule,
+ * the filters and the tables, and holds the fp64 reference).  All B images of a call share the geometry (h_in, w_in) -> (h_out, w_out)
+ * and one pair of DEVICE-resident tables, which the caller owns.  Per axis n_in -> n_out: start[n_out] (int32) and wgt[n_out][taps]
+ * (fp32, rows zero-padded to `taps`); output i of the axis is sum_j wgt[i][j] * x[min(start[i] + j, n_in - 1)], j ascending.  start
+ * must not decrease.  An axis with n_out == n_in is NOT filtered: its table pointers are null and its taps 0 (a bit copy on that
+ * axis); any other axis needs 1 <= taps <= 64.  yspan: the largest number of input rows any 16 consecutive output rows read,
+ * max_i(min(start[min(i + 15, h_out - 1)] + ytaps, h_in) - start[i]) (ignored when ytaps == 0): the host sizes a workgroup's tile from
+ * it so that its LDS stays within 64 KiB (two or more workgroups per CU), and a geometry whose narrowest tile does not fit returns -22.
+ * A resized pixel is the horizontal pass (fp32, taps ascending, one fused multiply-add per tap from 0) followed by the vertical pass
+ * (the same) over the horizontally filtered rows, which stay in LDS: no intermediate image goes to memory and there are no atomics, so
+ * two calls give the same bits.  One launch per 16 images (descriptors as kernel arguments, as the image entries above).
+ * Whatever the tables hold, nothing outside a source or destination extent is read or written: every index is clamped to its extent
+ * (a table that breaks the rules above gives wrong pixels, not a fault).  Every access is a byte or an fp32 scalar: bases and row
+ * strides may have any alignment.
+ * The 8-bit side is interleaved RGB (HOST arrays of DEVICE addresses and row strides in bytes, read before the call returns); an fp32
+ * source is a strided NCHW view, element (b, c, y, x) at src[b*src_img + c*src_plane + y*src_row + x] (crops of a decoder's padded batch
+ * are read in place); an fp32 destination is B images of 3 planes of the canvas (H, W) >= (h_out, w_out), dst_img elements apart:
+ * canvas pixel (y, x) holds resized pixel (min(y, h_out - 1), min(x, w_out - 1)) (replicate padding, as lvae_image_u8_to_f32).
+ * -22 before any HIP call: a null pointer (an entry of a HOST array included), B <= 0, a size <= 0, a canvas below (h_out, w_out), taps
+ * outside the rules above or table pointers that do not go with them, yspan <= 0 on a filtered vertical axis, a ratio n_in / n_out
+ * outside [1/8, 8], strides that do not hold their extents, a tile that does not fit.
+ * Added without a change to lvae_abi_version(), like the image entries above.
+ *
+ * lvae_resample_u8_to_f32: source pixels are (float)v / 255 (IEEE division); the result is clamped to [0, 1].  Equal, bit for bit, to
+ * lvae_resample_f32 with clamp != 0 applied to the output of lvae_image_u8_to_f32. */
+int lvae_resample_u8_to_f32(const uint8_t* const* src, const long* src_row, int B, int h_in, int w_in, int h_out, int w_out,
+                            const int* ystart, const float* ywgt, int ytaps, int yspan, const int* xstart, const float* xwgt, int xtaps,
+                            float* dst, long dst_img, int H, int W, void* stream);
+/* lvae_resample_f32_to_u8: byte c of pixel (y, x) of image b = rint(clamp(v, 0, 1) * 255), ties to even, NaN -> 0, for y < h_out,
+ * x < w_out (dst_row[b] >= 3 * w_out bytes).  Equal, bit for bit, to lvae_image_f32_to_u8 applied to the output of lvae_resample_f32. */
+int lvae_resample_f32_to_u8(const float* src, long src_img, long src_plane, long src_row, int B, int h_in, int w_in, int h_out, int w_out,
+                            const int* ystart, const float* ywgt, int ytaps, int yspan, const int* xstart, const float* xwgt, int xtaps,
+                            uint8_t* const* dst, const long* dst_row, void* stream);
+/* lvae_resample_f32: fp32 in, fp32 out; clamp != 0 clamps the result to [0, 1] (NaN -> 0). */
+int lvae_resample_f32(const float* src, long src_img, long src_plane, long src_row, int B, int h_in, int w_in, int h_out, int w_out,
+                      const int* ystart, const float* ywgt, int ytaps, int yspan, const int* xstart, const float* xwgt, int xtaps,
+                      int clamp, float* dst, long dst_img, int H, int W, void* stream);
+
 /* Stream ordering for launch plans with independent branches (lvae/engine.py: Plan.fork / Plan.join): an event without timing, and
  * "work enqueued on to_stream from now on runs after the work enqueued on from_stream so far" (hipEventRecord + hipStreamWaitEvent). */
 void* lvae_event_create(void);

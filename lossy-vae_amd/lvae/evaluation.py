@@ -94,6 +94,23 @@ def _eval_one_tiled(model, impath, tile, overlap, ms=False):
     return out
 
 
+def _eval_one_scaled(model, impath, scale, resample, ms=False):
+    """_eval_one through reduced-resolution coding: compress_scaled / decompress_scaled(out='f32'); the bits are the whole container's,
+    counted against the ORIGINAL pixel count, and the errors are taken at the original resolution."""
+    from .utils.image import load_u8, to_float01
+    dev = _u8_codec(model)
+    if dev is None or not hasattr(model, 'compress_scaled'):
+        raise ValueError('scale=...: the model has no reduced-resolution coding (compress_scaled) or is not on a GPU')
+    u8 = load_u8(impath).to(dev, non_blocking=True)
+    blob = model.compress_scaled([u8], scale=scale, filter=resample)[0]
+    fake = model.decompress_scaled([blob], out='f32')[0]
+    real = to_float01([u8], device=dev)[0][0]
+    out = _stats(len(blob) * 8, real, _mse(real, fake))
+    if ms:
+        out['ms-ssim'] = _ms_ssim([real], [fake])[0]
+    return out
+
+
 def _eval_one(model, impath, tmp_bits_dir, tag='', ms=False):
     from PIL import Image
     tmp_bits_path = tmp_bits_dir / f'{impath.stem}{tag}.bits'
@@ -116,12 +133,16 @@ def _eval_one(model, impath, tmp_bits_dir, tag='', ms=False):
 
 
 @torch.no_grad()
-def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=None, overlap=0):
+def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=None, overlap=0, scale=None, resample='lanczos3'):
     """dict {bpp, mse, psnr}: dataset means of per-image values (evaluation.py:59-66).  metrics=('psnr', 'ms-ssim') adds the key
     'ms-ssim' (lvae.metrics.ms_ssim, mean over images); the other keys are the same floats either way.  tile=(th, tw): every image is
     coded in tiles (compress_tiled / decompress_tiled(out='f32') with `overlap`) and bpp counts the whole tiled container; tile=None
-    is the whole-image path, float for float."""
+    is the whole-image path, float for float.  scale=S: every image is coded at reduced resolution (compress_scaled(scale=S, filter=resample)
+    / decompress_scaled(out='f32')): bpp counts the whole scaled container against the ORIGINAL pixel count, mse and psnr are taken at the
+    original resolution; scale=None changes nothing.  scale together with tile raises ValueError."""
     ms = _want_ms_ssim(metrics)
+    if scale is not None and tile is not None:
+        raise ValueError('imcoding_evaluate: scale and tile exclude each other (scaled and tiled containers are not combined)')
     assert hasattr(model, 'compress_file') and hasattr(model, 'decompress_file')
     img_paths = _list_images(dataset)
     tmp_bits_dir = Path(gettempdir())
@@ -131,7 +152,10 @@ def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=No
         from tqdm import tqdm
         it = tqdm(img_paths, ascii=True)
     for impath in it:
-        stats = _eval_one(model, impath, tmp_bits_dir, ms=ms) if tile is None else _eval_one_tiled(model, impath, tile, overlap, ms=ms)
+        if scale is not None:
+            stats = _eval_one_scaled(model, impath, scale, resample, ms=ms)
+        else:
+            stats = _eval_one(model, impath, tmp_bits_dir, ms=ms) if tile is None else _eval_one_tiled(model, impath, tile, overlap, ms=ms)
         n += 1
         for k, v in stats.items():      # timm AverageMeter: running sum / count
             sums[k] += v

@@ -929,6 +929,100 @@ class CodecBase(nn.Module):
             save_u8(x if out == 'u8' else self._decode_tiled(blob, box, 'u8', max_batch), png_path)
         return x
 
+    # ---- reduced-resolution coding (lvae/utils/resample.py: the resampler's definition and the `LVRS` container; csrc/resample.hip: the
+    # kernels).  An image is resampled where the encode plan reads its input, coded at the smaller size by the unchanged path, and
+    # resampled back from the decoder's padded batch where it lies; the payload is the model's own blob for the coded-resolution image.
+    @torch.no_grad()
+    def compress_scaled(self, images, scale=None, size=None, filter='lanczos3', lmb=None):
+        """A list of (h, w, 3) uint8 images of ONE size (anything compress_images takes) -> list of bytes, one scaled container
+        (utils.resample.pack_scaled) per image.  Exactly one of `scale` -- the coded size is (max(1, round(h * scale)), max(1, round(w *
+        scale))) -- and `size` = (h, w) of the coded image; ValueError otherwise, or for a ratio outside [1/8, 8] on an axis.  The images are
+        uploaded once, as bytes; lvae_resample_u8_to_f32 resamples them (`filter`: 'bilinear' | 'bicubic' | 'lanczos3'), clamped to [0, 1]
+        and replicate-padded, into each pipeline group's plan input.  The payload is the blob of the model's float path on
+        utils.image.resize(to_float01(img), coded size, clamp=True), replicate-padded -- the resampled image is never rounded to bytes;
+        with scale=1.0 it is compress_images' bytes.
+        lmb: as in compress_images."""
+        from ..utils import resample
+        from ..utils.image import ScaledU8Batch, _as_u8
+        resample._filter(filter)
+        ts = [_as_u8(im) for im in images]
+        if not ts:
+            raise ValueError('compress_scaled: no images')
+        h, w = int(ts[0].shape[0]), int(ts[0].shape[1])
+        coded = resample.scaled_size(h, w, scale=scale, size=size)
+        batch = ScaledU8Batch(ts, coded, filter, self.max_stride, self._dummy.device)
+        return [resample.pack_scaled(filter, (h, w), coded, blob) for blob in self._compress_byte_batch(batch, lmb, 'compress_scaled')]
+
+    def scaled_info(self, blob):
+        """utils.resample.scaled_info (header parsing only, no GPU) plus 'lmb': the lambda the payload was coded at on variable-rate
+        models, else None."""
+        from ..utils import resample
+        info, payload = resample.unpack_scaled(blob)
+        info['lmb'] = self._blob_lmb(payload) if self.variable_rate else None
+        return info
+
+    @torch.no_grad()
+    def decompress_scaled(self, blobs, out='u8', size=None):
+        """compress_scaled containers -> the images at their ORIGINAL sizes, on the model's device: out='u8': (h, w, 3) uint8 tensors
+        (rint(clamp(v, 0, 1) * 255), ties to even); out='f32': (1, 3, h, w) fp32 tensors, not clamped.  size: None, 'coded' (the coded
+        image, no resampling: decompress_images of the payload for out='u8') or (h, w), a preview at that size.  Payloads of one latent
+        shape decode as one batch, and the containers' filters resample the decoder's padded batch in place (lvae_resample_f32_to_u8 /
+        lvae_resample_f32).  ValueError: a malformed container, a payload whose size is not the header's coded size."""
+        from ..utils import resample
+        from ..utils.image import _resample_f32, to_u8
+        if out not in ('u8', 'f32'):
+            raise ValueError(f"out is 'u8' or 'f32', got {out!r}")
+        if size is not None and size != 'coded':
+            size = tuple(int(v) for v in size)
+            if len(size) != 2:
+                raise ValueError(f"size is None, 'coded' or (h, w), got {size!r}")
+        infos, bodies, groups = [], [], {}
+        for i, b in enumerate(blobs):
+            info, payload = resample.unpack_scaled(b)
+            body, coded, key = self._unpack_blob(payload)
+            if tuple(coded) != info['coded']:
+                raise ValueError(f"scaled container {i}: the payload holds a {tuple(coded)} image, the header says {info['coded']}")
+            if size not in (None, 'coded'):
+                resample.check_ratio(info['coded'][0], size[0])
+                resample.check_ratio(info['coded'][1], size[1])
+            infos.append(info)
+            bodies.append(body)
+            groups.setdefault(key, []).append(i)           # as _decompress_blobs: payloads that share a latent shape are one batch
+        result = [None] * len(blobs)
+        for idxs in groups.values():
+            x = self.decompress_batch([bodies[i] for i in idxs])
+            if size == 'coded':
+                coded = [infos[i]['coded'] for i in idxs]
+                items = to_u8(x, coded) if out == 'u8' else [x[r:r + 1, :, :ch, :cw] for r, (ch, cw) in enumerate(coded)]
+                for i, item in zip(idxs, items):
+                    result[i] = item
+                continue
+            calls = {}                                     # one resampling call per (coded size, target size, filter) of the batch
+            for r, i in enumerate(idxs):
+                target = infos[i]['size'] if size is None else size
+                calls.setdefault((infos[i]['coded'], target, infos[i]['filter']), []).append((r, i))
+            for ((ch, cw), target, filt), rows in calls.items():
+                got = _resample_f32([x[r, :, :ch, :cw] for r, _ in rows], target, filt, False, out)
+                for k, (_, i) in enumerate(rows):
+                    result[i] = got[k] if out == 'u8' else got[k:k + 1]
+        return result
+
+    def compress_file_scaled(self, img_path, out_path, scale=None, size=None, filter='lanczos3', lmb=None):
+        blob = self.compress_scaled([img_path], scale=scale, size=size, filter=filter, lmb=lmb)[0]
+        with open(out_path, 'wb') as f:
+            f.write(blob)
+        return len(blob)
+
+    def decompress_file_scaled(self, bits_path, png_path=None, out='u8', size=None):
+        """A compress_file_scaled file -> the image as decompress_scaled returns it; png_path: also written as a PNG."""
+        from ..utils.image import save_u8
+        with open(bits_path, 'rb') as f:
+            blob = f.read()
+        x = self.decompress_scaled([blob], out=out, size=size)[0]
+        if png_path is not None:
+            save_u8(x if out == 'u8' else self.decompress_scaled([blob], out='u8', size=size)[0], png_path)
+        return x
+
     # ---- the reference's single-image and file API, on the batch interfaces.  A variable-rate model adds `lmb` to the compress side
     @torch.no_grad()
     def compress(self, im):

@@ -146,6 +146,144 @@ def to_u8(x, sizes=None):
     return outs
 
 
+# ---- the resampler of reduced-resolution coding (lvae/utils/resample.py: the definition; csrc/resample.hip: the kernels)
+_AXIS_TABLES = {}
+
+
+def _axis_on_device(n_in, n_out, filter, device):
+    """One axis of a resampling call as the native entries take it: (start pointer, weights pointer, taps, span of a 16-row tile),
+    all 0 / None for an axis that keeps its size.  The device tables are built once per (n_in, n_out, filter, device) and kept."""
+    from . import resample
+    resample.check_ratio(n_in, n_out)
+    if n_in == n_out:
+        resample._filter(filter)
+        return None, None, 0, 0
+    key = (int(n_in), int(n_out), filter, str(device))
+    hit = _AXIS_TABLES.get(key)
+    if hit is None:
+        start, wgt = resample.axis_table(n_in, n_out, filter)
+        span = resample.tile_span(start, wgt.shape[1], n_in)
+        hit = _AXIS_TABLES[key] = (torch.from_numpy(start).to(device), torch.from_numpy(wgt).contiguous().to(device), int(wgt.shape[1]), span)
+    return hit[0].data_ptr(), hit[1].data_ptr(), hit[2], hit[3]
+
+
+def _tables(h_in, w_in, h_out, w_out, filter, device):
+    """The seven table arguments of lvae_resample_*: ystart, ywgt, ytaps, yspan, xstart, xwgt, xtaps."""
+    return _axis_on_device(h_in, h_out, filter, device) + _axis_on_device(w_in, w_out, filter, device)[:3]
+
+
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _u8_descriptors(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), (ctypes.c_long * len(ts))(*[t.stride(0) for t in ts])
+
+
+def _resample_f32(xs, size, filter, clamp, out, canvas=None):
+    """A list of (3, h, w) fp32 device views of ONE size -> resized to `size`: out='f32': a (B, 3, H, W) tensor (canvas (H, W) >= size,
+    replicate-padded; default: size itself); out='u8': a list of (h, w, 3) uint8 tensors.  Views cut from one tensor with common
+    strides (crops of a decoder's padded batch) are read in place."""
+    from .. import _native
+    from .views import strided_batch
+    device = xs[0].device
+    B, (h_in, w_in), (h_out, w_out) = len(xs), (int(xs[0].shape[1]), int(xs[0].shape[2])), (int(size[0]), int(size[1]))
+    tabs = _tables(h_in, w_in, h_out, w_out, filter, device)
+    lib = _native.lib()
+    with torch.cuda.device(device):
+        keep, px, (s_img, s_plane, s_row) = strided_batch(xs, h_in, w_in, device)
+        span = (h_in - 1) * s_row + w_in
+        if B > 1 and s_img < 2 * s_plane + span:         # views that overlap as a batch are packed instead
+            keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in xs], h_in, w_in, device)
+        s_img = s_img if B > 1 else 3 * s_plane
+        if out == 'u8':
+            outs = [torch.empty(h_out, w_out, 3, dtype=torch.uint8, device=device) for _ in range(B)]
+            dst, rows = _u8_descriptors(outs)
+            _native.check(lib.lvae_resample_f32_to_u8(px, s_img, s_plane, s_row, B, h_in, w_in, h_out, w_out, *tabs, dst, rows, _stream(device)),
+                          'resample_f32_to_u8')
+        else:
+            H, W = (h_out, w_out) if canvas is None else canvas
+            outs = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
+            _native.check(lib.lvae_resample_f32(px, s_img, s_plane, s_row, B, h_in, w_in, h_out, w_out, *tabs, int(bool(clamp)), outs.data_ptr(),
+                                                3 * H * W, H, W, _stream(device)), 'resample_f32')
+    del keep
+    return outs
+
+
+class ScaledU8Batch(U8Batch):
+    """B uint8 images of ONE size on one device, coded at `coded` = (h, w): what CodecBase.compress_scaled hands to compress_batch as `u8=`.
+    `sizes` are the coded sizes (what the models' containers record), `shape` the coded canvas; `fill` resamples images start .. start + n
+    straight into an encode plan's input -- v / 255, `filter`, clamped to [0, 1], replicate-padded -- with one launch
+    (lvae_resample_u8_to_f32).  With coded == the images' size that is lvae_image_u8_to_f32's result, bit for bit."""
+
+    def __init__(self, images, coded, filter, div, device):
+        ts = [_as_u8(im) for im in images]
+        if not ts:
+            raise ValueError('no images')
+        self.src_size = (int(ts[0].shape[0]), int(ts[0].shape[1]))
+        if any((int(t.shape[0]), int(t.shape[1])) != self.src_size for t in ts):
+            raise ValueError('the images of one scaled call share one size')
+        super().__init__(ts, 1, device)
+        self.filter = filter
+        self.sizes = [(int(coded[0]), int(coded[1]))] * len(ts)
+        self.shape = (len(ts), 3) + _canvas(self.sizes, div)
+        self._tabs = _tables(*self.src_size, *self.sizes[0], filter, self.device)
+
+    def fill(self, dst, start=0, n=None):
+        from .. import _native
+        n = len(self.images) - start if n is None else n
+        _, _, H, W = self.shape
+        assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
+        src, rows = _u8_descriptors(self.images[start:start + n])
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().lvae_resample_u8_to_f32(src, rows, n, *self.src_size, *self.sizes[0], *self._tabs, dst.data_ptr(),
+                                                                dst.stride(0) if n > 1 else 3 * H * W, H, W, _stream(self.device)),
+                          'resample_u8_to_f32')
+
+
+def resize(x, size, filter='lanczos3', clamp=False, out='f32', device=None):
+    """Resize images to size = (h, w) with the separable, antialiased resampler lvae/utils/resample.py defines (filter: 'bilinear' |
+    'bicubic' | 'lanczos3'; pixel-centre alignment; an axis that keeps its size is copied, not filtered).  x: a (B, 3, h, w) fp32 tensor,
+    or a list of (h, w, 3) uint8 images of ONE size (v / 255 first).  clamp: clamp the result to [0, 1] (bicubic and Lanczos overshoot).
+    -> out='f32': a (B, 3, H, W) fp32 tensor; out='u8': a list of (H, W, 3) uint8 tensors, rint(clamp(v, 0, 1) * 255), ties to even.
+    Inputs on a GPU (or `device`) run the kernels of csrc/resample.hip, one launch per 16 images on the current stream; CPU inputs take
+    resample.resize_reference (fp64) cast to fp32.  ValueError: an unknown filter or out, a ratio outside [1/8, 8] on an axis."""
+    from . import resample
+    if out not in ('u8', 'f32'):
+        raise ValueError(f"resize: out is 'u8' or 'f32', got {out!r}")
+    resample._filter(filter)
+    h, w = (int(v) for v in size)
+    u8_in = not torch.is_tensor(x)
+    if u8_in:
+        ts = [_as_u8(im) for im in x]
+        if not ts or any(t.shape != ts[0].shape for t in ts):
+            raise ValueError('resize: a list holds (h, w, 3) uint8 images of one size')
+        h_in, w_in = int(ts[0].shape[0]), int(ts[0].shape[1])
+        if device is None:
+            device = next((t.device for t in ts if t.device.type != 'cpu'), torch.device('cpu'))
+    else:
+        if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or x.shape[0] == 0:
+            raise ValueError(f'resize: expected a (B, 3, h, w) fp32 tensor, got {x.dtype} {tuple(x.shape)}')
+        h_in, w_in = int(x.shape[2]), int(x.shape[3])
+        device = x.device if device is None else device
+    device = torch.device(device)
+    resample.check_ratio(h_in, h)
+    resample.check_ratio(w_in, w)
+    if device.type == 'cpu':
+        x01 = to_float01(ts)[0] if u8_in else x
+        y = torch.from_numpy(resample.resize_reference(x01.numpy(), h, w, filter, clamp=clamp).astype(np.float32))
+        return y if out == 'f32' else to_u8(y)
+    if u8_in and out == 'f32' and clamp:                 # the encoder's path: bytes in, one launch
+        batch = ScaledU8Batch(ts, (h, w), filter, 1, device)
+        y = torch.empty(batch.shape, dtype=torch.float32, device=device)
+        batch.fill(y)
+        return y
+    x01 = to_float01(ts, device=device)[0] if u8_in else x.to(device)
+    if x01.stride(3) != 1:
+        x01 = x01.contiguous()
+    return _resample_f32([x01[i] for i in range(x01.shape[0])], (h, w), filter, clamp, out)
+
+
 def stitch_tiles(tiles, h, w, th, tw, overlap, box=None, out='u8', strides=None):
     """A window of an (h, w) image from the fp32 reconstructions of its tiles (grid and weights: lvae/utils/tiling.py), on the GPU
     (lvae_tile_stitch: one small copy and one launch on the current stream).  tiles: row-major list with one entry per tile of

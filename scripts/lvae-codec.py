@@ -7,6 +7,8 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py encode --synthetic 3 IMAGES/ BITS/ -m qres34m     # seeded weights; writes N seeded PNGs to IMAGES/ first
     python scripts/lvae-codec.py encode IMAGES/ BITS/ --tile 512 768 --overlap 32   # large images: one tiled container per image
     python scripts/lvae-codec.py region BITS/ CROPS/ --box 100 200 512 512          # y0 x0 h w of every tiled file, nothing else decoded
+    python scripts/lvae-codec.py encode IMAGES/ BITS/ --scale 0.5 [--filter bicubic]   # reduced resolution: one scaled container per image
+    python scripts/lvae-codec.py decode BITS/ PREVIEWS/ --preview 128 192              # scaled files at H x W instead of their original size
     python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 1920 1080 [--format nv12] [--frames N]   # raw 8-bit 4:2:0: one .bits per frame
     python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv [--format nv12]
     python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 1920 1080 --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]
@@ -18,6 +20,9 @@ Images whose sizes padded to the model's stride agree are coded as batches of up
 file is what compress_file writes; decode names every PNG after its .bits file.  --synthetic (on decode: seeded weights only) needs no
 checkpoint on disk.  With --tile every image is coded on its own as a tiled container (CodecBase.compress_tiled: tiles of one shape, coded
 --batch at a time, whatever the image's size); decode recognises such files by their magic, region decodes only the tiles a box touches.
+With --scale every image is resampled on the device, coded at S times its size and wrapped in a scaled container
+(CodecBase.compress_scaled, lvae/utils/resample.py); decode recognises these by their magic too and writes PNGs of the ORIGINAL size, or
+of --preview H W.  --scale and --tile exclude each other.
 encode-yuv / decode-yuv code the frames of a raw .yuv file as an intra-frame coder (CodecBase.compress_yuv420 / decompress_yuv420): frame
 k becomes BITS/frame<k>.bits, a file compress_file could have written; --matrix / --range / --chroma are NOT stored, give decode-yuv the
 same --matrix and --range.  With --synthetic N, encode-yuv first writes N seeded frames of --size to IN.yuv.  --depth 10 | 12,
@@ -54,8 +59,12 @@ def load_model(name, synthetic, device):
     return model.to(device).eval()
 
 
-def encode(model, src, dst, lmb, batch, tile=None, overlap=0):
+def encode(model, src, dst, lmb, batch, tile=None, overlap=0, scale=None, filt='lanczos3'):
     paths = sorted(p for p in Path(src).iterdir() if p.is_file())
+    if scale is not None:
+        total = sum(model.compress_file_scaled(p, Path(dst) / (p.stem + '.bits'), scale=scale, filter=filt, lmb=lmb) for p in paths)
+        print(f'encoded {len(paths)} images at scale {scale} ({filt}) -> {total} bytes')
+        return
     if tile is not None:
         total = sum(model.compress_file_tiled(p, Path(dst) / (p.stem + '.bits'), tile=tile, overlap=overlap, lmb=lmb, max_batch=batch)
                     for p in paths)
@@ -77,8 +86,22 @@ def _is_tiled(path):
         return f.read(4) == MAGIC
 
 
-def decode(model, src, dst, batch, box=None):
+def _is_scaled(path):
+    from lvae.utils.resample import MAGIC
+    with open(path, 'rb') as f:
+        return f.read(4) == MAGIC
+
+
+def decode(model, src, dst, batch, box=None, preview=None):
     paths = sorted(Path(src).glob('*.bits'))
+    scaled = [p for p in paths if _is_scaled(p)]
+    if preview is not None and len(scaled) != len(paths):
+        raise SystemExit('--preview: ' + ', '.join(p.name for p in paths if p not in scaled) + ' not coded with --scale')
+    if box is not None and scaled:
+        raise SystemExit('region: ' + ', '.join(p.name for p in scaled) + ' coded with --scale, not with --tile')
+    for p in scaled:
+        model.decompress_file_scaled(p, Path(dst) / (p.stem + '.png'), size=preview)
+    n_scaled, paths = len(scaled), [p for p in paths if p not in scaled]
     tiled = [p for p in paths if _is_tiled(p)]
     if box is not None and len(tiled) != len(paths):
         raise SystemExit('region: ' + ', '.join(p.name for p in paths if p not in tiled) + ' not coded with --tile')
@@ -87,7 +110,7 @@ def decode(model, src, dst, batch, box=None):
     paths = [p for p in paths if p not in tiled]
     for o in range(0, len(paths), batch):                  # decompress_images batches the files of a slice by latent shape itself
         model.decompress_to_files(paths[o:o + batch], [Path(dst) / (p.stem + '.png') for p in paths[o:o + batch]])
-    print(f'decoded {len(paths) + len(tiled)} files')
+    print(f'decoded {len(paths) + len(tiled) + n_scaled} files')
 
 
 def _is_sequence(path):
@@ -167,6 +190,9 @@ def main():
     ap.add_argument('-d', '--device', type=str, default='cuda:0')
     ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='encode: code every image in tiles of this size')
     ap.add_argument('--overlap', type=int, default=0, help='encode with --tile: pixels neighbouring tiles share')
+    ap.add_argument('--scale', type=float, default=None, help='encode: code every image at SCALE times its size (a scaled container per image)')
+    ap.add_argument('--filter', type=str, default='lanczos3', choices=['bilinear', 'bicubic', 'lanczos3'], help='encode with --scale: the resampling filter')
+    ap.add_argument('--preview', type=int, nargs=2, default=None, metavar=('H', 'W'), help='decode: write scaled files at this size')
     ap.add_argument('--box', type=int, nargs=4, default=None, metavar=('Y0', 'X0', 'H', 'W'), help='region: the window to decode')
     ap.add_argument('--synthetic', type=int, default=0, help='seeded weights; on encode also write N seeded 120x180 / 128x192 PNGs to SRC')
     ap.add_argument('--size', type=int, nargs=2, default=None, metavar=('W', 'H'), help='encode-yuv: the frame size of the raw file')
@@ -225,10 +251,13 @@ def main():
     model = load_model(args.model, args.synthetic, torch.device(args.device))
     if args.command == 'region' and args.box is None:
         ap.error('region needs --box y0 x0 h w')
+    if args.scale is not None and args.tile:
+        ap.error('--scale and --tile exclude each other')
     if args.command == 'encode':
-        encode(model, args.src, args.dst, args.lmb, args.batch, tuple(args.tile) if args.tile else None, args.overlap)
+        encode(model, args.src, args.dst, args.lmb, args.batch, tuple(args.tile) if args.tile else None, args.overlap, args.scale, args.filter)
     else:
-        decode(model, args.src, args.dst, args.batch, tuple(args.box) if args.command == 'region' else None)
+        decode(model, args.src, args.dst, args.batch, tuple(args.box) if args.command == 'region' else None,
+               tuple(args.preview) if args.preview and args.command == 'decode' else None)
 
 
 if __name__ == '__main__':
