@@ -342,6 +342,15 @@ int lvae_dwconv_ln_bf16_v(const void* x, const float* wt, const float* bias, con
                           int B, int H, int W, int C, int k, long vstride, void* stream);
 int lvae_dwconv_ln_q8_v(const void* x, const float* wt, const float* bias, const float* shift, const float* scale1p, void* y,
                         int B, int H, int W, int C, int k, long vstride, void* stream);
+
+/* Which kernel a lvae_dwconv_ln_<fmt>[_v] call with these arguments would launch.  Host arithmetic only, no HIP call.
+ * fmt: 0 f32, 1 bf16, 2 h2, 3 q8.  affines: 0 none, 1 LayerNorm affine or AdaLN (one of them), 2 both.
+ * *family: 0 = csrc/dwconv_cl.hip, 1 = sliding window (pointwise.hip).  *tile_rows: TH.  *tiles_per_wg: tpw (1 for family 1).
+ * Returns 0, or -22 exactly where the launch would return -22 for its (fmt, C, k, affines, sizes).  The launchers switch on the
+ * same function (csrc/dwconv_choice.h), so this is what they run; the outputs may be NULL. */
+int lvae_dwconv_ln_choice(int fmt, int affines, int per_image_vectors, int B, int H, int W, int C, int k,
+                          int* family, int* tile_rows, int* tiles_per_wg);
+
 int lvae_stem_bf16(const float* im, const float* wt, const float* bias, void* out,
                    int B, int H, int W, int Cout, float im_shift, float im_scale, int* range_flag, void* stream);
 int lvae_bias_expand_bf16(const float* bias, void* out, long M, int C, void* stream);

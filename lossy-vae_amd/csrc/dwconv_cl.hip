@@ -37,6 +37,7 @@
 #include <utility>
 
 #include "../../include/lvae_hip.h"
+#include "dwconv_choice.h"
 
 namespace {
 
@@ -114,19 +115,19 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
 
-constexpr int CL_SW = 8;                    // output pixels per lane along W
-constexpr int CL_TILE = 8 * 96;             // floats of a wave's transpose tile: 8 pixels x 384 B (64 channels + pad: conflict-free b128 reads)
+using lvae_dwln::CL_SW;                      // output pixels per lane along W
+using lvae_dwln::CL_TILE;                    // floats of a wave's transpose tile (dwconv_choice.h: the launcher's estimate needs the LDS footprint)
 
 // amdgpu_waves_per_eu pins the register budget: three waves per SIMD (168 VGPRs) for the k >= 5, TH = 8 tiles, four (128) for the others.
 // Measured at k = 7, C = 192: 85 us at three waves, 106 us when two more registers push the kernel to two.
 template <int KS, bool BF> struct ClGeom {
-    static constexpr int XW = CL_SW + KS - 1;                       // input pixels per lane and row
-    static constexpr int PPI = BF ? 8 : 4;                          // pixels per LDS-DMA instruction (64 lanes x 16 B = 64 channels x PPI pixels)
-    static constexpr int NG = (XW + PPI - 1) / PPI;                 // DMA instructions per row
-    static constexpr int ROWF = NG * 256;                           // floats of one row buffer (NG KiB)
+    static constexpr int XW = lvae_dwln::cl_xw(KS);                 // input pixels per lane and row
+    static constexpr int PPI = lvae_dwln::cl_ppi(BF);               // pixels per LDS-DMA instruction (64 lanes x 16 B = 64 channels x PPI pixels)
+    static constexpr int NG = lvae_dwln::cl_ng(KS, BF);             // DMA instructions per row
+    static constexpr int ROWF = lvae_dwln::cl_rowf(KS, BF);         // floats of one row buffer (NG KiB)
 };
 
-template <int KS, int NW, bool BF> constexpr int cl_lds_bytes() { return (NW * (CL_TILE + 2 * ClGeom<KS, BF>::ROWF) + 256 + 128 * NW) * 4; }
+template <int KS, int NW, bool BF> constexpr int cl_lds_bytes() { return lvae_dwln::cl_lds_bytes(KS, NW, BF); }
 // waves per SIMD the kernel is compiled for: what the registers allow (above), capped by what 160 KB of LDS lets reside on a CU
 template <int KS, int NW, int TH, bool BF> constexpr int cl_waves() {
     const int by_regs = (KS >= 5 && TH == 8) ? 3 : 4;              // k = 5: 25 unpacked weights = 50 registers too
@@ -407,48 +408,28 @@ int launch_cl_th(const void* x, const float* wt, const float* bias, const float*
     return (int)hipGetLastError();
 }
 
+// TH (output rows per tile) and tpw (tiles per workgroup) come from dwconv_choice.h::choose -- the function lvae_dwconv_ln_choice
+// reports -- and only select the instance here.
 template <int KS, int NW, bool BF, int OF>
 int launch_cl(const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y, int B, int H, int W,
-              long vs, hipStream_t st) {
-    // Output rows per tile (TH) and tiles per workgroup (tpw): the pair with the least estimated time.  A workgroup costs ~3 row
-    // steps for its weights plus, per tile, TH + k - 1 row steps and ~2 for the first rows' latency; the chip runs `slots`
-    // workgroups at a time (3 / 4 waves per SIMD -- the register budgets -- and 160 KB of LDS per CU), in whole rounds.
-    constexpr int LDSB = cl_lds_bytes<KS, NW, BF>();
-    const int n_sx = (W + CL_SW - 1) / CL_SW;
-    int best_th = 1, best_tpw = 1;
-    double best_t = 1e300;
-    for (int th = 1; th <= 8; th *= 2) {
-        if (KS == 1 && th > 1) break;                                  // k = 1: nothing is shared between rows
-        if (th == 2) continue;                                         // not instantiated (compile time; 1 / 4 / 8 cover the map sizes)
-        const int by_waves = (KS >= 5 && th == 8 ? 12 : 16) / NW, by_lds = (160 * 1024) / LDSB;
-        const long slots = 256L * (by_waves < by_lds ? by_waves : by_lds);
-        const int n_ty = (H + th - 1) / th;
-        // (tpw > 1 only pays at k = 1, where a tile is one row step: measured 63 -> 50 us on the 128 x 192 map; for k >= 3 it was
-        //  within noise at best -- the weight loads are not what bounds the kernel -- and cost 15 % where it unbalanced the rounds)
-        for (int tpw = 1; tpw <= (KS == 1 ? 8 : 1); ++tpw) {
-            const long wgs = (long)B * n_sx * ((n_ty + tpw - 1) / tpw);
-            const double t = (double)((wgs + slots - 1) / slots) * (3 + tpw * (th + KS - 1 + 2));
-            if (t < best_t * 0.999) { best_t = t; best_th = th; best_tpw = tpw; }
-            if (tpw >= n_ty) break;
-        }
-    }
-    const int TH = best_th, tpw = best_tpw;
+              int th, int tpw, long vs, hipStream_t st) {
     if constexpr (KS > 1) {
-        if (TH == 8) return launch_cl_th<KS, NW, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
-        if (TH >= 2) return launch_cl_th<KS, NW, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
+        if (th == 8) return launch_cl_th<KS, NW, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
+        if (th == 4) return launch_cl_th<KS, NW, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
     }
-    return launch_cl_th<KS, NW, 1, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
+    if (th == 1) return launch_cl_th<KS, NW, 1, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, tpw, vs, st);
+    return -22;                                                        // not an instance (the choice never names one)
 }
 
 template <int KS, bool BF, int OF = 0>
 int launch_cl_c(int C, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y, int B, int H,
-                int W, long vs, hipStream_t st) {
+                int W, int th, int tpw, long vs, hipStream_t st) {
     switch (C) {
-        case 128: return launch_cl<KS, 2, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 192: return launch_cl<KS, 3, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 256: return launch_cl<KS, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 384: return launch_cl<KS, 6, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 512: return launch_cl<KS, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 128: return launch_cl<KS, 2, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 192: return launch_cl<KS, 3, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 256: return launch_cl<KS, 4, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 384: return launch_cl<KS, 6, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 512: return launch_cl<KS, 8, BF, OF>(x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
     }
     return -22;
 }
@@ -461,69 +442,64 @@ int launch_cl_c(int C, const void* x, const float* wt, const float* bias, const 
 // instances take minutes otherwise.
 #if defined(LVAE_CL_Q8_TU)
 int lvae_dwln_cl_launch_q8(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, long vs, hipStream_t st) {
+                           int B, int H, int W, int th, int tpw, long vs, hipStream_t st) {
     switch (k) {
-        case 1: return launch_cl_c<1, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 3: return launch_cl_c<3, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 5: return launch_cl_c<5, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 7: return launch_cl_c<7, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 1: return launch_cl_c<1, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 3: return launch_cl_c<3, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 5: return launch_cl_c<5, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 7: return launch_cl_c<7, true, 2>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
     }
     return -22;
 }
 #elif defined(LVAE_CL_H2_TU)
 int lvae_dwln_cl_launch_h2(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, long vs, hipStream_t st) {
+                           int B, int H, int W, int th, int tpw, long vs, hipStream_t st) {
     switch (k) {
-        case 1: return launch_cl_c<1, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 3: return launch_cl_c<3, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 5: return launch_cl_c<5, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 7: return launch_cl_c<7, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 1: return launch_cl_c<1, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 3: return launch_cl_c<3, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 5: return launch_cl_c<5, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 7: return launch_cl_c<7, false, 1>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
     }
     return -22;
 }
 #elif defined(LVAE_CL_BF16_TU)
 int lvae_dwln_cl_launch_bf16(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                             int B, int H, int W, long vs, hipStream_t st) {
+                             int B, int H, int W, int th, int tpw, long vs, hipStream_t st) {
     switch (k) {
-        case 1: return launch_cl_c<1, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 3: return launch_cl_c<3, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 5: return launch_cl_c<5, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
-        case 7: return launch_cl_c<7, true>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st);
+        case 1: return launch_cl_c<1, true>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 3: return launch_cl_c<3, true>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 5: return launch_cl_c<5, true>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 7: return launch_cl_c<7, true>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
     }
     return -22;
 }
 #else
 int lvae_dwln_cl_launch_bf16(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                             int B, int H, int W, long vs, hipStream_t st);
+                             int B, int H, int W, int th, int tpw, long vs, hipStream_t st);
 int lvae_dwln_cl_launch_h2(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, long vs, hipStream_t st);
+                           int B, int H, int W, int th, int tpw, long vs, hipStream_t st);
 int lvae_dwln_cl_launch_q8(int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
-                           int B, int H, int W, long vs, hipStream_t st);
+                           int B, int H, int W, int th, int tpw, long vs, hipStream_t st);
 
-// Entry point for pointwise.hip's dispatchers.  Returns 1 when this kernel takes the problem (*rc = launch status), 0 otherwise.
-// Taken for C in {128, 192, 256, 384, 512}, k in {1, 3, 5, 7} and at most ONE per-channel affine after the normalisation -- a rule
-// in (C, k, which pointers are given) only, because this kernel's LayerNorm association differs from the other forms'.
+// Entry point for pointwise.hip's dispatcher, for the launches that dwconv_choice.h::choose gives to this kernel (family 0: C in
+// {128, 192, 256, 384, 512}, k in {1, 3, 5, 7}, at most ONE per-channel affine aw / ab after the normalisation); th / tpw are that
+// choice's tile rows and tiles per workgroup.  fmt: 0 fp32 maps, 1 bf16 maps, 2 fp32 in / f16x2 planes out, 3 bf16 in / MX-fp8 out.
 // vs: element stride between consecutive images' affine vectors (0: one pair for the batch -- the lvae_dwconv_ln_* entry points; > 0:
-// the lvae_dwconv_ln_*_v ones, image b reads shift + b * vs / scale1p + b * vs).
-int lvae_dwln_cl_try(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b, const float* shift,
-                     const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, long vs, hipStream_t st, int* rc) {
-    const int bf16 = fmt == 1 || fmt == 3;                              // fmt: 0 fp32 maps, 1 bf16 maps, 2 fp32 in / f16x2 planes out, 3 bf16 in / MX-fp8 out
-    if (ln_w && shift) return 0;
-    if (!(C == 128 || C == 192 || C == 256 || C == 384 || C == 512) || !(k == 1 || k == 3 || k == 5 || k == 7)) return 0;
-    // one image's map must fit a buffer descriptor (2 GiB, > 44 Mpixels at stride 4): an argument error, NOT a silent switch to the
-    // other kernel family (whose bits differ)
-    if ((long)H * W * C * (bf16 ? 2 : 4) > 0x7fffffffL) { *rc = -22; return 1; }
-    const float* aw = ln_w ? ln_w : scale1p;
-    const float* ab = ln_w ? ln_b : shift;
-    if (fmt == 3) { *rc = lvae_dwln_cl_launch_q8(C, k, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1; }
-    if (bf16) { *rc = lvae_dwln_cl_launch_bf16(C, k, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1; }
-    if (fmt == 2) { *rc = lvae_dwln_cl_launch_h2(C, k, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1; }
-    switch (k) {
-        case 1: *rc = launch_cl_c<1, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
-        case 3: *rc = launch_cl_c<3, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
-        case 5: *rc = launch_cl_c<5, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
-        case 7: *rc = launch_cl_c<7, false>(C, x, wt, bias, aw, ab, y, B, H, W, vs, st); return 1;
+// the lvae_dwconv_ln_*_v ones, image b reads ab + b * vs / aw + b * vs).
+int lvae_dwln_cl_launch(int fmt, int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
+                        int B, int H, int W, int th, int tpw, long vs, hipStream_t st) {
+    switch (fmt) {
+        case 3: return lvae_dwln_cl_launch_q8(C, k, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 1: return lvae_dwln_cl_launch_bf16(C, k, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 2: return lvae_dwln_cl_launch_h2(C, k, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+        case 0:
+            switch (k) {
+                case 1: return launch_cl_c<1, false>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+                case 3: return launch_cl_c<3, false>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+                case 5: return launch_cl_c<5, false>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+                case 7: return launch_cl_c<7, false>(C, x, wt, bias, aw, ab, y, B, H, W, th, tpw, vs, st);
+            }
     }
-    return 0;
+    return -22;
 }
 #endif

@@ -15,6 +15,7 @@
 
 #include "../../include/lvae_hip.h"
 #include "device_math.h"
+#include "dwconv_choice.h"
 
 namespace {
 
@@ -192,30 +193,28 @@ int launch_dwln_th(const void* x, const float* wt, const float* bias, const floa
     return (int)hipGetLastError();
 }
 
+// th: dwconv_choice.h::sw_tile_rows -- two output rows per group on the large k = 7, C = 128 / 192 maps, one otherwise.
 template <int KS, int VPL, int LPP>
 int launch_dwln(const float* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
-                const float* shift, const float* scale1p, float* y, int B, int H, int W, hipStream_t st) {
-    // two output rows per group (measured, B = 8): +12..17 % on the stride-4 maps (C <= 192, ~200k pixels, L2-bandwidth-bound);
-    // slower on the C >= 256 layers, where 200+ VGPRs halve the occupancy.  Same accumulation order => same bits either way.
-    const long px = (long)B * H * W;
-    constexpr int C = 4 * VPL * LPP;
-    int th = (KS == 7 && C <= 192 && VPL <= 3 && px >= 100000) ? 2 : 1;
-    if (KS == 1 || VPL > 4) th = 1;          // VPL = 9 (C = 144, 288) has no registers for a second row
-    if (th == 2) return launch_dwln_th<KS, VPL, LPP, (KS == 1 ? 1 : 2)>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-    return launch_dwln_th<KS, VPL, LPP, 1>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
+                const float* shift, const float* scale1p, float* y, int B, int H, int W, int th, hipStream_t st) {
+    if (th == 1) return launch_dwln_th<KS, VPL, LPP, 1>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
+    if constexpr (KS == 7 && 4 * VPL * LPP <= 192 && VPL <= 3) {
+        if (th == 2) return launch_dwln_th<KS, VPL, LPP, 2>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
+    }
+    return -22;                                                        // not an instance (the choice never names one)
 }
 
 template <int KS>
 int dispatch_dwln_c(int C, const float* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
-                    const float* shift, const float* scale1p, float* y, int B, int H, int W, hipStream_t st) {
+                    const float* shift, const float* scale1p, float* y, int B, int H, int W, int th, hipStream_t st) {
     switch (C) {
-        case 128: return launch_dwln<KS, 2, 16>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 144: return launch_dwln<KS, 9, 4>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);      // qres17m
-        case 288: return launch_dwln<KS, 9, 8>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 192: return launch_dwln<KS, 3, 16>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 256: return launch_dwln<KS, 2, 32>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 384: return launch_dwln<KS, 3, 32>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
-        case 512: return launch_dwln<KS, 4, 32>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st);
+        case 128: return launch_dwln<KS, 2, 16>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, th, st);
+        case 144: return launch_dwln<KS, 9, 4>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, th, st);      // qres17m
+        case 288: return launch_dwln<KS, 9, 8>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, th, st);
+        case 192: return launch_dwln<KS, 3, 16>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, th, st);
+        case 256: return launch_dwln<KS, 2, 32>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, th, st);
+        case 384: return launch_dwln<KS, 3, 32>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, th, st);
+        case 512: return launch_dwln<KS, 4, 32>(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, th, st);
     }
     return -22;
 }
@@ -928,10 +927,10 @@ __global__ __launch_bounds__(256) void sqerr_kernel(const float* __restrict__ a,
 
 // dwconv_cl.hip: the channel-per-lane form (weights in registers, LDS-DMA row buffers) takes the problem by (C, k) alone; what follows
 // here is the sliding-window kernel for the other channel counts (qres17m: C = 144 / 288) and the two-affine case
-int lvae_dwln_cl_try(const void* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b, const float* shift,
-                     const float* scale1p, void* y, int B, int H, int W, int C, int k, int fmt, long vs, hipStream_t st, int* rc);
+int lvae_dwln_cl_launch(int fmt, int C, int k, const void* x, const float* wt, const float* bias, const float* aw, const float* ab, void* y,
+                        int B, int H, int W, int th, int tpw, long vs, hipStream_t st);
 
-// The eight lvae_dwconv_ln_* entry points differ in the output format (`fmt` of lvae_dwln_cl_try: 0 fp32, 1 bf16, 2 H2K32, 3 Q8) and in
+// The eight lvae_dwconv_ln_* entry points differ in the output format (`fmt` of dwconv_choice.h::choose: 0 fp32, 1 bf16, 2 H2K32, 3 Q8) and in
 // whether the AdaLN vectors are per image (`vstride` given: image b is modulated by shift + b * *vstride / scale1p + b * *vstride, in
 // elements; no LayerNorm affine).  Only the channel-per-lane kernel has the pre-split / quantised formats and the per-image form: there
 // every other shape is an argument error (-22), never another kernel.
@@ -940,23 +939,38 @@ static int dwln(int fmt, const long* vstride, const void* x, const float* wt, co
     if (!x || !wt || !bias || !y || B <= 0 || H <= 0 || W <= 0) return -22;
     if (vstride ? (!shift || !scale1p || *vstride < 0) : ((ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale1p == nullptr))) return -22;
     hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    if (lvae_dwln_cl_try(x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, C, k, fmt, vstride ? *vstride : 0, st, &rc)) return rc;
-    if (vstride || fmt >= 2) return -22;
+    lvae_dwln::Choice ch;
+    const int rc = lvae_dwln::choose(fmt, (ln_w ? 1 : 0) + (shift ? 1 : 0), vstride != nullptr, B, H, W, C, k, &ch);
+    if (rc) return rc;
+    if (ch.family == 0)
+        return lvae_dwln_cl_launch(fmt, C, k, x, wt, bias, ln_w ? ln_w : scale1p, ln_w ? ln_b : shift, y, B, H, W, ch.tile_rows, ch.tiles_per_wg,
+                                   vstride ? *vstride : 0, st);
     // the sliding-window kernel: the other channel counts (qres17m: C = 144 / 288) and the two-affine case, fp32 and bf16 maps
     const float* xf = (const float*)x;
     float* yf = (float*)y;
+    const int th = ch.tile_rows;
     switch (k) {
         case 1: return fmt ? dispatch_dwln_bf16<1>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
-                           : dispatch_dwln_c<1>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
+                           : dispatch_dwln_c<1>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, th, st);
         case 3: return fmt ? dispatch_dwln_bf16<3>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
-                           : dispatch_dwln_c<3>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
+                           : dispatch_dwln_c<3>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, th, st);
         case 5: return fmt ? dispatch_dwln_bf16<5>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
-                           : dispatch_dwln_c<5>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
+                           : dispatch_dwln_c<5>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, th, st);
         case 7: return fmt ? dispatch_dwln_bf16<7>(C, x, wt, bias, ln_w, ln_b, shift, scale1p, y, B, H, W, st)
-                           : dispatch_dwln_c<7>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, st);
+                           : dispatch_dwln_c<7>(C, xf, wt, bias, ln_w, ln_b, shift, scale1p, yf, B, H, W, th, st);
     }
     return -22;
+}
+
+extern "C" int lvae_dwconv_ln_choice(int fmt, int affines, int per_image_vectors, int B, int H, int W, int C, int k, int* family,
+                                     int* tile_rows, int* tiles_per_wg) {
+    lvae_dwln::Choice ch;
+    const int rc = lvae_dwln::choose(fmt, affines, per_image_vectors, B, H, W, C, k, &ch);
+    if (rc) return rc;
+    if (family) *family = ch.family;
+    if (tile_rows) *tile_rows = ch.tile_rows;
+    if (tiles_per_wg) *tiles_per_wg = ch.tiles_per_wg;
+    return 0;
 }
 
 extern "C" int lvae_dwconv_ln_f32(const float* x, const float* wt, const float* bias, const float* ln_w, const float* ln_b,
@@ -1269,5 +1283,5 @@ extern "C" int lvae_stream_order(void* from_stream, void* to_stream, void* ev) {
     return (int)hipStreamWaitEvent((hipStream_t)to_stream, (hipEvent_t)ev, 0);
 }
 
-extern "C" int lvae_abi_version(void) { return 26; }
+extern "C" int lvae_abi_version(void) { return 27; }
 extern "C" const char* lvae_build_info(void) { return "liblvae_hip gfx950 (MI355X) fp32-MFMA; hipcc " __VERSION__; }

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblvae_hip.so')
-ABI_VERSION = 26
+ABI_VERSION = 27
 _lib = None
 
 
@@ -108,6 +108,7 @@ SIGNATURES = {
     'lvae_dwconv_ln_h2_v': (_i, [_vp] * 6 + [_i] * 5 + [_l, _vp]),
     'lvae_dwconv_ln_bf16_v': (_i, [_vp] * 6 + [_i] * 5 + [_l, _vp]),
     'lvae_dwconv_ln_q8_v': (_i, [_vp] * 6 + [_i] * 5 + [_l, _vp]),
+    'lvae_dwconv_ln_choice': (_i, [_i] * 8 + [_vp] * 3),
     'lvae_stem_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     'lvae_bias_expand_bf16': (_i, [_vp, _vp, _l, _i, _vp]),
     'lvae_gemv_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -27,7 +27,7 @@ def test_new_symbols_exported_and_declared():
     for name in NEW_SYMBOLS:
         assert re.search(r'\b' + name + r'\s*\(', src), name
         assert name in exported and name in _native.SIGNATURES and name in _native.OP_KINDS, name
-    assert _native.ABI_VERSION == 26 and _native.lib().lvae_abi_version() == 26
+    assert _native.ABI_VERSION == 27 and _native.lib().lvae_abi_version() == 27
 
 
 def test_new_kernels_reject_bad_arguments_without_gpu():

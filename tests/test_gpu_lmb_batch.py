@@ -48,26 +48,15 @@ def _image_bytes(fmt, buf, b, B, H, W, C):
     return torch.cat(parts)
 
 
-def _launcher_tile_rows(C, k, B, H, W, bf16):
-    """Output rows per tile (TH) that csrc/dwconv_cl.hip::launch_cl picks for a launch -- a copy of its cost model (slots from the
-    register budgets 3 / 4 waves per SIMD and 160 KB of LDS per CU; a workgroup costs 3 + TH + k - 1 + 2 row steps; whole rounds).
-    The kernel-level test below uses it to assert that its two map sizes really reach the one-row and the 8-row instances (the
-    k = 7, TH = 8 instance is the one at the register limit).  If the launcher's constants change, this copy has to follow: the
-    assertion then fails loudly instead of the coverage moving silently."""
-    if k == 1:
-        return 1
-    NW, ppi = C // 64, (8 if bf16 else 4)
-    rowf = -(-(8 + k - 1) // ppi) * 256
-    ldsb = (NW * (768 + 2 * rowf) + 256 + 128 * NW) * 4
-    n_sx = -(-W // 8)
-    best_t, best_th = 1e300, 1
-    for th in (1, 4, 8):
-        slots = 256 * min((12 if (k >= 5 and th == 8) else 16) // NW, (160 * 1024) // ldsb)
-        wgs = B * n_sx * -(-H // th)
-        t = -(-wgs // slots) * (3 + th + k - 1 + 2)
-        if t < best_t * 0.999:
-            best_t, best_th = t, th
-    return best_th
+def _tile_rows(L, fmt, C, k, B, H, W):
+    """Output rows per tile (TH) of the csrc/dwconv_cl.hip instance a launch runs: lvae_dwconv_ln_choice, the function the launcher
+    itself switches on (the same for the _v entry points).  The kernel-level test below uses it to assert that its two map sizes really
+    reach the one-row and the 8-row instances (the k = 7, TH = 8 instance is the one at the register limit)."""
+    import dwconv_cases
+    picks = {dwconv_cases.choice(L, fmt, 1, per_image, B, H, W, C, k) for per_image in (0, 1)}
+    (rc, family, th, _), = picks
+    assert rc == 0 and family == 0
+    return th
 
 
 # every (C, k) of qarv_base's AdaLN blocks
@@ -79,18 +68,18 @@ QARV_CK = [(128, 7), (192, 7), (256, 7), (384, 5), (384, 7), (512, 1), (512, 3),
 @pytest.mark.parametrize('C,k', QARV_CK)
 def test_strided_dwconv_equals_single_image_launches(L, C, k, size, fmt):
     B = 3
-    # which instance the launcher runs for this launch (see _launcher_tile_rows).  Small map: one-row tiles, for the batch of 3 and for a
+    # which instance the launcher runs for this launch (see _tile_rows).  Small map: one-row tiles, for the batch of 3 and for a
     # single image alike.  Large map: the first of two sizes that reaches the 8-row tiles.  C = 512 with k = 5, and with k = 7 on bf16
     # maps, never get there on any map (one workgroup per CU at TH = 8 against two at TH = 4, so the 4-row tiles always win): there the
     # large map stands for the largest instance the launcher uses.  k = 1 has one-row tiles only.
     lowp_ = fmt in ('bf16', 'q8')
     if size == 'small':
         H, W = 8, 16
-        assert _launcher_tile_rows(C, k, B, H, W, lowp_) == 1 and _launcher_tile_rows(C, k, 1, H, W, lowp_) == 1
+        assert _tile_rows(L, fmt, C, k, B, H, W) == 1 and _tile_rows(L, fmt, C, k, 1, H, W) == 1
     else:
-        H, W = next((hw for hw in ((128, 192), (128, 128)) if _launcher_tile_rows(C, k, B, *hw, lowp_) == 8), (128, 192))
+        H, W = next((hw for hw in ((128, 192), (128, 128)) if _tile_rows(L, fmt, C, k, B, *hw) == 8), (128, 192))
         want = 1 if k == 1 else 4 if (C == 512 and (k == 5 or (k == 7 and lowp_))) else 8
-        assert _launcher_tile_rows(C, k, B, H, W, lowp_) == want, (C, k, fmt, H, W)
+        assert _tile_rows(L, fmt, C, k, B, H, W) == want, (C, k, fmt, H, W)
     g = torch.Generator(device='cpu').manual_seed(C * 31 + k * 7 + H)
     x = torch.randn(B, H, W, C, generator=g).cuda()
     wt = (torch.randn(k * k, C, generator=g) / k).cuda()
