@@ -159,9 +159,12 @@ typedef struct {
                                              prec 2: three such planes hi | mid | lo, plane stride N*ldw elements,
                                              followed -- when K % 32 == 0 and ldw == K -- by the same values in
                                              k16-interleaved order [N][K/16][3][16] (lvae.models.base.pack_bf16x3) */
-    int  cfg;                             /* tile configuration: 0 = library heuristic, k>0 = candidate k-1 of
-                                             lvae_gemm_num_configs() (results are bit-identical for every choice;
-                                             the Python host passes 0; tests force the others) */
+    int  cfg;                             /* tile configuration (prec 0 / 1 / 2): 0 = library heuristic, k>0 = candidate k-1 of
+                                             lvae_gemm_num_configs(), -22 beyond it (results are bit-identical for every choice;
+                                             the Python host passes 0; tests/test_gpu_gemm_configs.py forces the others).  The two
+                                             64-deep candidates (k = 11, 12) exist for prec 0 without split-K only: elsewhere they
+                                             run the 32-deep tile of the same shape (k = 3, 2), and k = 8 (128 x 256) runs k = 4
+                                             (256 x 256) under prec 2.  prec 4 / 3 read their own codes here (see `prec`) */
     int  ksplit;                          /* split-K: S > 1 cuts K into S equal slices (K % (32*S) == 0) computed by S x tiles
                                              workgroups into `ws`, then reduced IN SLICE ORDER and passed through the epilogue by a
                                              second kernel -- deterministic; for the few-tile, long-K layers (stride 32/64 MLPs, 3x3

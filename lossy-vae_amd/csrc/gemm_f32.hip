@@ -603,7 +603,9 @@ int launch_mode(const lvae_gemm_desc* d, hipStream_t st) {
 
 // This source is compiled three times (build_native.py): as is (plain-A instances + every entry point) and, through gemm_f32_patch2.hip /
 // gemm_f32_conv3.hip, with LVAE_GEMM_TU_AMODE = 1 / 2 (the 2x2-patch and 3x3-tap gather instances of the 12 tile configurations x 3
-// arithmetics) -- one translation unit with all 108 kernel instances took four minutes to compile.
+// arithmetics) -- one translation unit with all the kernel instances took four minutes to compile.  Per unit: 12 fp32 instances and,
+// for the ten 32-deep configurations, a bf16 and a bf16x3 one (launch_mode never runs CfgD256's bf16x3 instance): 31 a launch can
+// reach, each run under every forced cfg by tests/test_gpu_gemm_configs.py.
 #ifdef LVAE_GEMM_TU_AMODE
 }  // namespace
 #if LVAE_GEMM_TU_AMODE == 1
@@ -710,6 +712,7 @@ static int gemm_dispatch(const lvae_gemm_desc* d, hipStream_t st) {
         int rc = 0;
         if (lvae_gemm_x3v2_try(d, st, 0, &rc)) return rc;
     }
+    if (d->cfg > lvae_gemm_num_configs()) return -22;      // no such candidate (launch_mode's switch would run its default: tile)
     switch (d->a_mode) {
         case LVAE_A_PLAIN:
             if ((d->K0 & 3) || (d->lda0 & 3) || d->K0 + d->K1 != d->K || (d->K1 && (!d->A1 || (d->lda1 & 3) || (d->K1 & 3))))
