@@ -710,6 +710,33 @@ int lvae_resample_f32(const float* src, long src_img, long src_plane, long src_r
                       const int* ystart, const float* ywgt, int ytaps, int yspan, const int* xstart, const float* xwgt, int xtaps,
                       int clamp, float* dst, long dst_img, int H, int W, void* stream);
 
+/* ---- rate maps (csrc/rate_map.hip): where an image's estimated bits go.  Deterministic: no atomics, every sum in the order stated, each
+ * fp64 operation rounded on its own (no fused multiply-add), so a torch fp64 expression of the definitions gives the same bits and two
+ * calls agree.  Every output is overwritten.  Launched by the callers between the ranges of a launch plan: the entries have no
+ * lvae_op kind, because the table of kinds is part of what a client sees and stays at its 26 rows with LVAE_OP_ORDER where it is (a new
+ * kind in front of it would renumber it).  lvae_gaussian_nll_pos_f32 would fit an lvae_op; lvae_rate_map_f32 would not (eight integers).
+ * Added without a change to lvae_abi_version() (no existing signature changed).
+ *
+ * lvae_gaussian_nll_pos_f32: the position-wise latent rate of one block.  out[b*HW + p] = the sum over c = 0 .. z-1, in ascending c, of
+ * the float lvae_gaussian_nll_map_f32 stores at (b, c, p) -- the same arithmetic; prm NHWC [B*HW][2z], sym NCHW, cdf_form 0 erf | 1 erfc --
+ * each term widened to fp64 and added to the running sum (from 0).  Nats.  The sum of out over p is the image's rate in that block. */
+int lvae_gaussian_nll_pos_f32(const float* prm, const int32_t* sym, double* out, float scale_bound, int B, int HW, int z, int cdf_form,
+                              void* stream);
+/* lvae_pixel_nll_pos_f32: the same for the lossless model's pixel stage.  out[b*H*W + y*W + x] = the sum over the 3 channels, ascending,
+ * in fp64, of the -log P terms of lvae_pixel_nll_f32 (raw6, im and status as there). */
+int lvae_pixel_nll_pos_f32(const float* raw6, const float* im, double* out, int B, int H, int W, int* status, void* stream);
+/* lvae_rate_map_f32: the block maps composed at image resolution, one launch for the batch.  pos / lat_h / lat_w: HOST arrays of n_blocks
+ * (<= 32) entries, read before the call returns: pos[i] = DEVICE address of block i's map, double[B][lat_h[i]][lat_w[i]] (nats); block i
+ * stands at stride s_i = H / lat_h[i].  pix (optional, DEVICE): double[B][H][W] (nats).  For Y < crop_h, X < crop_w:
+ *   out[b*out_img + Y*out_row + X] = (float)( sum over i ascending, from 0, of (pos[i][b, Y / s_i, X / s_i] * LOG2E) * 2^(-2 log2 s_i),
+ *                                             then + pix[b, Y, X] * LOG2E when pix is given ),   LOG2E = 1.4426950408889634 (fp64):
+ * bits per pixel at that pixel; over an uncropped map the sum of out is the image's estimated size in bits.  Nothing outside the crop
+ * is written (out_row >= crop_w; out_img is ignored for B == 1).
+ * -22: a null pointer, B outside 1 .. 65535, n_blocks outside 0 .. 32 (0 only with pix), a crop outside 1 .. H x 1 .. W, strides that do
+ * not hold the crop, H % lat_h[i] or W % lat_w[i] non-zero, H / lat_h[i] != W / lat_w[i], a ratio that is no power of two. */
+int lvae_rate_map_f32(const double* const* pos, const int* lat_h, const int* lat_w, int n_blocks, const double* pix, int B, int H, int W,
+                      float* out, long out_img, long out_row, int crop_h, int crop_w, void* stream);
+
 /* Stream ordering for launch plans with independent branches (lvae/engine.py: Plan.fork / Plan.join): an event without timing, and
  * "work enqueued on to_stream from now on runs after the work enqueued on from_stream so far" (hipEventRecord + hipStreamWaitEvent). */
 void* lvae_event_create(void);

@@ -15,6 +15,7 @@
 
 #include "../../include/lvae_hip.h"
 #include "device_math.h"
+#include "rate_terms.h"
 #include "dwconv_choice.h"
 
 namespace {
@@ -665,29 +666,7 @@ __global__ __launch_bounds__(256) void latent_sample_box_kernel(const float* __r
     }
 }
 
-// Eval-mode rate estimate (qarv/model.py:95-96; CompressAI GaussianConditional._likelihood): per latent element
-// P = Phi((.5-|v|)/s) - Phi((-.5-|v|)/s), v = zhat - mean = the integer symbol, s = max(exp(softplus(x+2.3)-2.3), bound),
-// P = max(P, 1e-9); accumulates sum(-ln P) per image (nats) in fp64.  Phi in fp32 as the reference: erf form for
-// DiscretizedGaussian (underflows to exactly 0 in the tails), erfc form for stock GaussianConditional.
-// ln P of one latent element (the per-element arithmetic of gaussian_nll_kernel and gaussian_nll_map_kernel).
-__device__ __forceinline__ float gaussian_logp(float lv, int32_t sym, float bound, int cdf_form) {
-    const float xs = lv + 2.3f;
-    const float sp = xs > 20.0f ? xs : log1pf(expf(xs));
-    const float s = fmaxf(expf(sp - 2.3f), bound);
-    const float v = fabsf((float)sym);
-    const float a = (0.5f - v) / s, d = (-0.5f - v) / s;
-    float up, lo;
-    if (cdf_form == 0) {
-        up = 0.5f * (1.0f + lvae_erff(a * 0.70710678118654752440f));
-        lo = 0.5f * (1.0f + lvae_erff(d * 0.70710678118654752440f));
-    } else {
-        up = 0.5f * erfcf(-0.70710678118654752440f * a);
-        lo = 0.5f * erfcf(-0.70710678118654752440f * d);
-    }
-    const float P = fmaxf(up - lo, 1e-9f);
-    return logf(P);
-}
-
+// Eval-mode rate estimate: gaussian_logp (rate_terms.h) per latent element; accumulates sum(-ln P) per image (nats) in fp64.
 __global__ __launch_bounds__(256) void gaussian_nll_kernel(const float* __restrict__ prm, const int32_t* __restrict__ sym,
                                                            double* __restrict__ out, float bound, long per_image, int HW,
                                                            int z, int cdf_form) {
@@ -835,12 +814,8 @@ __global__ __launch_bounds__(EV_WG) void rd_image_kernel(const float* __restrict
     }
 }
 
-// Lossless model: GaussianNLLOutputNet.forward_loss (qresvae/model.py:24-38, entropy_coding.py:18-49) in fp32 with torch's operation
-// order: logscale = softplus(l + 16) - 16 (threshold 20), s = exp(logscale), x = (im - 0.5)*2, bin b = 1/127.5,
-// P = Phi((x + b/2 - m)/s) - Phi((x - b/2 - m)/s) with Phi(v) = 0.5*(1 + erf((v - m)*(1/s)/sqrt 2));
-// log P = P > 1e-6 ? log(max(P, 1e-8)) : -(x - m)^2/(2 s^2) - log s - log sqrt(2 pi) + log b.  The mean is not rounded (that belongs to
-// the coder).  raw6 = px_raw, NHWC [B*HW][6] (mean c0..2 | log-scale c0..2).  im_hat = clamp(m)*0.5 + 0.5 and the fp64 partial sums
-// of -log P and of (im_hat - im)^2.
+// Lossless model: GaussianNLLOutputNet.forward_loss, one pixel_logp (rate_terms.h) per sample.  raw6 = px_raw, NHWC [B*HW][6]
+// (mean c0..2 | log-scale c0..2).  im_hat = clamp(m)*0.5 + 0.5 and the fp64 partial sums of -log P and of (im_hat - im)^2.
 __global__ __launch_bounds__(EV_WG) void pixel_nll_kernel(const float* __restrict__ raw, const float* __restrict__ im,
                                                           float* __restrict__ im_hat, double* __restrict__ part, int HW,
                                                           int* __restrict__ status) {
@@ -852,34 +827,14 @@ __global__ __launch_bounds__(EV_WG) void pixel_nll_kernel(const float* __restric
     const float* r6 = raw + (long)b * HW * 6;
     const float* xi = im + (long)b * 3 * HW;
     float* o = im_hat + (long)b * 3 * HW;
-    const float hb = (float)(0.5 * (1.0 / 127.5));
-    const float log_bin = (float)-4.848116364598481;                      // math.log(1/127.5)
-    const float log_sqrt_2pi = (float)0.9189385332046727;                 // math.log(math.sqrt(2 * math.pi))
-    const float sqrt2 = 1.41421356237309504880f;                           // math.sqrt(2), the divisor of torch's Normal.cdf
     double nll = 0.0, sq = 0.0;
     bool bad = false;
     for (int p = p_lo + threadIdx.x; p < p_hi; p += EV_WG) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float m = r6[(long)p * 6 + c];
-            float ls = r6[(long)p * 6 + 3 + c] + 16.0f;
-            ls = ls > 20.0f ? ls : log1pf(expf(ls));
-            ls = ls - 16.0f;
-            const float s = expf(ls);
-            const float inv = 1.0f / s;
             const float t = xi[(long)c * HW + p];
-            const float x = (t - 0.5f) * 2.0f;
-            const float up = 0.5f * (1.0f + erff((((x + hb) - m) * inv) / sqrt2));
-            const float lo = 0.5f * (1.0f + erff((((x - hb) - m) * inv) / sqrt2));
-            const float P = up - lo;
-            float lp;
-            if (P > 1e-6f) {
-                lp = logf(fmaxf(P, 1e-8f));
-            } else {
-                const float d = x - m;
-                lp = -(d * d) / (2.0f * (s * s)) - logf(s) - log_sqrt_2pi;
-                lp = lp + log_bin;
-            }
+            const float lp = pixel_logp(m, r6[(long)p * 6 + 3 + c], t);
             bad |= !(fabsf(m) <= 3.4028234664e38f) || !(fabsf(lp) <= 3.4028234664e38f);
             const float h = fminf(fmaxf(m, -1.0f), 1.0f) * 0.5f + 0.5f;
             o[(long)c * HW + p] = h;

@@ -154,6 +154,9 @@ SIGNATURES = {
     'lvae_resample_u8_to_f32': (_i, [_vp, _vp] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp, _l, _i, _i, _vp]),
     'lvae_resample_f32_to_u8': (_i, [_vp, _l, _l, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp, _vp, _vp]),
     'lvae_resample_f32': (_i, [_vp, _l, _l, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_i, _vp, _l, _i, _i, _vp]),
+    'lvae_gaussian_nll_pos_f32': (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    'lvae_pixel_nll_pos_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'lvae_rate_map_f32': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _l, _l, _i, _i, _vp]),
 }
 
 

@@ -162,6 +162,60 @@ def imcoding_evaluate(model, dataset, progress=False, metrics=('psnr',), tile=No
     return {k: v / n for k, v in sums.items()}
 
 
+def _cropped_block_bits(pos, size, canvas, log2e):
+    """Bits of one (h_i, w_i) fp64 block map (nats per position) that fall on the top-left (h, w) pixels of an (H, W) canvas: a position
+    at stride s gives pos * log2e / s^2 to each of its s x s pixels, so it counts with the number of its pixels inside the crop."""
+    (h, w), (H, W) = size, canvas
+    s = H // pos.shape[0]
+    ny = (h - torch.arange(pos.shape[0], dtype=torch.float64, device=pos.device) * s).clamp(0, s)
+    nx = (w - torch.arange(pos.shape[1], dtype=torch.float64, device=pos.device) * s).clamp(0, s)
+    return float((pos * ny[:, None] * nx[None, :]).sum() * log2e / (s * s))
+
+
+@torch.no_grad()
+def rate_map_evaluate(model, dataset, out_dir=None, lmb=None):
+    """Where the bits of every image of `dataset` (a known name or a folder, as imcoding_evaluate) go: model.rate_map on the image's
+    bytes (the u8 path of compress_images), one image per call.  -> a list, in sorted path order, of
+      {'name': the file's stem, 'bits': the fp64 sum of the image's map, 'shares': [the fraction of those bits each latent block -- and,
+       last, the lossless model's pixel stage -- gives inside the image's own (h, w)]}.
+    out_dir: also write <stem>.npy (the (h, w) fp32 map, bits per pixel at each pixel) and <stem>.png (grey, to_u8(map / map.max()),
+    rounded where the map lies) there; the folder is created.  lmb: variable-rate models only (model.rate_map raises TypeError otherwise).
+    ValueError: a model without rate_map, a dataset without files, two files of one stem with out_dir."""
+    import numpy as np
+    from .utils.image import load_u8, to_u8
+    if not callable(getattr(model, 'rate_map', None)):
+        raise ValueError(f'rate_map_evaluate: {type(model).__name__} has no rate_map')
+    img_paths = [p for p in _list_images(dataset) if p.is_file()]
+    if not img_paths:
+        raise ValueError(f'rate_map_evaluate: no images in {dataset}')
+    if out_dir is not None:
+        stems = [p.stem for p in img_paths]
+        if len(set(stems)) != len(stems):
+            raise ValueError('rate_map_evaluate: two images share a stem; their maps would share a file name')
+        out_dir = Path(out_dir)
+        out_dir.mkdir(parents=True, exist_ok=True)
+    log2e = getattr(model, 'LOG2E', 1.4426950408889634)
+    d = int(getattr(model, 'max_stride', 1))
+    rows = []
+    for impath in img_paths:
+        u8 = load_u8(impath)
+        h, w = int(u8.shape[0]), int(u8.shape[1])
+        maps, blocks = model.rate_map([u8], blocks=True, **({} if lmb is None else {'lmb': lmb}))
+        m = maps[0]
+        assert tuple(m.shape) == (1, h, w), f'{impath}: map {tuple(m.shape)} for a {h} x {w} image'
+        canvas = (d * math.ceil(h / d), d * math.ceil(w / d))
+        per_block = [_cropped_block_bits(b[0], (h, w), canvas, log2e) for b in blocks]
+        total = sum(per_block)
+        rows.append({'name': impath.stem, 'bits': float(m.double().sum()), 'shares': [v / total if total > 0 else 0.0 for v in per_block]})
+        if out_dir is not None:
+            top = m.max()
+            grey = to_u8([(m / top if float(top) > 0 else m).expand(3, h, w)])[0][:, :, 0]
+            np.save(out_dir / f'{impath.stem}.npy', m[0].cpu().numpy())
+            from PIL import Image
+            Image.fromarray(grey.cpu().contiguous().numpy()).save(out_dir / f'{impath.stem}.png', format='PNG')
+    return rows
+
+
 @torch.no_grad()
 def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, depth=8, subsampling='420', siting='center',
                  layout='planar', **colour):

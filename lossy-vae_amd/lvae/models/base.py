@@ -226,6 +226,11 @@ class CodecPlan(Plan):
             self.idx_host = torch.empty(n_sym, dtype=torch.uint8).pin_memory()
             self.sym_np, self.idx_np = self.sym_host.numpy(), self.idx_host.numpy()
 
+    def alloc_pos(self):
+        """Position plans (rate_map): one fp64 buffer per latent block, (B, h, w) nats, written by lvae_gaussian_nll_pos_f32 behind that
+        block's quantize launch (CodecBase._run_with_pos)."""
+        self.pos_bufs = [self.new(self.B * hw, torch.float64) for _, hw in self.lat_shapes]
+
     def dwln_add(self, fmt, p, x, y, H, W, C, k):
         """Record block p's depthwise + LayerNorm launch with output format `fmt` ('f32' | 'h2' | 'bf16' | 'q8': lvae_dwconv_ln_<fmt>) as
         p + '.dwln', with the model's affine: LayerNorm weights, or AdaLN vectors."""
@@ -812,6 +817,95 @@ class CodecBase(nn.Module):
         for blob, out in zip(self.compress_images(images, lmb=lmb), output_paths):
             with open(out, 'wb') as f:
                 f.write(blob)
+
+    # ---- rate maps (csrc/rate_map.hip): where an image's estimated bits go
+    LOG2E = 1.4426950408889634            # the fp64 constant of lvae_rate_map_f32
+
+    @staticmethod
+    def _run_with_pos(pl, cdf_form, upto=None):
+        """Replay a plan that owns `pos_bufs` (CodecPlan.alloc_pos) on the current stream with lvae_gaussian_nll_pos_f32 behind each latent
+        block's quantize launch (pl.qcuts), where the per-channel kernel of the eval plans stands: the scratch `prm` still holds that
+        block's prior there.  The position kernel has no lvae_op kind (the table of kinds is pinned at its 26 rows), so the plan is
+        replayed as one native range per block -- len(qcuts) + 1 lvae_run_ops calls in place of one -- with the kernel launched between
+        them, on the same stream (a side-stream prior head of the next block is forked behind it).  upto: the op index the replay stops
+        at behind the last block's position kernel (None: the plan's end; pl.qcuts[-1]: nothing more)."""
+        lib = pl.lib
+        st = ctypes.c_void_p(torch.cuda.current_stream(pl.device).cuda_stream)
+        lo = 0
+        for li, cut in enumerate(pl.qcuts):
+            pl.run(lo, cut)
+            lo = cut
+            z, hw = pl.lat_shapes[li]
+            _native.check(lib.lvae_gaussian_nll_pos_f32(pl.prm_bufs[li].data_ptr(), pl.sym_all.data_ptr() + 4 * pl.sym_off[li],
+                                                        pl.pos_bufs[li].data_ptr(), pl.pk.scale_bound, pl.B, hw, z, cdf_form, st),
+                          'lvae_gaussian_nll_pos_f32')
+        if upto is None or upto > lo:
+            pl.run(lo, upto)
+
+    def _rate_map_run(self, im, u8, B, H, W, lmb, return_rec):
+        """The model's part of rate_map: load the input (_load_input), run its position plan and -- return_rec -- what forward() runs for
+        im_hat, raise as forward() does.  -> (the plan that owns pos_bufs / lat_hw, the pixel stage's (B*H*W,) fp64 map or None, im_hat
+        (B, 3, H, W) or None)."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    @on_model_device
+    def rate_map(self, im, lmb=None, blocks=False, return_rec=False):
+        """Where an image's bits go: the eval-mode rate estimate of forward() kept per pixel.  im: a (B, 3, H, W) fp32 tensor in [0, 1]
+        with H, W multiples of max_stride (forward()'s contract: AssertionError outside [0, 1], NonFiniteError), or a list of (h, w, 3)
+        uint8 images of one padded size (whatever compress_images takes; uploaded and replicate-padded by the same path).  lmb:
+        variable-rate models only (None = default_lmb, a number, or one per image); the others raise TypeError.
+        -> a (B, 1, H, W) fp32 tensor on the model's device in BITS PER PIXEL AT THAT PIXEL -- each latent block's position-wise rate
+        (lvae_gaussian_nll_pos_f32) spread over the s x s pixels a position stands for, blocks added in order, then the lossless model's
+        pixel stage (lvae_rate_map_f32: fp64, rounded to fp32 once; one launch for the batch) -- so map.sum() is the image's estimated
+        size in bits.  The list form returns a list of (1, h, w) tensors, each written at its image's own size by the kernel (the
+        padding's bits are left out): the crops differ between images, so there it is one lvae_rate_map_f32 launch per image.
+        blocks=True: also a list with one (B, h_i, w_i) fp64 tensor per latent block, in nats (the lossless model appends its (B, H, W)
+        pixel stage).  return_rec=True: also im_hat, the bits of forward(..., return_rec=True)['im_hat'] (list form: (3, h, w) crops).
+        Deterministic: two calls return the same bits; on variable-rate models row i of a batch with per-image lambdas is the single call."""
+        if lmb is not None and not self.variable_rate:
+            raise TypeError(f'{type(self).__name__} is a fixed-rate model: rate_map takes no lmb')
+        u8 = None
+        if isinstance(im, (list, tuple)):
+            from ..utils.image import U8Batch
+            u8 = U8Batch(im, self.max_stride, self._dummy.device)
+            B, _, H, W = u8.shape
+            d = self.max_stride
+            assert all((d * math.ceil(h / d), d * math.ceil(w / d)) == (H, W) for h, w in u8.sizes), 'rate_map: padded sizes differ'
+            im = None
+        else:
+            im = im.to(self._dummy.device)
+            assert im.dim() == 4 and im.shape[1] == 3 and im.dtype == torch.float32 and not im.requires_grad, f'{im.shape=}'
+            B, _, H, W = im.shape
+        assert H % self.max_stride == 0 and W % self.max_stride == 0, f'{(B, 3, H, W)=}'
+        pl, pix, im_hat = self._rate_map_run(im, u8, B, H, W, lmb, return_rec)
+        n = len(pl.pos_bufs)
+        lat_h = (ctypes.c_int * n)(*[h for h, _ in pl.lat_hw])
+        lat_w = (ctypes.c_int * n)(*[w for _, w in pl.lat_hw])
+        lib = _native.lib()
+        st = ctypes.c_void_p(torch.cuda.current_stream(pl.device).cuda_stream)
+        dev = pl.device
+
+        def compose(out, b0, nb, row, ch, cw):
+            pos = (ctypes.c_void_p * n)(*[t.data_ptr() + 8 * b0 * h * w for t, (h, w) in zip(pl.pos_bufs, pl.lat_hw)])
+            _native.check(lib.lvae_rate_map_f32(pos, lat_h, lat_w, n, None if pix is None else pix.data_ptr() + 8 * b0 * H * W, nb, H, W,
+                                                out.data_ptr(), ch * row, row, ch, cw, st), 'lvae_rate_map_f32')
+
+        if u8 is None:
+            out = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+            compose(out, 0, B, W, H, W)
+        else:
+            out = [torch.empty(1, h, w, dtype=torch.float32, device=dev) for h, w in u8.sizes]
+            for b, (h, w) in enumerate(u8.sizes):
+                compose(out[b], b, 1, w, h, w)
+            if im_hat is not None:
+                im_hat = [im_hat[b, :, :h, :w].clone() for b, (h, w) in enumerate(u8.sizes)]
+        res = [out]
+        if blocks:
+            res.append([t.view(B, h, w).clone() for t, (h, w) in zip(pl.pos_bufs, pl.lat_hw)] + ([pix.view(B, H, W).clone()] if pix is not None else []))
+        if return_rec:
+            res.append(im_hat)
+        return res[0] if len(res) == 1 else tuple(res)
 
     # ---- tiled coding of large images (lvae/utils/tiling.py: grid, weights, container; csrc/tile_stitch.hip: the blend).  A tile's bytes
     # are exactly compress_images' for that crop, so the streams of the models do not change; all tiles of an image share one shape,

@@ -297,9 +297,11 @@ class _NetPlan(CodecPlan):
 class _EncPlan(_NetPlan):
     """forward_end2end(mode='compress') (qarv/model.py:294-315) for B images of size HxW."""
 
-    def __init__(self, model, pk, B, H, W, with_bits=False, chan_bits=False, vec=False):
+    def __init__(self, model, pk, B, H, W, with_bits=False, chan_bits=False, pos_bits=False, vec=False):
         """with_bits ('encb'): each block's rate per image in `nats` ([block][image], accumulated); chan_bits ('ence', the encoder half of
-        forward()): per image and channel in `kl_chan` (fp64 [L][B][z_l] at chan_off[l], lvae_gaussian_nll_chan_f32: deterministic)."""
+        forward()): per image and channel in `kl_chan` (fp64 [L][B][z_l] at chan_off[l], lvae_gaussian_nll_chan_f32: deterministic);
+        pos_bits ('encp', rate_map): per position in `pos_bufs` (one fp64 (B, h, w) buffer per block, lvae_gaussian_nll_pos_f32 where
+        chan_bits has its kernel -- launched by CodecBase._run_with_pos at qcuts, the plan records the 'enc' launches)."""
         super().__init__(model, pk, B, vec)
         lib = self.lib
         self.im = self.new(B * 3 * H * W)
@@ -312,7 +314,7 @@ class _EncPlan(_NetPlan):
         # path leaves stride 16 and runs on the side stream under the stride-32 / 64 stages of both paths, whose launches (M = 96 ... 384
         # rows per image) leave the chip almost empty (round 5; same kernels, same inputs, same bits)
         hoisted = {}                                    # dec_blocks index -> buffer holding posterior0's output
-        self.alloc_latent_io(H // 64, W // 64, host=not chan_bits)         # forward()'s symbols never leave the device
+        self.alloc_latent_io(H // 64, W // 64, host=not (chan_bits or pos_bits))         # forward()'s symbols never leave the device
         self.nats = self.new(model.num_latents * B, torch.float64) if with_bits else None   # [block][image] sum(-ln P)
         if chan_bits:
             self.kl_chan = self.new(B * sum(m.zdim for m in model.dec_blocks if m.kind == 'vrlv'), torch.float64)
@@ -396,6 +398,8 @@ class _EncPlan(_NetPlan):
                     self.add(lib.lvae_quantize_f32, (qm.data_ptr(), pm.data_ptr(), ptr(self.sym_all, ioff), zhat.data_ptr(),
                                                      B, h * w, z, z, self.status_ptr()), p + '.quantize')
                 self.qcuts.append(len(self.ops))        # this block's symbols and indexes are final from here on
+                if pos_bits:
+                    self.lat_hw.append((h, w))
                 if with_bits:       # eval-mode likelihood of the quantised latent (qarv/model.py:95-96), prm still holds this block
                     li = len(self.sym_off) - 1
                     self.add(lib.lvae_gaussian_nll_f32, (self.bufs['prm'].data_ptr(), ptr(self.sym_all, ioff), ptr(self.nats, li * B),
@@ -415,7 +419,8 @@ class _EncPlan(_NetPlan):
                 h, w = h * m.rate, w * m.rate
             elif m.kind == 'stop':
                 break                                                     # qarv/model.py:310-312
-
+        if pos_bits:
+            self.alloc_pos()
 
     def _hoist_posterior0(self, model, feats, hoisted, H, W):
         """Record posterior0 of every latent block whose encoder feature is already there (strides 8 and 16) on the side stream,
@@ -609,8 +614,8 @@ class VariableRateLossyVAE(CodecBase):
         return (kind, B, a, b, group, bool(getattr(self, 'side_streams', False)) and kind != 'dec', self._prec) + (('vec',) if vec else ())
 
     def _build_plan(self, kind, B, a, b, group=0, vec=False):
-        if kind in ('enc', 'encb', 'ence'):
-            return _EncPlan(self, self._packed, B, a, b, with_bits=(kind == 'encb'), chan_bits=(kind == 'ence'), vec=vec)
+        if kind in ('enc', 'encb', 'ence', 'encp'):
+            return _EncPlan(self, self._packed, B, a, b, with_bits=(kind == 'encb'), chan_bits=(kind == 'ence'), pos_bits=(kind == 'encp'), vec=vec)
         return _DecPlan(self, self._packed, B, a, b, evaluate=(kind == 'evald'), vec=vec)
 
     # ---- reference API
@@ -1026,6 +1031,30 @@ class VariableRateLossyVAE(CodecBase):
             pm = dec.pm_bufs[li].view(B, hw, zdim).permute(0, 2, 1)
             zs.append((sym + pm).reshape(B, zdim, *dec.lat_hw[li]).contiguous())
         return zs, nats
+
+    def _rate_map_run(self, im, u8, B, H, W, lmb, return_rec):
+        """CodecBase.rate_map: the 'encp' plan up to the last block's position kernel; im_hat from the 'evald' plan forward() runs."""
+        lmb = self._lmb_arg(lmb, B)
+        vec = isinstance(lmb, list)
+        self._prepare(); self._set_lmb(lmb)
+        enc = self._plan('encp', B, H, W, vec=vec)
+        self._load_input(enc.im.view(B, 3, H, W), im, u8, 0, B)
+        self._use_lmb(enc)
+        self._run_with_pos(enc, 0, upto=enc.qcuts[-1])
+        enc.fetch_status()
+        torch.cuda.current_stream(enc.device).synchronize()
+        enc.raise_if_flagged(where='in rate_map() (encoder)')
+        if not return_rec:
+            return enc, None, None
+        dec = self._plan('evald', B, H // self.max_stride, W // self.max_stride, vec=vec)
+        dec.im.view(B, 3, H, W).copy_(enc.im.view(B, 3, H, W))
+        dec.sym_all.copy_(enc.sym_all)
+        self._use_lmb(dec)
+        dec.run()
+        dec.fetch_status()
+        torch.cuda.current_stream(dec.device).synchronize()
+        dec.raise_if_flagged(where='in rate_map() (decoder)')
+        return enc, None, dec.out.clone()
 
     @torch.no_grad()
     @on_model_device

@@ -262,13 +262,16 @@ class _Packed(PackedWeights):
 
 
 class _QresPlan(CodecPlan):
-    def __init__(self, model, pk, B, H, W, encode, evaluate=False):
+    def __init__(self, model, pk, B, H, W, encode, evaluate=False, pos=False):
         """encode: the encode plan ('enc'); evaluate (with encode): the eval plan of forward() ('eval') -- the encode plan with each
         block's per-channel rate behind its quantize launch (kl_chan, fp64 [L][B][z_l] at chan_off[l]), and the distortion in place of
         the coder's sinks: the lossy models' final conv stored raw + lvae_rd_image_f32, the lossless model's lvae_pixel_nll_f32 on the
-        out-net map (rd_sums, fp64 [B][2]; `out` = im_hat)."""
+        out-net map (rd_sums, fp64 [B][2]; `out` = im_hat).  pos (with evaluate): the position plan of rate_map() ('evalp') -- the eval
+        plan without the per-channel launches; CodecBase._run_with_pos launches lvae_gaussian_nll_pos_f32 in their place (qcuts) into
+        `pos_bufs` (one fp64 (B, h, w) buffer per block), and the lossless model's pixel stage goes to `pix_pos` (fp64 (B, H, W))."""
         super().__init__(model, pk, B)
         evaluate = bool(evaluate and encode)
+        pos = bool(pos and evaluate)
         lib = self.lib
         nH, nW = H // 64, W // 64
         # latent I/O sizes: resolution doubles at every rate-2 upsample of the top-down path
@@ -280,7 +283,7 @@ class _QresPlan(CodecPlan):
                 s *= m.rate
         self.evaluate = evaluate
         if evaluate:
-            self.kl_chan = self.new(B * sum(m.zdim for m in model.decoder.dec_blocks if m.kind == 'qlb'), torch.float64)
+            self.kl_chan = None if pos else self.new(B * sum(m.zdim for m in model.decoder.dec_blocks if m.kind == 'qlb'), torch.float64)
             self.rd_sums = self.new(B * 2, torch.float64)
             self.rd_ws = self.new(B * _native.EVAL_CHUNKS * 2, torch.float64)     # per-chunk partials of the distortion kernel
             self.chan_off = []
@@ -380,7 +383,7 @@ class _QresPlan(CodecPlan):
                          p + '.quantize')
                 self.qm_bufs.append(qm)
                 self.qcuts.append(len(self.ops))
-                if evaluate:            # prm still holds this block's prior (scratch shared by every block)
+                if evaluate and not pos:            # prm still holds this block's prior (scratch shared by every block)
                     co = B * sum(zz for zz, _ in self.lat_shapes[:-1])
                     self.chan_off.append(co)
                     self.add(lib.lvae_gaussian_nll_chan_f32, (prm.data_ptr(), ptr(self.sym_all, ioff), ptr(self.kl_chan, co), pk.scale_bound,
@@ -398,6 +401,9 @@ class _QresPlan(CodecPlan):
                       res=f.data_ptr(), ldres=m.width, out=f.data_ptr(), epi=_native.EPI_RES, label=p + '.z_proj.2')
             self.cnx(p + '.resnet_end', m.resnet_end, f.data_ptr(), f.data_ptr(), h, w)
         self.lossless = isinstance(model.out_net, GaussianNLLOutParams)
+        if pos:
+            self.alloc_pos()
+            self.pix_pos = self.new(B * H * W, torch.float64) if self.lossless else None
         if self.lossless:
             # GaussianNLLOutputNet.compress / decompress (:69-94): per-pixel coding of the 3*H*W image samples
             on = model.out_net
@@ -409,6 +415,7 @@ class _QresPlan(CodecPlan):
                       out=raw.data_ptr(), store=_native.ST_SHUFFLE, r=on.rate, H=h, W=w, label='out_net.conv')
             if evaluate:                # forward_loss: the pixel likelihood of the unrounded mean, no coder parameters
                 im_hat = self.new(B * 3 * H * W)
+                self.nll_op = len(self.ops)                 # rate_map without im_hat replays up to here: px_raw is all it needs
                 self.add(lib.lvae_pixel_nll_f32, (raw.data_ptr(), self.im.data_ptr(), im_hat.data_ptr(), self.rd_sums.data_ptr(),
                                                   self.rd_ws.data_ptr(), B, H, W,
                                                   self.status_ptr()), 'out_net.nll')
@@ -506,7 +513,7 @@ class HierarchicalVAE(CodecBase):
         return (kind, B, H, W, group, self._prec)
 
     def _build_plan(self, kind, B, H, W, group=0):
-        return _QresPlan(self, self._packed, B, H, W, encode=(kind in ('enc', 'eval')), evaluate=(kind == 'eval'))
+        return _QresPlan(self, self._packed, B, H, W, encode=(kind in ('enc', 'eval', 'evalp')), evaluate=(kind in ('eval', 'evalp')), pos=(kind == 'evalp'))
 
     def compress_mode(self, mode=True):
         """(:640-647) -> QLatentBlockX.update (:317-325): 64 log-spaced scales 0.1..20, stock erfc-form tables."""
@@ -693,6 +700,25 @@ class HierarchicalVAE(CodecBase):
         if return_rec:
             stats['im_hat'] = pl.out.clone()
         return stats
+
+    def _rate_map_run(self, im, u8, B, H, W, lmb, return_rec):
+        """CodecBase.rate_map: one run of the 'evalp' plan (forward()'s launches, the position kernel in place of the per-channel one), then
+        the lossless model's pixel stage by position from the out-net map the plan left.  Without return_rec the launches that only make
+        im_hat are left out: the lossy models stop behind the last block's position kernel, the lossless one in front of
+        lvae_pixel_nll_f32 (whose terms lvae_pixel_nll_pos_f32 evaluates)."""
+        self._ensure_tables()
+        self._prepare()
+        pl = self._plan('evalp', B, H, W)
+        self._load_input(pl.im.view(B, 3, H, W), im, u8, 0, B)
+        self._run_with_pos(pl, 1, upto=None if return_rec else (pl.nll_op if pl.lossless else pl.qcuts[-1]))
+        if pl.lossless:
+            st = ctypes.c_void_p(torch.cuda.current_stream(pl.device).cuda_stream)
+            _native.check(pl.lib.lvae_pixel_nll_pos_f32(pl.px_raw.data_ptr(), pl.im.data_ptr(), pl.pix_pos.data_ptr(), B, H, W, pl.status_ptr(), st),
+                          'lvae_pixel_nll_pos_f32')
+        pl.fetch_status()
+        torch.cuda.current_stream(pl.device).synchronize()
+        pl.raise_if_flagged(where='in rate_map()')
+        return pl, pl.pix_pos, (pl.out.clone() if return_rec else None)
 
     @torch.no_grad()
     def forward_eval(self, *args, **kwargs):

@@ -15,6 +15,7 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]   # yuv420p10le ...
     python scripts/lvae-codec.py encode-yuv IN.yuv OUT.lvys --size 1920 1080 --container [--layout p010] [--siting left] [--matrix bt2020]
     python scripts/lvae-codec.py decode-yuv IN.lvys OUT.yuv [--layout p010]          # no colour flags: the container holds them
+    python scripts/lvae-codec.py ratemap IMAGES/ MAPS/ -m qarv_base [--lmb 256]      # where the bits go: <stem>.npy + <stem>.png per image
 
 Images whose sizes padded to the model's stride agree are coded as batches of up to --batch (lvae.evaluation.batch_same_size).  A .bits
 file is what compress_file writes; decode names every PNG after its .bits file.  --synthetic (on decode: seeded weights only) needs no
@@ -32,7 +33,10 @@ ask for another depth or subsampling on purpose: the reconstruction is fp32).  -
 semi-planar with the value in the high bits (what hardware decoders deliver); the name gives depth and subsampling.  --container:
 encode-yuv writes ONE self-describing file (CodecBase.compress_yuv_sequence, the LVYS container of lvae/utils/yuvseq.py) instead of a
 folder; decode-yuv recognises it by its magic, takes every parameter from its header and writes the source's layout unless --layout
-/ --format asks for another."""
+/ --format asks for another.
+ratemap writes, for every image of IMAGES/, the per-pixel bit allocation of the model's rate estimate (lvae.evaluation.rate_map_evaluate:
+CodecBase.rate_map on the image's bytes) as MAPS/<stem>.npy (fp32, bits per pixel at each pixel) and a grey MAPS/<stem>.png, and prints
+each image's estimated bits and the share of every latent block; nothing is entropy-coded.  --synthetic N writes seeded PNGs first, as encode."""
 import argparse
 import os
 import sys
@@ -178,10 +182,18 @@ def synthetic_yuv(path, n, size, fmt, colour, layout=None, sp=False):
         write_yuv(from_rgb01_any(rgb, matrix=colour['matrix'], range=colour['range'], **layout), path)
 
 
-@torch.no_grad()
-def main():
+def ratemap(model, src, dst, lmb):
+    from lvae.evaluation import rate_map_evaluate
+    rows = rate_map_evaluate(model, src, out_dir=dst, lmb=lmb)
+    for r in rows:
+        print(f"{r['name']}: {r['bits']:.1f} bits; blocks " + ' '.join(f'{100 * v:.1f}%' for v in r['shares']))
+    print(f"mapped {len(rows)} images -> {sum(r['bits'] for r in rows):.1f} estimated bits")
+    return rows
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
-    ap.add_argument('command', choices=['encode', 'decode', 'region', 'encode-yuv', 'decode-yuv'])
+    ap.add_argument('command', choices=['encode', 'decode', 'region', 'encode-yuv', 'decode-yuv', 'ratemap'])
     ap.add_argument('src')
     ap.add_argument('dst')
     ap.add_argument('-m', '--model', type=str, default='qarv_base')
@@ -194,7 +206,7 @@ def main():
     ap.add_argument('--filter', type=str, default='lanczos3', choices=['bilinear', 'bicubic', 'lanczos3'], help='encode with --scale: the resampling filter')
     ap.add_argument('--preview', type=int, nargs=2, default=None, metavar=('H', 'W'), help='decode: write scaled files at this size')
     ap.add_argument('--box', type=int, nargs=4, default=None, metavar=('Y0', 'X0', 'H', 'W'), help='region: the window to decode')
-    ap.add_argument('--synthetic', type=int, default=0, help='seeded weights; on encode also write N seeded 120x180 / 128x192 PNGs to SRC')
+    ap.add_argument('--synthetic', type=int, default=0, help='seeded weights; on encode / ratemap also write N seeded 120x180 / 128x192 PNGs to SRC')
     ap.add_argument('--size', type=int, nargs=2, default=None, metavar=('W', 'H'), help='encode-yuv: the frame size of the raw file')
     ap.add_argument('--format', type=str, default='i420', choices=['i420', 'nv12'], help='encode-yuv / decode-yuv: the plane layout of the raw file')
     ap.add_argument('--frames', type=int, default=None, help='encode-yuv: code only the first N frames')
@@ -207,7 +219,13 @@ def main():
     ap.add_argument('--layout', type=str, default=None, choices=['p010', 'p012', 'p210', 'p212'],
                     help='encode-yuv / decode-yuv: the raw file is semi-planar with the value in the high bits; sets --depth and --subsampling')
     ap.add_argument('--container', action='store_true', help='encode-yuv: write one self-describing .lvys file to DST instead of a folder of .bits files')
-    args = ap.parse_args()
+    return ap
+
+
+@torch.no_grad()
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
     if args.command in ('encode-yuv', 'decode-yuv'):
         if args.command == 'decode-yuv' and _is_sequence(args.src):      # every parameter comes from the container's header
             model = load_model(args.model, args.synthetic, torch.device(args.device))
@@ -241,7 +259,7 @@ def main():
             decode_yuv(model, args.src, args.dst, args.format, args.batch, colour, layout, sp)
         return
     os.makedirs(args.dst, exist_ok=True)
-    if args.synthetic and args.command == 'encode':
+    if args.synthetic and args.command in ('encode', 'ratemap'):
         import seeded_init
         from lvae.utils.image import save_u8
         os.makedirs(args.src, exist_ok=True)
@@ -249,6 +267,9 @@ def main():
             h, w = ((120, 180), (128, 192))[i % 2]
             save_u8(torch.from_numpy(seeded_init.synthetic_image_u8(h, w, 300 + i)), Path(args.src) / f'im{i:02d}.png')
     model = load_model(args.model, args.synthetic, torch.device(args.device))
+    if args.command == 'ratemap':
+        ratemap(model, args.src, args.dst, args.lmb)
+        return
     if args.command == 'region' and args.box is None:
         ap.error('region needs --box y0 x0 h w')
     if args.scale is not None and args.tile:
