@@ -542,7 +542,8 @@ int lvae_image_u8_to_f32(const uint8_t* const* src, const long* src_row, const i
 int lvae_image_f32_to_u8(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B,
                          uint8_t* const* dst, const long* dst_row, void* stream);
 
-/* ---- 8-bit YUV 4:2:0 frames in and out of the codec (csrc/yuv_io.hip), with the conventions of the image entries above: HOST arrays
+/* ---- 8-bit YUV 4:2:0 frames in and out of the codec (csrc/yuv_io.hip, which holds all eight YUV entries: these two are its 8-bit 4:2:0
+ * centre-sited kernels, planar for I420 and semi-planar for NV12, behind their own argument contract), with the conventions of the image entries above: HOST arrays
  * of DEVICE plane addresses and row strides in bytes, hw[2b], hw[2b + 1] = (h_b, w_b), all read before the call returns (16 frames per
  * launch, descriptors as kernel arguments); fp32 side NCHW RGB planes with unit column stride; any alignment (dword / 16-byte accesses
  * where the addresses allow, bytes / scalars where not).  A frame is a luma plane of (h, w) bytes and chroma at (h/2, w/2); h and w even.
@@ -584,8 +585,8 @@ int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uint8_t* const
                 uint64_t* out, void* stream);
 /* The three entries above were added without a change to lvae_abi_version() (no existing signature changed). */
 
-/* ---- Planar YUV frames of 8, 10 or 12 bits at 4:2:0 / 4:2:2 / 4:4:4 (csrc/yuv_hbd_io.hip): the generalisation of the three entries above,
- * which keep their behaviour; the conventions (HOST arrays of DEVICE plane addresses, hw, 16 frames per launch, fp32 side, alignment) are
+/* ---- Planar YUV frames of 8, 10 or 12 bits at 4:2:0 / 4:2:2 / 4:4:4 (csrc/yuv_io.hip): the general form of the three entries above,
+ * which are instances of the same kernels; the conventions (HOST arrays of DEVICE plane addresses, hw, 16 frames per launch, fp32 side, alignment) are
  * theirs.  depth: 8, 10 or 12.  A sample is a byte at depth 8 and otherwise a 16-bit word with the value in its LOW bits (yuv420p10le,
  * yuv422p12le ...; P010-style layouts with the value in the high bits: the two entries further down); every sample read is masked to `depth` bits.
  * Row strides are in SAMPLES.  subsampling: LVAE_YUV_SUB_420: chroma planes of (h/2, w/2), h and w even; LVAE_YUV_SUB_422: (h, w/2), w even;
@@ -603,7 +604,7 @@ int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uint8_t* const
  * axis: LVAE_YUV_NEAREST: sample x/2; LVAE_YUV_BILINEAR, centre: 3/4 of sample x/2 and 1/4 of its neighbour on the pixel's side, clamped to
  * the plane; left (horizontal axis only): column 2k takes sample k, column 2k + 1 takes (c[k] + c[min(k + 1, cw - 1)]) / 2 -- exact on
  * integers.  Then, every operation rounded to fp32 on its own: y' = (Y - yoff) / yscale, c = (C - 128 s) / cscale, and R, G, B as in
- * lvae_image_yuv420_to_f32; at depth 8, 4:2:0, centre siting the result has the bits of that entry's. */
+ * lvae_image_yuv420_to_f32; at depth 8, 4:2:0, centre siting it is that entry's kernel. */
 enum { LVAE_YUV_SUB_420 = 0, LVAE_YUV_SUB_422 = 1, LVAE_YUV_SUB_444 = 2 };
 enum { LVAE_YUV_SITING_CENTER = 0, LVAE_YUV_SITING_LEFT = 1 };
 enum { LVAE_YUV_BT2020 = 2 };
@@ -618,14 +619,14 @@ int lvae_image_yuv_to_f32(const void* const* y, const void* const* u, const void
 int lvae_image_f32_to_yuv(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int depth,
                           int subsampling, int siting, int matrix, int range, void* const* y, void* const* u, void* const* v,
                           const long* y_row, const long* u_row, const long* v_row, void* stream);
-/* lvae_sse_u16: lvae_sse_u8 for planes of 16-bit words (row strides in samples): exact for ANY 16-bit values -- sums are 64-bit integers
- * from the lane on, one integer atomic per wave. */
+/* lvae_sse_u16: lvae_sse_u8 (the same kernel template) for planes of 16-bit words (row strides in samples): exact for ANY 16-bit values
+ * -- sums are 64-bit integers from the lane on, one integer atomic per wave. */
 int lvae_sse_u16(const uint16_t* const* a, const long* a_row, const uint16_t* const* b, const long* b_row, const int* hw, int n,
                  uint64_t* out, void* stream);
 /* These three were added without a change to lvae_abi_version() either. */
 
 /* ---- Semi-planar frames of 10 or 12 bits at 4:2:0 / 4:2:2 (P010, P012, P210, P212: what hardware video decoders deliver; the SP variants of
- * csrc/yuv_hbd_io.hip), with the conventions of the two planar entries above.  A frame is a luma plane y[b] of (h, w) 16-bit words and ONE
+ * csrc/yuv_io.hip), with the conventions of the two planar entries above.  A frame is a luma plane y[b] of (h, w) 16-bit words and ONE
  * chroma plane uv[b] of (h/2, w/2) (LVAE_YUV_SUB_420) or (h, w/2) (LVAE_YUV_SUB_422) chroma pixels, a chroma pixel being two neighbouring words,
  * U then V: a UV row of cw chroma pixels has 2 cw samples.  Row strides are in SAMPLES (uv_row >= w).  A sample's code is the HIGH `depth`
  * bits of its word: word >> (16 - depth) on input, whatever the low bits hold; code << (16 - depth) on output, low bits zero.  depth: 10 or

@@ -1,19 +1,32 @@
-// 8-bit YUV 4:2:0 frames in and out of the codec on the device, and the exact squared error of byte planes for PSNR-YUV.
-// include/lvae_hip.h (lvae_image_yuv420_to_f32 / lvae_image_f32_to_yuv420 / lvae_sse_u8) states the contract; lvae/utils/yuv.py states
-// the two conversions as torch expressions, and the kernels here reproduce their bits: floating-point contraction is switched off for
-// this file (the pragma below), so every product and sum is rounded on its own and nothing becomes a fused multiply-add, and divisions are
+// YUV frames in and out of the codec on the device -- planar, 8, 10 or 12 bits at 4:2:0 / 4:2:2 / 4:4:4, with centre- or left-sited
+// (co-sited) chroma, and semi-planar (NV12; P010, P012, P210, P212) -- and the exact squared error of 8- and 16-bit planes for PSNR-YUV.
+// include/lvae_hip.h states the contract of the eight entries; lvae/utils/yuv.py states the two conversions as torch expressions
+// (yuv_to_rgb_expr2 / rgb_to_yuv_expr2), and the kernels here reproduce their bits: floating-point contraction is switched off for this
+// file (the pragma below), so every product and sum is rounded on its own and nothing becomes a fused multiply-add, and divisions are
 // IEEE divisions (__fdiv_rn, as in image_io.hip), never a multiplication by a reciprocal.  (The __fmul_rn / __fadd_rn wrappers of the HIP
 // headers do NOT serve here: they are plain products and sums compiled under the default contraction, and fuse after inlining.)
 //
-// All three are streaming kernels in the mould of image_io.hip: up to YUV_CHUNK frames (SSE_CHUNK plane pairs) per launch, their
-// descriptors in the kernel arguments -- no copy to the device, no scratch.  yuv420_to_f32: one lane owns 4 consecutive canvas pixels of
-// one row (4 luma bytes, the 2 x 4 chroma samples under and beside them, one float4 per RGB plane); the chroma filter runs on integers
-// (its weights are sixteenths, so it is exact in any order).  f32_to_yuv420: one lane owns a 2-row x 4-column block (six float4, two
-// luma dwords, two chroma samples per plane).  sse_u8: one lane owns 16 consecutive bytes of one row of both planes; sums are integers
-// from the lane to the one 64-bit atomic per wave.
+// All are streaming kernels in the mould of image_io.hip: up to YUV_CHUNK frames (plane pairs) per launch, their descriptors in the
+// kernel arguments -- no copy to the device, no scratch.  Samples of more than 8 bits are the low bits of 16-bit words (yuv420p10le ...);
+// the kernels mask every sample to `depth` bits.  Row strides are in samples.  Kernels are templates on the sample type, the two
+// subsampling shifts and the siting, so a variant has no branch on any of them.  yuv_to_f32: one lane owns 4 consecutive canvas pixels of
+// one row (one 4- or 8-byte luma load where the address allows, one float4 per RGB plane); the chroma filter runs on integers: per
+// subsampled axis the weights are quarters, so 4 (or 16) times the filtered value is an integer of at most 16 * 4095 and exact in any
+// order.  f32_to_yuv: one lane owns a block of (2 or 1 rows) x 4 columns; left siting needs the column before the block, which is one more
+// scalar load per row and plane.  sse: one lane owns 16 consecutive bytes of one row of both planes; integer sums from the lane to the one
+// 64-bit atomic per wave.
+//
+// Semi-planar frames are one more template parameter, SP, of the same two kernels: a chroma pixel is two neighbouring samples, U then V, of
+// one plane, and a sample's code is the HIGH `depth` bits of its container (>> (8 * sizeof(T) - depth) in, << the same out: 6 or 4 bits for
+// the 16-bit words of the P010 family, none for the bytes of NV12).  The host passes the UV plane as u, the same plane one sample on as v,
+// and the UV row stride for both, so the only new addressing is the chroma column c at sample 2c.  A lane's two chroma pixels are 4
+// consecutive samples: one 4- or 8-byte access where the address allows.  The arithmetic is the planar variants', hence so are the bits.
+// lvae_image_yuv420_to_f32 / lvae_image_f32_to_yuv420 are the <uint8_t, 4:2:0, centre> instances, planar for I420 and SP for NV12.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/lvae_hip.h"
 
@@ -21,19 +34,32 @@
 
 namespace {
 
-constexpr int YUV_CHUNK = 16;                                // frames per launch
-constexpr int SSE_CHUNK = 16;                                // plane pairs per launch
+constexpr int YUV_CHUNK = 16;                                // frames (plane pairs) per launch
 constexpr int YUV_WG = 256;
 
-// one frame: planes, row strides in bytes, valid extent.  NV12: u = the UV plane, v = u + 1, urow == vrow; the sample step is 2
-struct YuvDesc { uint8_t *y, *u, *v; long yrow, urow, vrow; int h, w; };
-struct YuvBatch { YuvDesc d[YUV_CHUNK]; };
+// one frame: planes, row strides in samples, valid extent
+struct PlaneDesc { void *y, *u, *v; long yrow, urow, vrow; int h, w; };
+struct PlaneBatch { PlaneDesc d[YUV_CHUNK]; };
 
-// fp32 constants of a matrix: a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg -- the literals of lvae/utils/yuv.py
-struct YuvCoef { float kr, kg, kb, a, b, d, e; };
-__host__ __device__ inline YuvCoef yuv_coef(int matrix) {
-    return matrix == LVAE_YUV_BT601 ? YuvCoef{0.299f, 0.587f, 0.114f, 1.402f, 1.772f, 0.344136286f, 0.714136286f}
-                                    : YuvCoef{0.2126f, 0.7152f, 0.0722f, 1.5748f, 1.8556f, 0.187324273f, 0.468124273f};
+// the fp32 constants of a conversion: the matrix (a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg, the literals of
+// lvae/utils/yuv.py), the range at this depth (all integers, exact) and the sample mask 2^depth - 1 (peak is the same number as a float)
+// -- and, for the semi-planar variants, the position (bits of the container) - depth of a code inside its sample
+struct YuvParams { float kr, kg, kb, a, b, d, e, yo, ys, co, cs, peak; unsigned mask, shift; };
+
+YuvParams yuv_params(int matrix, int range, int depth) {
+    YuvParams k = matrix == LVAE_YUV_BT601   ? YuvParams{0.299f, 0.587f, 0.114f, 1.402f, 1.772f, 0.344136286f, 0.714136286f}
+                  : matrix == LVAE_YUV_BT709 ? YuvParams{0.2126f, 0.7152f, 0.0722f, 1.5748f, 1.8556f, 0.187324273f, 0.468124273f}
+                                             : YuvParams{0.2627f, 0.678f, 0.0593f, 1.4746f, 1.8814f, 0.164553127f, 0.571353127f};
+    const float s = (float)(1 << (depth - 8)), peak = (float)((1 << depth) - 1);
+    const bool full = range == LVAE_YUV_FULL;
+    k.yo = full ? 0.0f : 16.0f * s;
+    k.ys = full ? peak : 219.0f * s;
+    k.co = 128.0f * s;
+    k.cs = full ? peak : 224.0f * s;
+    k.peak = peak;
+    k.mask = (1u << depth) - 1u;
+    k.shift = (depth == 8 ? 8u : 16u) - (unsigned)depth;     // (read by the SP variants only: 0 for NV12's bytes)
+    return k;
 }
 
 __device__ __forceinline__ float clamp01(float x) {          // NaN -> 0: both comparisons are false for a NaN
@@ -41,123 +67,209 @@ __device__ __forceinline__ float clamp01(float x) {          // NaN -> 0: both c
     return x < 1.0f ? x : 1.0f;
 }
 
-// (Y, C16 = 16 * the upsampled chroma, exact) -> RGB in [0, 1]
-__device__ __forceinline__ void yuv_to_rgb(unsigned Y, unsigned U16, unsigned V16, const YuvCoef k, int full, float& r, float& g, float& b) {
-    const float yo = full ? 0.0f : 16.0f, ys = full ? 255.0f : 219.0f, cs = full ? 255.0f : 224.0f;
-    const float yn = __fdiv_rn((float)Y - yo, ys);
-    const float cb = __fdiv_rn((float)U16 * 0.0625f - 128.0f, cs);      // U16 / 16 is exact
-    const float cr = __fdiv_rn((float)V16 * 0.0625f - 128.0f, cs);
-    r = clamp01(yn + k.a * cr);
-    b = clamp01(yn + k.b * cb);
-    g = clamp01((yn - k.d * cb) - k.e * cr);
+// 4 consecutive samples: one 4-byte (8-bit) or 8-byte (16-bit) access where the address allows, scalars where not
+// (SP: the code is the word's high bits)
+template <typename T, int SP = 0>
+__device__ __forceinline__ void load4(const T* __restrict__ p, const YuvParams& k, unsigned o[4]) {
+    if (((uintptr_t)p & (4 * sizeof(T) - 1)) == 0) {
+        if constexpr (sizeof(T) == 1) {
+            const uint32_t q = *(const uint32_t*)p;
+            o[0] = q & 255u; o[1] = (q >> 8) & 255u; o[2] = (q >> 16) & 255u; o[3] = q >> 24;
+        } else {
+            const uint2 q = *(const uint2*)p;
+            o[0] = q.x & 0xffffu; o[1] = q.x >> 16; o[2] = q.y & 0xffffu; o[3] = q.y >> 16;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = p[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = (SP ? o[i] >> k.shift : o[i]) & k.mask;
 }
 
-__global__ __launch_bounds__(YUV_WG) void yuv420_to_f32_kernel(YuvBatch fb, float* __restrict__ dst, long dst_img, int H, int W, int quads,
-                                                               int vec_ok, int cstep, int matrix, int full, int bilinear) {
+// the first n (1..4) of 4 codes to consecutive samples
+template <typename T>
+__device__ __forceinline__ void store4(T* __restrict__ p, const unsigned v[4], int n) {
+    if (n == 4 && ((uintptr_t)p & (4 * sizeof(T) - 1)) == 0) {
+        if constexpr (sizeof(T) == 1) *(uint32_t*)p = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        else *(uint2*)p = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+    } else {
+        for (int i = 0; i < n; ++i) p[i] = (T)v[i];
+    }
+}
+
+// Semi-planar chroma: the first n (2 or 4) of the samples U V U V -- all four at once (store4's whole store), or a chroma pixel's U and V
+// as one store of twice a sample, where the address allows
+template <typename T>
+__device__ __forceinline__ void store_uv(T* __restrict__ p, const unsigned v[4], int n) {
+    using Pair = typename std::conditional<sizeof(T) == 1, uint16_t, uint32_t>::type;
+    constexpr int BITS = 8 * sizeof(T);
+    if (n == 4 && ((uintptr_t)p & (4 * sizeof(T) - 1)) == 0) {
+        store4(p, v, 4);
+    } else if (((uintptr_t)p & (2 * sizeof(T) - 1)) == 0) {
+        *(Pair*)p = (Pair)(v[0] | (v[1] << BITS));
+        if (n == 4) *(Pair*)(p + 2) = (Pair)(v[2] | (v[3] << BITS));
+    } else {
+        for (int i = 0; i < n; ++i) p[i] = (T)v[i];
+    }
+}
+
+// SX, SY: the chroma planes are (h >> SY, w >> SX); LEFT: the chroma sample lies on the even luma column (SX only; vertically it is centred);
+// SP: semi-planar words (the head of the file)
+template <typename T, int SX, int SY, int LEFT, int SP = 0>
+__global__ __launch_bounds__(YUV_WG) void yuv_to_f32_kernel(PlaneBatch fb, float* __restrict__ dst, long dst_img, int H, int W, int quads,
+                                                            int vec_ok, YuvParams k, int bilinear) {
+    static_assert(SX || !SY, "4:4:0 is not a layout of this file");
+    static_assert(!SP || SX, "semi-planar frames are 4:2:0 / 4:2:2");
+    constexpr int CS = SP ? 2 : 1;                           // samples from one chroma column to the next
     const long idx = (long)blockIdx.x * YUV_WG + threadIdx.x;
     if (idx >= (long)H * quads) return;
     const int y = (int)(idx / quads), x0 = (int)(idx - (long)y * quads) * 4;
-    const YuvDesc im = fb.d[blockIdx.y];
-    const YuvCoef k = yuv_coef(matrix);
-    const int ch = im.h >> 1, cw = im.w >> 1;
+    const PlaneDesc im = fb.d[blockIdx.y];
+    const int ch = im.h >> SY, cw = im.w >> SX;
+    auto code = [&](unsigned word) -> unsigned { return (SP ? word >> k.shift : word) & k.mask; };
     const int ys = min(y, im.h - 1);                         // rows below the extent repeat its last row
-    const int cy = ys >> 1;
-    // the second chroma row of the vertical filter: the neighbour on the pixel's side, clamped (weight 0 for nearest: cyb = cy)
-    const int cyb = bilinear ? min(max(cy + ((ys & 1) ? 1 : -1), 0), ch - 1) : cy;
-    const uint8_t* __restrict__ yr = im.y + (long)ys * im.yrow;
-    const uint8_t* __restrict__ ua = im.u + (long)cy * im.urow;
-    const uint8_t* __restrict__ ub = im.u + (long)cyb * im.urow;
-    const uint8_t* __restrict__ va = im.v + (long)cy * im.vrow;
-    const uint8_t* __restrict__ vb = im.v + (long)cyb * im.vrow;
-    unsigned Y[4], U16[4], V16[4];
-    if (x0 + 3 < im.w) {                                     // 4 valid pixels: chroma columns c0 - 1 .. c0 + 2 (clamped) cover them
-        if (((uintptr_t)(yr + x0) & 3) == 0) {
-            const uint32_t q = *(const uint32_t*)(yr + x0);
-            Y[0] = q & 255u; Y[1] = (q >> 8) & 255u; Y[2] = (q >> 16) & 255u; Y[3] = q >> 24;
+    const int cy = ys >> SY;
+    // the second chroma row of the vertical filter: the neighbour on the pixel's side, clamped (nearest, or no vertical subsampling: cy itself)
+    const int cyb = (SY && bilinear) ? min(max(cy + ((ys & 1) ? 1 : -1), 0), ch - 1) : cy;
+    const T* __restrict__ yr = (const T*)im.y + (long)ys * im.yrow;
+    const T* __restrict__ ua = (const T*)im.u + (long)cy * im.urow;
+    const T* __restrict__ ub = (const T*)im.u + (long)cyb * im.urow;
+    const T* __restrict__ va = (const T*)im.v + (long)cy * im.vrow;
+    const T* __restrict__ vb = (const T*)im.v + (long)cyb * im.vrow;
+    // Y and CU, CV = (SX ? 4 : 1) * (SY ? 4 : 1) times the upsampled chroma, exact
+    unsigned Y[4], CU[4], CV[4];
+    if (x0 + 3 < im.w) {                                     // 4 valid pixels
+        load4<T, SP>(yr + x0, k, Y);
+        if constexpr (!SX) {
+            load4(ua + x0, k, CU);
+            load4(va + x0, k, CV);
         } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) Y[i] = yr[x0 + i];
-        }
-        const int c0 = x0 >> 1;                              // c0 + 1 <= cw - 1 because x0 + 3 <= w - 1
-        if (bilinear) {
-            const int cm = max(c0 - 1, 0), cp = min(c0 + 2, cw - 1);
-            const int col[4] = {cm, c0, c0 + 1, cp};
-            unsigned tu[4], tv[4];                           // 4 * the vertically filtered column
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const long o = (long)col[j] * cstep;
-                tu[j] = 3u * ua[o] + ub[o];
-                tv[j] = 3u * va[o] + vb[o];
+            const int c0 = x0 >> 1;                          // c0 + 1 <= cw - 1 because x0 + 3 <= w - 1
+            auto vert = [&](const T* __restrict__ a, const T* __restrict__ b, int c) -> unsigned {
+                const unsigned p = code(a[c * CS]);
+                return SY ? 3u * p + code(b[c * CS]) : p;    // (nearest: b == a, 4 p)
+            };
+            unsigned u1, u2, v1, v2;
+            if constexpr (SP) {                              // U V U V of columns c0, c0 + 1: 4 consecutive words per chroma row
+                unsigned qa[4], qb[4];
+                load4<T, 1>(ua + 2 * c0, k, qa);
+                if constexpr (SY) load4<T, 1>(ub + 2 * c0, k, qb);
+                auto vert4 = [&](int i) -> unsigned { return SY ? 3u * qa[i] + qb[i] : qa[i]; };
+                u1 = vert4(0); v1 = vert4(1); u2 = vert4(2); v2 = vert4(3);
+            } else {
+                u1 = vert(ua, ub, c0); u2 = vert(ua, ub, c0 + 1); v1 = vert(va, vb, c0); v2 = vert(va, vb, c0 + 1);
             }
-            U16[0] = 3u * tu[1] + tu[0]; U16[1] = 3u * tu[1] + tu[2]; U16[2] = 3u * tu[2] + tu[1]; U16[3] = 3u * tu[2] + tu[3];
-            V16[0] = 3u * tv[1] + tv[0]; V16[1] = 3u * tv[1] + tv[2]; V16[2] = 3u * tv[2] + tv[1]; V16[3] = 3u * tv[2] + tv[3];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const long o = (long)(c0 + j) * cstep;
-                U16[2 * j] = U16[2 * j + 1] = 16u * ua[o];
-                V16[2 * j] = V16[2 * j + 1] = 16u * va[o];
+            if (bilinear) {
+                const int cp = min(c0 + 2, cw - 1);
+                const unsigned u3 = vert(ua, ub, cp), v3 = vert(va, vb, cp);
+                if constexpr (LEFT) {                        // column 2k: sample k; column 2k + 1: (c[k] + c[k + 1]) / 2
+                    CU[0] = 4u * u1; CU[1] = 2u * (u1 + u2); CU[2] = 4u * u2; CU[3] = 2u * (u2 + u3);
+                    CV[0] = 4u * v1; CV[1] = 2u * (v1 + v2); CV[2] = 4u * v2; CV[3] = 2u * (v2 + v3);
+                } else {                                     // 3/4 of the sample the pixel lies in, 1/4 of the neighbour on its side
+                    const int cm = max(c0 - 1, 0);
+                    const unsigned u0 = vert(ua, ub, cm), v0 = vert(va, vb, cm);
+                    CU[0] = 3u * u1 + u0; CU[1] = 3u * u1 + u2; CU[2] = 3u * u2 + u1; CU[3] = 3u * u2 + u3;
+                    CV[0] = 3u * v1 + v0; CV[1] = 3u * v1 + v2; CV[2] = 3u * v2 + v1; CV[3] = 3u * v2 + v3;
+                }
+            } else {
+                CU[0] = CU[1] = 4u * u1; CU[2] = CU[3] = 4u * u2;
+                CV[0] = CV[1] = 4u * v1; CV[2] = CV[3] = 4u * v2;
             }
         }
     } else {                                                 // at or beyond the right edge: every pixel from its nearest valid one
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int xs = min(x0 + i, im.w - 1);
-            Y[i] = yr[xs];
-            const int cx = xs >> 1;
-            const int cxb = bilinear ? min(max(cx + ((xs & 1) ? 1 : -1), 0), cw - 1) : cx;
-            const long oa = (long)cx * cstep, ob = (long)cxb * cstep;
-            if (bilinear) {
-                U16[i] = 3u * (3u * ua[oa] + ub[oa]) + (3u * ua[ob] + ub[ob]);
-                V16[i] = 3u * (3u * va[oa] + vb[oa]) + (3u * va[ob] + vb[ob]);
+            Y[i] = code(yr[xs]);
+            if constexpr (!SX) {
+                CU[i] = code(ua[xs]);
+                CV[i] = code(va[xs]);
             } else {
-                U16[i] = 16u * ua[oa];
-                V16[i] = 16u * va[oa];
+                const int cx = (xs >> 1) * CS;               // in samples, as cxb
+                int cxb = cx;                                // the second tap and the weight of the first, in quarters
+                unsigned wa = 4u;
+                if (bilinear) {
+                    if (LEFT) {
+                        if (xs & 1) { cxb = min((xs >> 1) + 1, cw - 1) * CS; wa = 2u; }
+                    } else {
+                        cxb = min(max((xs >> 1) + ((xs & 1) ? 1 : -1), 0), cw - 1) * CS;
+                        wa = 3u;
+                    }
+                }
+                const unsigned wb = 4u - wa;
+                const unsigned pa = code(ua[cx]), pb = code(ua[cxb]), qa = code(va[cx]), qb = code(va[cxb]);
+                if (SY) {
+                    CU[i] = wa * (3u * pa + code(ub[cx])) + wb * (3u * pb + code(ub[cxb]));
+                    CV[i] = wa * (3u * qa + code(vb[cx])) + wb * (3u * qb + code(vb[cxb]));
+                } else {
+                    CU[i] = wa * pa + wb * pb;
+                    CV[i] = wa * qa + wb * qb;
+                }
             }
         }
     }
-    float v[3][4];
+    constexpr float inv = 1.0f / (float)((SX ? 4 : 1) * (SY ? 4 : 1));
+    float o3[3][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) yuv_to_rgb(Y[i], U16[i], V16[i], k, full, v[0][i], v[1][i], v[2][i]);
+    for (int i = 0; i < 4; ++i) {
+        const float yn = __fdiv_rn((float)Y[i] - k.yo, k.ys);
+        const float cb = __fdiv_rn((float)CU[i] * inv - k.co, k.cs);   // C / 16 (/ 4) is exact
+        const float cr = __fdiv_rn((float)CV[i] * inv - k.co, k.cs);
+        o3[0][i] = clamp01(yn + k.a * cr);
+        o3[2][i] = clamp01(yn + k.b * cb);
+        o3[1][i] = clamp01((yn - k.d * cb) - k.e * cr);
+    }
     float* o = dst + (long)blockIdx.y * dst_img + (long)y * W + x0;
     const long plane = (long)H * W;
     if (vec_ok) {                                            // W % 4 == 0: the quad is whole and 16-byte aligned
 #pragma unroll
-        for (int c = 0; c < 3; ++c) *(float4*)(o + c * plane) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+        for (int c = 0; c < 3; ++c) *(float4*)(o + c * plane) = make_float4(o3[c][0], o3[c][1], o3[c][2], o3[c][3]);
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (x0 + i < W) o[c * plane + i] = v[c][i];
+                if (x0 + i < W) o[c * plane + i] = o3[c][i];
     }
 }
 
-// rint(v), ties to even, clamped to 0..255 (v is finite: its inputs were clamped)
-__device__ __forceinline__ unsigned byte_of(float v) {
+// rint(v), ties to even, clamped to 0..peak (v is finite: its inputs were clamped)
+__device__ __forceinline__ unsigned code_of(float v, float peak) {
     v = rintf(v);
     v = v > 0.0f ? v : 0.0f;
-    v = v < 255.0f ? v : 255.0f;
+    v = v < peak ? v : peak;
     return (unsigned)(int)v;
 }
 
-__global__ __launch_bounds__(YUV_WG) void f32_to_yuv420_kernel(const float* __restrict__ src, long src_img, long src_plane, long src_row,
-                                                               YuvBatch fb, int quads, int hmax2, int vec_ok, int cstep, int matrix, int full) {
+// one pixel: clamped r, g, b -> y' and the two colour differences
+__device__ __forceinline__ void ycc(float r, float g, float b, const YuvParams& k, float& yn, float& cb, float& cr) {
+    const float R = clamp01(r), G = clamp01(g), B = clamp01(b);
+    yn = (k.kr * R + k.kg * G) + k.kb * B;
+    cb = __fdiv_rn(B - yn, k.b);
+    cr = __fdiv_rn(R - yn, k.a);
+}
+
+template <typename T, int SX, int SY, int LEFT, int SP = 0>
+__global__ __launch_bounds__(YUV_WG) void f32_to_yuv_kernel(const float* __restrict__ src, long src_img, long src_plane, long src_row,
+                                                            PlaneBatch fb, int quads, int hblocks, int vec_ok, YuvParams k) {
+    static_assert(SX || !SY, "4:4:0 is not a layout of this file");
+    static_assert(!SP || SX, "semi-planar frames are 4:2:0 / 4:2:2");
+    constexpr int R = SY ? 2 : 1;                            // rows of a block
     const long idx = (long)blockIdx.x * YUV_WG + threadIdx.x;
-    if (idx >= (long)hmax2 * quads) return;
+    if (idx >= (long)hblocks * quads) return;
     const int by = (int)(idx / quads), x0 = (int)(idx - (long)by * quads) * 4;
-    const int y0 = 2 * by;
-    const YuvDesc im = fb.d[blockIdx.y];
-    if (y0 >= im.h || x0 >= im.w) return;                    // h and w are even: rows y0, y0 + 1 and columns x0, x0 + 1 are inside
-    const YuvCoef k = yuv_coef(matrix);
-    const int n = x0 + 3 < im.w ? 4 : 2;                     // valid columns of this block
+    const int y0 = by << SY;
+    const PlaneDesc im = fb.d[blockIdx.y];
+    if (y0 >= im.h || x0 >= im.w) return;                    // h (w) is even where subsampled: the block's R rows (a column pair) are inside
+    const int n = min(4, im.w - x0);                         // valid columns of this block (2 or 4 where SX)
     const float* __restrict__ s = src + (long)blockIdx.y * src_img + (long)y0 * src_row + x0;
-    float p[3][2][4];
+    float p[3][R][4];
     if (vec_ok && n == 4) {
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
+            for (int r = 0; r < R; ++r) {
                 const float4 f = *(const float4*)(s + c * src_plane + r * src_row);
                 p[c][r][0] = f.x; p[c][r][1] = f.y; p[c][r][2] = f.z; p[c][r][3] = f.w;
             }
@@ -165,80 +277,108 @@ __global__ __launch_bounds__(YUV_WG) void f32_to_yuv420_kernel(const float* __re
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
-            for (int r = 0; r < 2; ++r)
+            for (int r = 0; r < R; ++r)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) p[c][r][i] = i < n ? s[c * src_plane + r * src_row + i] : 0.0f;
     }
-    const float ys = full ? 255.0f : 219.0f, yo = full ? 0.0f : 16.0f, cs = full ? 255.0f : 224.0f;
-    unsigned Yb[2][4];
-    float cb[2][4], cr[2][4];
+    unsigned Yc[R][4];
+    float cb[R][4], cr[R][4];
 #pragma unroll
-    for (int r = 0; r < 2; ++r)
+    for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float R = clamp01(p[0][r][i]), G = clamp01(p[1][r][i]), B = clamp01(p[2][r][i]);
-            const float yn = (k.kr * R + k.kg * G) + k.kb * B;
-            cb[r][i] = __fdiv_rn(B - yn, k.b);
-            cr[r][i] = __fdiv_rn(R - yn, k.a);
-            Yb[r][i] = byte_of(yn * ys + yo);
+            float yn;
+            ycc(p[0][r][i], p[1][r][i], p[2][r][i], k, yn, cb[r][i], cr[r][i]);
+            Yc[r][i] = code_of(yn * k.ys + k.yo, k.peak);
+            if constexpr (SP) Yc[r][i] <<= k.shift;
         }
-    unsigned Ub[2], Vb[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float mu = ((cb[0][2 * j] + cb[0][2 * j + 1]) + (cb[1][2 * j] + cb[1][2 * j + 1])) * 0.25f;
-        const float mv = ((cr[0][2 * j] + cr[0][2 * j + 1]) + (cr[1][2 * j] + cr[1][2 * j + 1])) * 0.25f;
-        Ub[j] = byte_of(mu * cs + 128.0f);
-        Vb[j] = byte_of(mv * cs + 128.0f);
-    }
+    for (int r = 0; r < R; ++r) store4((T*)im.y + (long)(y0 + r) * im.yrow + x0, Yc[r], n);
+    if constexpr (!SX) {                                     // 4:4:4: a chroma sample per pixel
+        unsigned Uc[4], Vc[4];
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        uint8_t* o = im.y + (long)(y0 + r) * im.yrow + x0;
-        if (n == 4 && ((uintptr_t)o & 3) == 0) {
-            *(uint32_t*)o = Yb[r][0] | (Yb[r][1] << 8) | (Yb[r][2] << 16) | (Yb[r][3] << 24);
-        } else {
-            for (int i = 0; i < n; ++i) o[i] = (uint8_t)Yb[r][i];
+        for (int i = 0; i < 4; ++i) {
+            Uc[i] = code_of(cb[0][i] * k.cs + k.co, k.peak);
+            Vc[i] = code_of(cr[0][i] * k.cs + k.co, k.peak);
         }
-    }
-    const long co = (long)(x0 >> 1) * cstep;
-    uint8_t* ou = im.u + (long)by * im.urow + co;
-    uint8_t* ov = im.v + (long)by * im.vrow + co;
-    if (cstep == 2 && n == 4 && ((uintptr_t)ou & 3) == 0) {  // NV12: U V U V is one dword
-        *(uint32_t*)ou = Ub[0] | (Vb[0] << 8) | (Ub[1] << 16) | (Vb[1] << 24);
+        store4((T*)im.u + (long)y0 * im.urow + x0, Uc, n);
+        store4((T*)im.v + (long)y0 * im.vrow + x0, Vc, n);
     } else {
-        for (int j = 0; 2 * j < n; ++j) {
-            ou[(long)j * cstep] = (uint8_t)Ub[j];
-            ov[(long)j * cstep] = (uint8_t)Vb[j];
+        float pb[R], pr[R];                                  // left siting: the colour differences of column max(x0 - 1, 0), another lane's pixel
+        if constexpr (LEFT) {
+            const int off = x0 > 0 ? -1 : 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                float yn;
+                ycc(s[r * src_row + off], s[src_plane + r * src_row + off], s[2 * src_plane + r * src_row + off], k, yn, pb[r], pr[r]);
+            }
         }
+        [[maybe_unused]] T* ou = (T*)im.u + (long)by * im.urow + (x0 >> 1);
+        [[maybe_unused]] T* ov = (T*)im.v + (long)by * im.vrow + (x0 >> 1);
+        [[maybe_unused]] unsigned UV[4];                                      // SP: the words U V U V of the block's two chroma pixels
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float hu[R], hv[R];                              // the horizontal step per row
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if constexpr (LEFT) {                        // ((c[2k - 1] + c[2k + 1]) + (c[2k] + c[2k])) / 4, c[-1] = c[0]
+                    const float mu = j ? cb[r][1] : pb[r], mv = j ? cr[r][1] : pr[r];
+                    hu[r] = ((mu + cb[r][2 * j + 1]) + (cb[r][2 * j] + cb[r][2 * j])) * 0.25f;
+                    hv[r] = ((mv + cr[r][2 * j + 1]) + (cr[r][2 * j] + cr[r][2 * j])) * 0.25f;
+                } else {
+                    hu[r] = cb[r][2 * j] + cb[r][2 * j + 1];
+                    hv[r] = cr[r][2 * j] + cr[r][2 * j + 1];
+                }
+            }
+            float mu, mv;
+            if constexpr (LEFT) {
+                mu = SY ? (hu[0] + hu[R - 1]) * 0.5f : hu[0];
+                mv = SY ? (hv[0] + hv[R - 1]) * 0.5f : hv[0];
+            } else {
+                mu = SY ? (hu[0] + hu[R - 1]) * 0.25f : hu[0] * 0.5f;
+                mv = SY ? (hv[0] + hv[R - 1]) * 0.25f : hv[0] * 0.5f;
+            }
+            if constexpr (SP) {
+                UV[2 * j] = code_of(mu * k.cs + k.co, k.peak) << k.shift;
+                UV[2 * j + 1] = code_of(mv * k.cs + k.co, k.peak) << k.shift;
+            } else if (2 * j < n) {
+                ou[j] = (T)code_of(mu * k.cs + k.co, k.peak);
+                ov[j] = (T)code_of(mv * k.cs + k.co, k.peak);
+            }
+        }
+        if constexpr (SP) store_uv((T*)im.u + (long)by * im.urow + x0, UV, n);   // n (2 or 4) columns are n samples of the UV row
     }
 }
 
-struct SsePair { const uint8_t *a, *b; long arow, brow; int h, w; };
-struct SseBatch { SsePair d[SSE_CHUNK]; };
+template <typename T> struct SsePair { const T *a, *b; long arow, brow; int h, w; };
+template <typename T> struct SseBatch { SsePair<T> d[YUV_CHUNK]; };
 
-__global__ __launch_bounds__(YUV_WG) void sse_u8_kernel(SseBatch pb, unsigned long long* __restrict__ out, int chunks) {
-    const SsePair pr = pb.d[blockIdx.y];
+template <typename T>
+__global__ __launch_bounds__(YUV_WG) void sse_kernel(SseBatch<T> pb, unsigned long long* __restrict__ out, int chunks) {
+    constexpr int N = 16 / sizeof(T), BITS = 8 * sizeof(T);  // samples per lane, bits per sample
+    // bytes: <= 16 * 255^2 per lane, <= 64 * that per wave: fits 32 bits.  words: 64 bits from the lane on: 8 * 65535^2 does not fit 32
+    using Acc = typename std::conditional<sizeof(T) == 1, unsigned, unsigned long long>::type;
+    const SsePair<T> pr = pb.d[blockIdx.y];
     const long idx = (long)blockIdx.x * YUV_WG + threadIdx.x;
-    unsigned acc = 0;                                        // <= 16 * 255^2 per lane, <= 64 * that per wave: fits 32 bits
-    const int y = (int)(idx / chunks), x0 = (int)(idx - (long)y * chunks) * 16;
+    Acc acc = 0;
+    const int y = (int)(idx / chunks), x0 = (int)(idx - (long)y * chunks) * N;
     if (y < pr.h && x0 < pr.w) {                             // (no early return: every lane takes part in the wave's sum below)
-        const uint8_t* __restrict__ a = pr.a + (long)y * pr.arow + x0;
-        const uint8_t* __restrict__ b = pr.b + (long)y * pr.brow + x0;
-        if (x0 + 15 < pr.w && (((uintptr_t)a | (uintptr_t)b) & 15) == 0) {
+        const T* __restrict__ a = pr.a + (long)y * pr.arow + x0;
+        const T* __restrict__ b = pr.b + (long)y * pr.brow + x0;
+        auto sq = [](unsigned p, unsigned q) -> Acc {
+            const unsigned d = p > q ? p - q : q - p;
+            return (Acc)(d * d);                             // 65535^2 < 2^32
+        };
+        if (x0 + N - 1 < pr.w && (((uintptr_t)a | (uintptr_t)b) & 15) == 0) {
             const uint4 va = *(const uint4*)a, vb = *(const uint4*)b;
             const uint32_t wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int s = 0; s < 32; s += 8) {
-                    const int d = (int)((wa[j] >> s) & 255u) - (int)((wb[j] >> s) & 255u);
-                    acc += (unsigned)(d * d);
-                }
+                for (int s = 0; s < 32; s += BITS) acc += sq((wa[j] >> s) & ((1u << BITS) - 1u), (wb[j] >> s) & ((1u << BITS) - 1u));
         } else {
-            const int n = min(16, pr.w - x0);
-            for (int i = 0; i < n; ++i) {
-                const int d = (int)a[i] - (int)b[i];
-                acc += (unsigned)(d * d);
-            }
+            const int n = min(N, pr.w - x0);
+            for (int i = 0; i < n; ++i) acc += sq(a[i], b[i]);
         }
     }
 #pragma unroll
@@ -246,82 +386,114 @@ __global__ __launch_bounds__(YUV_WG) void sse_u8_kernel(SseBatch pb, unsigned lo
     if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out + blockIdx.y, (unsigned long long)acc);
 }
 
-bool yuv_enums_ok(int fmt, int matrix, int range) {
-    return (fmt == LVAE_YUV_I420 || fmt == LVAE_YUV_NV12) && (matrix == LVAE_YUV_BT601 || matrix == LVAE_YUV_BT709) &&
+// The frames of a call as the entries take them: HOST arrays of plane addresses and row strides in samples, `bytes` per sample.  Planar:
+// three planes.  Semi-planar (sp): u is the UV plane, whose rows hold 2 * (w / 2) = w samples; v and v_row are not read.
+struct Planes { const void *const *y, *const *u, *const *v; const long *y_row, *u_row, *v_row; const int* hw; int bytes, sp; };
+
+bool enums_ok(int depth, int subsampling, int siting, int matrix, int range) {
+    return (depth == 8 || depth == 10 || depth == 12) &&
+           (subsampling == LVAE_YUV_SUB_420 || subsampling == LVAE_YUV_SUB_422 || subsampling == LVAE_YUV_SUB_444) &&
+           (siting == LVAE_YUV_SITING_CENTER || siting == LVAE_YUV_SITING_LEFT) &&
+           (matrix == LVAE_YUV_BT601 || matrix == LVAE_YUV_BT709 || matrix == LVAE_YUV_BT2020) &&
            (range == LVAE_YUV_LIMITED || range == LVAE_YUV_FULL);
 }
 
-// The frames' descriptors are valid: planes non-null, extents even, positive and inside (H, W), rows that hold their plane's width
-bool yuv_frames_ok(const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v, const long* y_row, const long* u_row,
-                   const long* v_row, const int* hw, int B, int fmt, int H, int W) {
-    const bool nv12 = fmt == LVAE_YUV_NV12;
-    if (!y || !u || !y_row || !u_row || !hw || (!nv12 && (!v || !v_row))) return false;
+// The frames' descriptors are valid: planes non-null, extents positive, even where subsampled and inside (H, W), rows that hold their plane's width
+bool frames_ok(const Planes& p, int B, int sx, int sy, int H, int W) {
+    if (!p.y || !p.u || !p.y_row || !p.u_row || !p.hw || (!p.sp && (!p.v || !p.v_row))) return false;
     for (int b = 0; b < B; ++b) {
-        const int h = hw[2 * b], w = hw[2 * b + 1];
-        if (h <= 0 || w <= 0 || (h & 1) || (w & 1) || h > H || w > W) return false;
-        if (!y[b] || !u[b] || y_row[b] < w || u_row[b] < (nv12 ? w : w / 2)) return false;
-        if (!nv12 && (!v[b] || v_row[b] < w / 2)) return false;
+        const int h = p.hw[2 * b], w = p.hw[2 * b + 1];
+        if (h <= 0 || w <= 0 || (h & sy) || (w & sx) || h > H || w > W) return false;
+        if (!p.y[b] || !p.u[b] || p.y_row[b] < w || p.u_row[b] < (p.sp ? w : w >> sx)) return false;
+        if (!p.sp && (!p.v[b] || p.v_row[b] < (w >> sx))) return false;
     }
     return true;
 }
 
-YuvDesc yuv_desc(const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v, const long* y_row, const long* u_row,
-                 const long* v_row, const int* hw, int b, int fmt) {
-    const bool nv12 = fmt == LVAE_YUV_NV12;
-    uint8_t* up = const_cast<uint8_t*>(u[b]);
-    return {const_cast<uint8_t*>(y[b]), up, nv12 ? up + 1 : const_cast<uint8_t*>(v[b]), y_row[b], u_row[b], nv12 ? u_row[b] : v_row[b],
-            hw[2 * b], hw[2 * b + 1]};
+// frames b0 .. b0 + n for one launch.  Semi-planar: v = the UV plane one sample on, with the UV row stride: what the SP variants index with column * 2
+PlaneBatch plane_batch(const Planes& p, int b0, int n) {
+    PlaneBatch fb = {};
+    for (int i = 0; i < n; ++i) {
+        const int b = b0 + i;
+        void* u = const_cast<void*>(p.u[b]);
+        fb.d[i] = {const_cast<void*>(p.y[b]), u, p.sp ? (char*)u + p.bytes : const_cast<void*>(p.v[b]), p.y_row[b], p.u_row[b],
+                   p.sp ? p.u_row[b] : p.v_row[b], p.hw[2 * b], p.hw[2 * b + 1]};
+    }
+    return fb;
 }
 
-}  // namespace
+// the variant of KERNEL for (depth, subsampling, siting, semi-planar) -- siting has no effect without horizontal subsampling; the
+// semi-planar ones are the P010 family (16-bit words, 4:2:0 / 4:2:2) and NV12 (bytes, 4:2:0, centre)
+#define YUV_PICK_SUB(KERNEL, T, sub, left, SP)                                                                                          \
+    ((sub) == LVAE_YUV_SUB_422 ? ((left) ? KERNEL<T, 1, 0, 1, SP> : KERNEL<T, 1, 0, 0, SP>)                                             \
+                               : ((left) ? KERNEL<T, 1, 1, 1, SP> : KERNEL<T, 1, 1, 0, SP>))
+#define YUV_PICK(KERNEL, depth, sub, left, sp)                                                                                          \
+    ((sp)                            ? ((depth) == 8 ? KERNEL<uint8_t, 1, 1, 0, 1> : YUV_PICK_SUB(KERNEL, uint16_t, sub, left, 1))      \
+     : (sub) == LVAE_YUV_SUB_444     ? ((depth) == 8 ? KERNEL<uint8_t, 0, 0, 0, 0> : KERNEL<uint16_t, 0, 0, 0, 0>)                      \
+     : (depth) == 8                  ? YUV_PICK_SUB(KERNEL, uint8_t, sub, left, 0)                                                      \
+                                     : YUV_PICK_SUB(KERNEL, uint16_t, sub, left, 0))
 
-extern "C" int lvae_image_yuv420_to_f32(const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v, const long* y_row,
-                                        const long* u_row, const long* v_row, const int* hw, int B, int fmt, int matrix, int range,
-                                        int chroma, float* dst, long dst_img, int H, int W, void* stream) {
-    if (!dst || B <= 0 || H <= 0 || W <= 0 || !yuv_enums_ok(fmt, matrix, range) || (chroma != LVAE_YUV_NEAREST && chroma != LVAE_YUV_BILINEAR))
+bool sp_layout_ok(int depth, int subsampling) {              // the P010 family
+    return (depth == 10 || depth == 12) && (subsampling == LVAE_YUV_SUB_420 || subsampling == LVAE_YUV_SUB_422);
+}
+
+// the 8-bit 4:2:0 entries: I420 | NV12, and BT.601 | BT.709 only
+bool yuv420_enums_ok(int fmt, int matrix, int range) {
+    return (fmt == LVAE_YUV_I420 || fmt == LVAE_YUV_NV12) && (matrix == LVAE_YUV_BT601 || matrix == LVAE_YUV_BT709) &&
+           (range == LVAE_YUV_LIMITED || range == LVAE_YUV_FULL);
+}
+
+// Frames -> the fp32 canvas: every check of the three entries' common arguments, then one launch per YUV_CHUNK frames
+int yuv_to_f32(const Planes& p, int B, int depth, int subsampling, int siting, int matrix, int range, int chroma, float* dst, long dst_img,
+               int H, int W, void* stream) {
+    if (!dst || B <= 0 || H <= 0 || W <= 0 || !enums_ok(depth, subsampling, siting, matrix, range) ||
+        (chroma != LVAE_YUV_NEAREST && chroma != LVAE_YUV_BILINEAR))
         return -22;
+    const int sx = subsampling != LVAE_YUV_SUB_444, sy = subsampling == LVAE_YUV_SUB_420;
     const int quads = (W + 3) / 4;
     if ((long)H * quads > (long)INT_MAX || (B > 1 && dst_img < 3L * H * W)) return -22;
-    if (!yuv_frames_ok(y, u, v, y_row, u_row, v_row, hw, B, fmt, H, W)) return -22;
+    if (!frames_ok(p, B, sx, sy, H, W)) return -22;
     const int vec_ok = W % 4 == 0 && dst_img % 4 == 0 && ((uintptr_t)dst & 15) == 0;
     const unsigned gx = (unsigned)(((long)H * quads + YUV_WG - 1) / YUV_WG);
+    const YuvParams k = yuv_params(matrix, range, depth);
+    auto kernel = YUV_PICK(yuv_to_f32_kernel, depth, subsampling, siting == LVAE_YUV_SITING_LEFT, p.sp);
     for (int b0 = 0; b0 < B; b0 += YUV_CHUNK) {
         const int n = B - b0 < YUV_CHUNK ? B - b0 : YUV_CHUNK;
-        YuvBatch fb = {};
-        for (int i = 0; i < n; ++i) fb.d[i] = yuv_desc(y, u, v, y_row, u_row, v_row, hw, b0 + i, fmt);
-        hipLaunchKernelGGL(yuv420_to_f32_kernel, dim3(gx, (unsigned)n), dim3(YUV_WG), 0, (hipStream_t)stream, fb, dst + (long)b0 * dst_img,
-                           dst_img, H, W, quads, vec_ok, fmt == LVAE_YUV_NV12 ? 2 : 1, matrix, range == LVAE_YUV_FULL, chroma == LVAE_YUV_BILINEAR);
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)n), dim3(YUV_WG), 0, (hipStream_t)stream, plane_batch(p, b0, n), dst + (long)b0 * dst_img,
+                           dst_img, H, W, quads, vec_ok, k, chroma == LVAE_YUV_BILINEAR);
     }
     return (int)hipGetLastError();
 }
 
-extern "C" int lvae_image_f32_to_yuv420(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B,
-                                        int fmt, int matrix, int range, uint8_t* const* y, uint8_t* const* u, uint8_t* const* v,
-                                        const long* y_row, const long* u_row, const long* v_row, void* stream) {
-    if (!src || B <= 0 || H <= 0 || W <= 0 || !yuv_enums_ok(fmt, matrix, range)) return -22;
+// The inverse, with the same division of labour
+int f32_to_yuv(const float* src, long src_img, long src_plane, long src_row, int H, int W, int B, int depth, int subsampling, int siting,
+               int matrix, int range, const Planes& p, void* stream) {
+    if (!src || B <= 0 || H <= 0 || W <= 0 || !enums_ok(depth, subsampling, siting, matrix, range)) return -22;
     if (src_row < W || src_plane < (long)(H - 1) * src_row + W || (B > 1 && src_img < 2 * src_plane + (long)(H - 1) * src_row + W)) return -22;
-    if (!yuv_frames_ok(y, u, v, y_row, u_row, v_row, hw, B, fmt, H, W)) return -22;
+    const int sx = subsampling != LVAE_YUV_SUB_444, sy = subsampling == LVAE_YUV_SUB_420;
+    if (!frames_ok(p, B, sx, sy, H, W)) return -22;
     int hmax = 0, wmax = 0;
     for (int b = 0; b < B; ++b) {
-        hmax = hw[2 * b] > hmax ? hw[2 * b] : hmax;
-        wmax = hw[2 * b + 1] > wmax ? hw[2 * b + 1] : wmax;
+        hmax = p.hw[2 * b] > hmax ? p.hw[2 * b] : hmax;
+        wmax = p.hw[2 * b + 1] > wmax ? p.hw[2 * b + 1] : wmax;
     }
-    const int quads = (wmax + 3) / 4, hmax2 = hmax / 2;
-    if ((long)hmax2 * quads > (long)INT_MAX) return -22;
+    const int quads = (wmax + 3) / 4, hblocks = hmax >> sy;
+    if ((long)hblocks * quads > (long)INT_MAX) return -22;
     const int vec_ok = src_img % 4 == 0 && src_plane % 4 == 0 && src_row % 4 == 0 && ((uintptr_t)src & 15) == 0;
-    const unsigned gx = (unsigned)(((long)hmax2 * quads + YUV_WG - 1) / YUV_WG);
+    const unsigned gx = (unsigned)(((long)hblocks * quads + YUV_WG - 1) / YUV_WG);
+    const YuvParams k = yuv_params(matrix, range, depth);
+    auto kernel = YUV_PICK(f32_to_yuv_kernel, depth, subsampling, siting == LVAE_YUV_SITING_LEFT, p.sp);
     for (int b0 = 0; b0 < B; b0 += YUV_CHUNK) {
         const int n = B - b0 < YUV_CHUNK ? B - b0 : YUV_CHUNK;
-        YuvBatch fb = {};
-        for (int i = 0; i < n; ++i) fb.d[i] = yuv_desc(y, u, v, y_row, u_row, v_row, hw, b0 + i, fmt);
-        hipLaunchKernelGGL(f32_to_yuv420_kernel, dim3(gx, (unsigned)n), dim3(YUV_WG), 0, (hipStream_t)stream, src + (long)b0 * src_img, src_img,
-                           src_plane, src_row, fb, quads, hmax2, vec_ok, fmt == LVAE_YUV_NV12 ? 2 : 1, matrix, range == LVAE_YUV_FULL);
+        hipLaunchKernelGGL(kernel, dim3(gx, (unsigned)n), dim3(YUV_WG), 0, (hipStream_t)stream, src + (long)b0 * src_img, src_img, src_plane,
+                           src_row, plane_batch(p, b0, n), quads, hblocks, vec_ok, k);
     }
     return (int)hipGetLastError();
 }
 
-extern "C" int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uint8_t* const* b, const long* b_row, const int* hw, int n,
-                           uint64_t* out, void* stream) {
+template <typename T>
+int sse(const T* const* a, const long* a_row, const T* const* b, const long* b_row, const int* hw, int n, uint64_t* out, void* stream) {
+    constexpr int N = 16 / sizeof(T);                        // samples per lane
     if (!a || !a_row || !b || !b_row || !hw || !out || n <= 0) return -22;
     int hmax = 0, wmax = 0;
     for (int k = 0; k < n; ++k) {
@@ -330,21 +502,81 @@ extern "C" int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uin
         hmax = h > hmax ? h : hmax;
         wmax = w > wmax ? w : wmax;
     }
-    const int chunks = (wmax - 1) / 16 + 1;                  // one grid shape for every launch of the call: the largest plane's
+    const int chunks = (wmax - 1) / N + 1;                   // one grid shape for every launch of the call: the largest plane's
     const long most = (long)hmax * chunks;
     if (most > (long)INT_MAX) return -22;
     hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t) * (size_t)n, (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
     const unsigned gx = (unsigned)((most + YUV_WG - 1) / YUV_WG);
-    for (int k0 = 0; k0 < n; k0 += SSE_CHUNK) {
-        const int m = n - k0 < SSE_CHUNK ? n - k0 : SSE_CHUNK;
-        SseBatch pb = {};
+    for (int k0 = 0; k0 < n; k0 += YUV_CHUNK) {
+        const int m = n - k0 < YUV_CHUNK ? n - k0 : YUV_CHUNK;
+        SseBatch<T> pb = {};
         for (int i = 0; i < m; ++i) {
             const int k = k0 + i;
             pb.d[i] = {a[k], b[k], a_row[k], b_row[k], hw[2 * k], hw[2 * k + 1]};
         }
-        hipLaunchKernelGGL(sse_u8_kernel, dim3(gx, (unsigned)m), dim3(YUV_WG), 0, (hipStream_t)stream, pb,
-                           (unsigned long long*)out + k0, chunks);
+        hipLaunchKernelGGL(sse_kernel<T>, dim3(gx, (unsigned)m), dim3(YUV_WG), 0, (hipStream_t)stream, pb, (unsigned long long*)out + k0, chunks);
     }
     return (int)hipGetLastError();
 }
+
+}  // namespace
+
+extern "C" int lvae_image_yuv_to_f32(const void* const* y, const void* const* u, const void* const* v, const long* y_row, const long* u_row,
+                                     const long* v_row, const int* hw, int B, int depth, int subsampling, int siting, int matrix, int range,
+                                     int chroma, float* dst, long dst_img, int H, int W, void* stream) {
+    return yuv_to_f32({y, u, v, y_row, u_row, v_row, hw, depth == 8 ? 1 : 2, 0}, B, depth, subsampling, siting, matrix, range, chroma, dst,
+                      dst_img, H, W, stream);
+}
+
+extern "C" int lvae_image_f32_to_yuv(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int depth,
+                                     int subsampling, int siting, int matrix, int range, void* const* y, void* const* u, void* const* v,
+                                     const long* y_row, const long* u_row, const long* v_row, void* stream) {
+    return f32_to_yuv(src, src_img, src_plane, src_row, H, W, B, depth, subsampling, siting, matrix, range,
+                      {y, u, v, y_row, u_row, v_row, hw, depth == 8 ? 1 : 2, 0}, stream);
+}
+
+extern "C" int lvae_image_yuvsp_to_f32(const uint16_t* const* y, const uint16_t* const* uv, const long* y_row, const long* uv_row, const int* hw,
+                                       int B, int depth, int subsampling, int siting, int matrix, int range, int chroma, float* dst, long dst_img,
+                                       int H, int W, void* stream) {
+    if (!sp_layout_ok(depth, subsampling)) return -22;
+    return yuv_to_f32({(const void* const*)y, (const void* const*)uv, nullptr, y_row, uv_row, nullptr, hw, 2, 1}, B, depth, subsampling, siting,
+                      matrix, range, chroma, dst, dst_img, H, W, stream);
+}
+
+extern "C" int lvae_image_f32_to_yuvsp(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B, int depth,
+                                       int subsampling, int siting, int matrix, int range, uint16_t* const* y, uint16_t* const* uv,
+                                       const long* y_row, const long* uv_row, void* stream) {
+    if (!sp_layout_ok(depth, subsampling)) return -22;
+    return f32_to_yuv(src, src_img, src_plane, src_row, H, W, B, depth, subsampling, siting, matrix, range,
+                      {(const void* const*)y, (const void* const*)uv, nullptr, y_row, uv_row, nullptr, hw, 2, 1}, stream);
+}
+
+// The 8-bit 4:2:0 entries: depth 8, 4:2:0, centre siting; I420 is the planar instance and NV12 the semi-planar one (v / v_row may be NULL)
+extern "C" int lvae_image_yuv420_to_f32(const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v, const long* y_row,
+                                        const long* u_row, const long* v_row, const int* hw, int B, int fmt, int matrix, int range,
+                                        int chroma, float* dst, long dst_img, int H, int W, void* stream) {
+    if (!yuv420_enums_ok(fmt, matrix, range)) return -22;
+    return yuv_to_f32({(const void* const*)y, (const void* const*)u, (const void* const*)v, y_row, u_row, v_row, hw, 1, fmt == LVAE_YUV_NV12}, B,
+                      8, LVAE_YUV_SUB_420, LVAE_YUV_SITING_CENTER, matrix, range, chroma, dst, dst_img, H, W, stream);
+}
+
+extern "C" int lvae_image_f32_to_yuv420(const float* src, long src_img, long src_plane, long src_row, int H, int W, const int* hw, int B,
+                                        int fmt, int matrix, int range, uint8_t* const* y, uint8_t* const* u, uint8_t* const* v,
+                                        const long* y_row, const long* u_row, const long* v_row, void* stream) {
+    if (!yuv420_enums_ok(fmt, matrix, range)) return -22;
+    return f32_to_yuv(src, src_img, src_plane, src_row, H, W, B, 8, LVAE_YUV_SUB_420, LVAE_YUV_SITING_CENTER, matrix, range,
+                      {(const void* const*)y, (const void* const*)u, (const void* const*)v, y_row, u_row, v_row, hw, 1, fmt == LVAE_YUV_NV12},
+                      stream);
+}
+
+extern "C" int lvae_sse_u8(const uint8_t* const* a, const long* a_row, const uint8_t* const* b, const long* b_row, const int* hw, int n,
+                           uint64_t* out, void* stream) {
+    return sse(a, a_row, b, b_row, hw, n, out, stream);
+}
+
+extern "C" int lvae_sse_u16(const uint16_t* const* a, const long* a_row, const uint16_t* const* b, const long* b_row, const int* hw, int n,
+                            uint64_t* out, void* stream) {
+    return sse(a, a_row, b, b_row, hw, n, out, stream);
+}
+

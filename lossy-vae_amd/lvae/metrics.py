@@ -27,22 +27,23 @@ def psnr(real, fake):
 
 
 PSNR_YUV_KEYS = ('mse-y', 'mse-u', 'mse-v', 'psnr-y', 'psnr-u', 'psnr-v', 'psnr-yuv')
+PSNR_YUV_KEYS2 = PSNR_YUV_KEYS + ('psnr-avg',)
 
 
-def sse_u8(pairs):
-    """[(a, b)] pairs of equally shaped 2-D uint8 planes -> their sums of squared differences as Python ints, exact.  If a plane is on a
-    GPU: ONE lvae_sse_u8 launch for all pairs on that device's current stream (integer arithmetic on the device, one 64-bit word per pair
-    comes back; planes with unit column stride are read where they lie); CPU planes: numpy int64."""
+def _sse(pairs, dtype, entry, who):
+    """sse_u8 / sse_u16: planes of `dtype` (torch.int16 is read as UNSIGNED 16-bit words); on a GPU ONE launch of `entry` for all pairs."""
+    name = str(dtype).split('.')[-1]
     for a, b in pairs:
-        if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 2 or a.shape != b.shape or a.numel() == 0:
-            raise ValueError(f'sse_u8: expected two equally shaped, non-empty 2-D uint8 planes, got {tuple(a.shape)} and {tuple(b.shape)}')
+        if a.dtype != dtype or b.dtype != dtype or a.dim() != 2 or a.shape != b.shape or a.numel() == 0:
+            raise ValueError(f'{who}: expected two equally shaped, non-empty 2-D {name} planes, got {tuple(a.shape)} and {tuple(b.shape)}')
     devs = {p.device for ab in pairs for p in ab if p.is_cuda}
     if len(devs) > 1:
-        raise ValueError(f'sse_u8: planes on several GPUs {sorted(map(str, devs))}')
+        raise ValueError(f'{who}: planes on several GPUs {sorted(map(str, devs))}')
     if not devs:
+        codes = lambda p: p.contiguous().numpy().view('uint8' if dtype == torch.uint8 else 'uint16').astype('int64')
         out = []
         for a, b in pairs:
-            d = a.numpy().astype('int64') - b.numpy().astype('int64')
+            d = codes(a) - codes(b)
             out.append(int((d * d).sum()))
         return out
     from . import _native
@@ -51,13 +52,46 @@ def sse_u8(pairs):
     a = [plane(p.to(device, non_blocking=True)) for p, _ in pairs]
     b = [plane(p.to(device, non_blocking=True)) for _, p in pairs]
     ptr = lambda ps: (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
-    row = lambda ps: (ctypes.c_long * n)(*[p.stride(0) for p in ps])
+    row = lambda ps: (ctypes.c_long * n)(*[p.stride(0) for p in ps])          # in samples
     hw = (ctypes.c_int * (2 * n))(*[int(v) for p in a for v in p.shape])
-    out = torch.empty(n, dtype=torch.int64, device=device)            # (the sums stay far below 2^63: 255^2 per byte)
+    out = torch.empty(n, dtype=torch.int64, device=device)            # (the sums stay far below 2^63: 65535^2 per sample at the most)
     with torch.cuda.device(device):
         st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _native.check(_native.lib().lvae_sse_u8(ptr(a), row(a), ptr(b), row(b), hw, n, out.data_ptr(), st), 'sse_u8')
+        _native.check(getattr(_native.lib(), 'lvae_' + entry)(ptr(a), row(a), ptr(b), row(b), hw, n, out.data_ptr(), st), entry)
     return [int(v) for v in out.cpu().tolist()]
+
+
+def sse_u8(pairs):
+    """[(a, b)] pairs of equally shaped 2-D uint8 planes -> their sums of squared differences as Python ints, exact.  If a plane is on a
+    GPU: ONE lvae_sse_u8 launch for all pairs on that device's current stream (integer arithmetic on the device, one 64-bit word per pair
+    comes back; planes with unit column stride are read where they lie); CPU planes: numpy int64."""
+    return _sse(pairs, torch.uint8, 'sse_u8', 'sse_u8')
+
+
+def sse_u16(pairs):
+    """sse_u8 for planes of 16-bit codes: [(a, b)] pairs of equally shaped 2-D torch.int16 planes, read as UNSIGNED 16-bit words -> their
+    sums of squared differences as Python ints, exact for any 16-bit values.  If a plane is on a GPU: ONE lvae_sse_u16 launch for all pairs
+    (64-bit integer sums on the device, one word per pair comes back); CPU planes: numpy int64."""
+    return _sse(pairs, torch.int16, 'sse_u16', 'sse_u16')
+
+
+def _psnr_rows(ref, rec, depth, keys):
+    """Per frame pair the dict of `keys`; peak = 255 * 2^(depth - 8)."""
+    sse = (sse_u8 if depth == 8 else sse_u16)([(getattr(a, p), getattr(b, p)) for a, b in zip(ref, rec) for p in 'yuv'])
+    peak2 = (255.0 * (1 << (depth - 8))) ** 2
+    db = lambda mse: float(10 * math.log10(peak2 / mse)) if mse > 0 else math.inf
+    out = []
+    for i, a in enumerate(ref):
+        row, total, count = {}, 0, 0
+        for j, p in enumerate('yuv'):
+            mse = sse[3 * i + j] / float(getattr(a, p).numel())
+            row['mse-' + p] = mse
+            row['psnr-' + p] = db(mse)
+            total, count = total + sse[3 * i + j], count + getattr(a, p).numel()
+        row['psnr-yuv'] = (6 * row['psnr-y'] + row['psnr-u'] + row['psnr-v']) / 8
+        row['psnr-avg'] = db(total / float(count))
+        out.append({k: row[k] for k in keys})
+    return out
 
 
 def psnr_yuv420(ref_frames, rec_frames):
@@ -74,51 +108,7 @@ def psnr_yuv420(ref_frames, rec_frames):
     for i, (a, b) in enumerate(zip(ref, rec)):
         if a.size != b.size:
             raise ValueError(f'psnr_yuv420: frame {i} is {a.size} against {b.size}')
-    sse = sse_u8([(getattr(a, p), getattr(b, p)) for a, b in zip(ref, rec) for p in 'yuv'])
-    out = []
-    for i, a in enumerate(ref):
-        row = {}
-        for j, p in enumerate('yuv'):
-            mse = sse[3 * i + j] / float(getattr(a, p).numel())
-            row['mse-' + p] = mse
-            row['psnr-' + p] = float(10 * math.log10(255.0 ** 2 / mse)) if mse > 0 else math.inf
-        row['psnr-yuv'] = (6 * row['psnr-y'] + row['psnr-u'] + row['psnr-v']) / 8
-        out.append({k: row[k] for k in PSNR_YUV_KEYS})
-    return out
-
-
-PSNR_YUV_KEYS2 = PSNR_YUV_KEYS + ('psnr-avg',)
-
-
-def sse_u16(pairs):
-    """sse_u8 for planes of 16-bit codes: [(a, b)] pairs of equally shaped 2-D torch.int16 planes, read as UNSIGNED 16-bit words -> their
-    sums of squared differences as Python ints, exact for any 16-bit values.  If a plane is on a GPU: ONE lvae_sse_u16 launch for all pairs
-    (64-bit integer sums on the device, one word per pair comes back); CPU planes: numpy int64."""
-    for a, b in pairs:
-        if a.dtype != torch.int16 or b.dtype != torch.int16 or a.dim() != 2 or a.shape != b.shape or a.numel() == 0:
-            raise ValueError(f'sse_u16: expected two equally shaped, non-empty 2-D int16 planes, got {tuple(a.shape)} and {tuple(b.shape)}')
-    devs = {p.device for ab in pairs for p in ab if p.is_cuda}
-    if len(devs) > 1:
-        raise ValueError(f'sse_u16: planes on several GPUs {sorted(map(str, devs))}')
-    if not devs:
-        out = []
-        for a, b in pairs:
-            d = a.contiguous().numpy().view('uint16').astype('int64') - b.contiguous().numpy().view('uint16').astype('int64')
-            out.append(int((d * d).sum()))
-        return out
-    from . import _native
-    device, n = devs.pop(), len(pairs)
-    plane = lambda p: (p if p.stride(1) == 1 and p.stride(0) >= p.shape[1] else p.contiguous())
-    a = [plane(p.to(device, non_blocking=True)) for p, _ in pairs]
-    b = [plane(p.to(device, non_blocking=True)) for _, p in pairs]
-    ptr = lambda ps: (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
-    row = lambda ps: (ctypes.c_long * n)(*[p.stride(0) for p in ps])          # in samples
-    hw = (ctypes.c_int * (2 * n))(*[int(v) for p in a for v in p.shape])
-    out = torch.empty(n, dtype=torch.int64, device=device)            # (the sums stay far below 2^63: 65535^2 per sample)
-    with torch.cuda.device(device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _native.check(_native.lib().lvae_sse_u16(ptr(a), row(a), ptr(b), row(b), hw, n, out.data_ptr(), st), 'sse_u16')
-    return [int(v) for v in out.cpu().tolist()]
+    return _psnr_rows(ref, rec, 8, PSNR_YUV_KEYS)
 
 
 def psnr_yuv(ref_frames, rec_frames):
@@ -140,22 +130,7 @@ def psnr_yuv(ref_frames, rec_frames):
             raise ValueError(f'psnr_yuv: frame {i} is {a.size} {a.depth}-bit {a.subsampling} against {b.size} {b.depth}-bit {b.subsampling}')
     if any(a.depth != ref[0].depth for a in ref):
         raise ValueError('psnr_yuv: the frames of one call share a depth')
-    depth = ref[0].depth
-    sse = (sse_u8 if depth == 8 else sse_u16)([(getattr(a, p), getattr(b, p)) for a, b in zip(ref, rec) for p in 'yuv'])
-    peak2 = (255.0 * (1 << (depth - 8))) ** 2
-    db = lambda mse: float(10 * math.log10(peak2 / mse)) if mse > 0 else math.inf
-    out = []
-    for i, a in enumerate(ref):
-        row, total, count = {}, 0, 0
-        for j, p in enumerate('yuv'):
-            mse = sse[3 * i + j] / float(getattr(a, p).numel())
-            row['mse-' + p] = mse
-            row['psnr-' + p] = db(mse)
-            total, count = total + sse[3 * i + j], count + getattr(a, p).numel()
-        row['psnr-yuv'] = (6 * row['psnr-y'] + row['psnr-u'] + row['psnr-v']) / 8
-        row['psnr-avg'] = db(total / float(count))
-        out.append({k: row[k] for k in PSNR_YUV_KEYS2})
-    return out
+    return _psnr_rows(ref, rec, ref[0].depth, PSNR_YUV_KEYS2)
 
 
 def ms_ssim_db(v):

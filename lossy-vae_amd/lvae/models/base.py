@@ -647,7 +647,7 @@ class CodecBase(nn.Module):
         from ..utils.yuv import from_rgb01
         return self._decompress_blobs(blobs, lambda x, sizes: from_rgb01(x, sizes, fmt=fmt, matrix=matrix, range=range))
 
-    # ---- the same for planar frames of 8 / 10 / 12 bits at 4:2:0 / 4:2:2 / 4:4:4 with centre- or left-sited chroma (csrc/yuv_hbd_io.hip)
+    # ---- the same for planar frames of 8 / 10 / 12 bits at 4:2:0 / 4:2:2 / 4:4:4 with centre- or left-sited chroma (the same kernels)
     @torch.no_grad()
     def compress_yuv(self, frames, lmb=None, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
         """compress_yuv420 for a list of utils.yuv.YuvFrame that share depth and subsampling and whose sizes PADDED to multiples of

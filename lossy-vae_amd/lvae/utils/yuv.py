@@ -1,22 +1,22 @@
 """YUV frames in and out of the codec: planes of raw video <-> the fp32 NCHW RGB tensors in [0, 1] the models code, and raw .yuv files.
 
-Two generations live here.  The first is the 8-bit 4:2:0 path (`Yuv420Frame`: planar I420 / semi-planar NV12 bytes, centre-sited chroma,
-BT.601 / BT.709; `yuv_to_rgb_expr`, `rgb_to_yuv_expr`, `to_rgb01`, `from_rgb01`, `read_yuv420`, `write_yuv420`), which keeps its behaviour
-and its bits.  The second generalises it (`YuvFrame`: planar, 8 / 10 / 12 bits, 4:2:0 / 4:2:2 / 4:4:4, chroma sited in the centre or on
-the left (co-sited, H.264 / HEVC chroma_sample_loc_type 0), BT.601 / BT.709 / BT.2020 non-constant luminance; `yuv_to_rgb_expr2`,
-`rgb_to_yuv_expr2`, `to_rgb01_any`, `from_rgb01_any`, `read_yuv`, `write_yuv`); at 8 bits, 4:2:0, centre siting it gives the bits of the first.
+One implementation behind two sets of names.  The general one is `YuvFrame`: planar, 8 / 10 / 12 bits, 4:2:0 / 4:2:2 / 4:4:4, chroma sited
+in the centre or on the left (co-sited, H.264 / HEVC chroma_sample_loc_type 0), BT.601 / BT.709 / BT.2020 non-constant luminance
+(`yuv_to_rgb_expr2`, `rgb_to_yuv_expr2`, `to_rgb01_any`, `from_rgb01_any`, `read_yuv`, `write_yuv`).  The 8-bit 4:2:0 API (`Yuv420Frame`:
+planar I420 / semi-planar NV12 bytes, centre-sited chroma, BT.601 / BT.709; `yuv_to_rgb_expr`, `rgb_to_yuv_expr`, `to_rgb01`, `from_rgb01`,
+`read_yuv420`, `write_yuv420`) is the general one at depth 8, '420', 'center' with its own frame class and argument checks.
 
 This file DEFINES the conversions, as torch expressions on CPU tensors: fp32 throughout, the constants below as fp32 values, every
-operation rounded on its own, divisions IEEE.  On the GPU the conversions are the HIP kernels of csrc/yuv_io.hip and csrc/yuv_hbd_io.hip,
-which reproduce the expressions' bits: a frame is uploaded as the bytes its file held (1 or 2 per sample), upsampled, converted and
-replicate-padded where the encoder reads it, and a reconstruction becomes codes on the device before it is copied back.  The same split
-as utils.image.to_float01 / to_u8.
+operation rounded on its own, divisions IEEE.  On the GPU the conversions are the HIP kernels of csrc/yuv_io.hip, which reproduce the
+expressions' bits: a frame is uploaded as the bytes its file held (1 or 2 per sample), upsampled, converted and replicate-padded where
+the encoder reads it, and a reconstruction becomes codes on the device before it is copied back.  The same split as
+utils.image.to_float01 / to_u8.
 
 Samples of more than 8 bits are 16-bit little-endian words with the value in the LOW bits (yuv420p10le, yuv422p12le: what ffmpeg rawvideo
 and HM / VTM read and write), held as torch.int16.  The frames hardware video decoders deliver are a third kind, `YuvSpFrame`: semi-planar,
 10 / 12 bits at 4:2:0 / 4:2:2 (P010, P012, P210, P212), a luma plane and ONE plane of interleaved U V words with the value in the HIGH bits
 (`read_yuv_sp`, `write_yuv_sp`, `YuvSpBatch`; `YuvSpFrame.to_planar` / `YuvFrame.to_semiplanar` state the layout as torch ops).  Their
-conversion IS the planar one -- the SP variants of csrc/yuv_hbd_io.hip give the bits the planar kernels give for the deinterleaved, shifted
+conversion IS the planar one -- the SP variants of csrc/yuv_io.hip give the bits the planar kernels give for the deinterleaved, shifted
 planes -- so yuv_to_rgb_expr2 / rgb_to_yuv_expr2 define it too.  Not supported: 16-bit depth (P016), chroma sitings other than centre / left,
 8-bit semi-planar 4:2:2 / 4:4:4 (NV16 / NV24).  The colour parameters, the depth and the siting are the caller's on both sides: no stream
 stores them; the sequence container of utils/yuvseq.py does.
@@ -36,7 +36,7 @@ from .._native import YUV_LAYOUTS as LAYOUTS                 # LVAE_YUV_LAYOUT_*
 # per matrix: Kr, Kg, Kb, a = 2(1 - Kr), b = 2(1 - Kb), d = 2 Kb (1 - Kb) / Kg, e = 2 Kr (1 - Kr) / Kg -- the literals of csrc/yuv_io.hip
 COEF = {'bt601': (0.299, 0.587, 0.114, 1.402, 1.772, 0.344136286, 0.714136286),
         'bt709': (0.2126, 0.7152, 0.0722, 1.5748, 1.8556, 0.187324273, 0.468124273),
-        'bt2020': (0.2627, 0.678, 0.0593, 1.4746, 1.8814, 0.164553127, 0.571353127)}    # YuvFrame path only (MATRICES2; csrc/yuv_hbd_io.hip)
+        'bt2020': (0.2627, 0.678, 0.0593, 1.4746, 1.8814, 0.164553127, 0.571353127)}    # YuvFrame API only (MATRICES2)
 SCALES = {'limited': (16.0, 219.0, 224.0), 'full': (0.0, 255.0, 255.0)}       # luma offset, luma scale, chroma scale
 
 
@@ -103,6 +103,25 @@ def frame_bytes(width, height):
     return width * height * 3 // 2
 
 
+def _read_raw(path, per, frames, start, who):
+    """Frames `start` .. of a raw file of `per` bytes per frame (all of them, or the first `frames`) -> a list of uint8 views, one per
+    frame, of ONE buffer -- pinned when a GPU is there, so a frame's upload is an asynchronous copy.  ValueError: a file size that is
+    not a whole number of frames, no frame in the range, a short read."""
+    size = os.path.getsize(path)
+    if size == 0 or size % per:
+        raise ValueError(f'{who}: {path} holds {size} bytes, not a whole number of frames of {per} bytes')
+    n = size // per - int(start) if frames is None else min(int(frames), size // per - int(start))
+    if n <= 0 or start < 0:
+        raise ValueError(f'{who}: frames={frames}, start={start} of {size // per}')
+    buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    with open(path, 'rb') as f:
+        f.seek(int(start) * per)
+        got = f.readinto(buf.numpy())
+    if got != n * per:
+        raise ValueError(f'{who}: short read of {path}')
+    return [buf[i * per:(i + 1) * per] for i in range(n)]
+
+
 def read_yuv420(path, width, height, fmt='i420', frames=None, start=0):
     """A raw .yuv file of `width` x `height` 8-bit 4:2:0 frames -> list of Yuv420Frame on the CPU (all of them, or the first `frames`; from frame `start` on).
     The file is read into ONE buffer -- pinned when a GPU is there, so a frame's upload is an asynchronous copy -- and the planes are
@@ -110,22 +129,8 @@ def read_yuv420(path, width, height, fmt='i420', frames=None, start=0):
     _check('bt709', 'limited', fmt=fmt)
     if width <= 0 or height <= 0 or width % 2 or height % 2:
         raise ValueError(f'read_yuv420: a 4:2:0 frame has even, positive sides, got {width} x {height}')
-    per = frame_bytes(width, height)
-    size = os.path.getsize(path)
-    if size == 0 or size % per:
-        raise ValueError(f'read_yuv420: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
-    n = size // per - int(start) if frames is None else min(int(frames), size // per - int(start))
-    if n <= 0 or start < 0:
-        raise ValueError(f'read_yuv420: frames={frames}, start={start} of {size // per}')
-    buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-    with open(path, 'rb') as f:
-        f.seek(int(start) * per)
-        got = f.readinto(buf.numpy())
-    if got != n * per:
-        raise ValueError(f'read_yuv420: short read of {path}')
     out, ny, nc = [], width * height, (width // 2) * (height // 2)
-    for i in range(n):
-        fr = buf[i * per:(i + 1) * per]
+    for fr in _read_raw(path, frame_bytes(width, height), frames, start, 'read_yuv420'):
         y = fr[:ny].view(height, width)
         if fmt == 'i420':
             out.append(Yuv420Frame('i420', y, fr[ny:ny + nc].view(height // 2, width // 2), fr[ny + nc:].view(height // 2, width // 2)))
@@ -140,190 +145,6 @@ def write_yuv420(frames, path, append=False):
         for fr in frames:
             for p in fr.planes():
                 f.write(p.cpu().contiguous().numpy().tobytes())
-
-
-# ----------------------------------------------------------------------------------------------- the defining expressions (CPU, fp32)
-def _f32(v):
-    return torch.tensor(v, dtype=torch.float32)
-
-
-def _upsample(c, chroma):
-    """(ch, cw) uint8 chroma -> (2 ch, 2 cw) fp32 at the luma positions, centre siting.  'bilinear': per axis 3/4 of the sample a pixel
-    lies in and 1/4 of the neighbour on the pixel's side, indices clamped at the plane's edges; sixteenths of bytes: exact in fp32."""
-    c = c.to(torch.float32)
-    if chroma == 'nearest':
-        return c.repeat_interleave(2, 0).repeat_interleave(2, 1)
-    for dim in (0, 1):
-        n = c.shape[dim]
-        i = torch.arange(n)
-        prev, nxt = c.index_select(dim, (i - 1).clamp(min=0)), c.index_select(dim, (i + 1).clamp(max=n - 1))
-        even, odd = c * 0.75 + prev * 0.25, c * 0.75 + nxt * 0.25
-        c = torch.stack([even, odd], dim + 1).flatten(dim, dim + 1)
-    return c
-
-
-def yuv_to_rgb_expr(y, u, v, matrix='bt709', range='limited', chroma='bilinear'):
-    """THE DEFINITION of lvae_image_yuv420_to_f32 inside a frame's extent: uint8 planes y (h, w), u, v (h/2, w/2) on the CPU -> (3, h, w)
-    fp32 RGB in [0, 1]."""
-    _check(matrix, range, chroma)
-    _, _, _, a, b, d, e = (_f32(k) for k in COEF[matrix])
-    yo, ys, cs = (_f32(k) for k in SCALES[range])
-    yn = (y.to(torch.float32) - yo) / ys
-    cb = (_upsample(u, chroma) - _f32(128.0)) / cs
-    cr = (_upsample(v, chroma) - _f32(128.0)) / cs
-    r = yn + a * cr
-    bl = yn + b * cb
-    g = (yn - d * cb) - e * cr
-    return torch.stack([r, g, bl]).clamp(0, 1)
-
-
-def rgb_to_yuv_expr(x, matrix='bt709', range='limited'):
-    """THE DEFINITION of lvae_image_f32_to_yuv420: (3, h, w) fp32 RGB on the CPU, h and w even -> uint8 planes y (h, w), u, v (h/2, w/2).
-    Values are clamped to [0, 1] first and a NaN counts as 0."""
-    _check(matrix, range)
-    kr, kg, kb, a, b, _, _ = (_f32(k) for k in COEF[matrix])
-    yo, ys, cs = (_f32(k) for k in SCALES[range])
-    x = x.to(torch.float32)
-    x = torch.where(x > 0, x, torch.zeros((), dtype=torch.float32))
-    x = torch.where(x < 1, x, torch.ones((), dtype=torch.float32))
-    r, g, bl = x[0], x[1], x[2]
-    yn = (kr * r + kg * g) + kb * bl
-    cb, cr = (bl - yn) / b, (r - yn) / a
-    mean4 = lambda c: ((c[0::2, 0::2] + c[0::2, 1::2]) + (c[1::2, 0::2] + c[1::2, 1::2])) * 0.25
-    byte = lambda t: torch.round(t).clamp(0, 255).to(torch.uint8)
-    return byte(yn * ys + yo), byte(mean4(cb) * cs + _f32(128.0)), byte(mean4(cr) * cs + _f32(128.0))
-
-
-# ----------------------------------------------------------------------------------------------- batches and the kernel path
-def _as_frame(f):
-    if not isinstance(f, Yuv420Frame):
-        raise ValueError(f'expected a Yuv420Frame, got {type(f).__name__}')
-    return f
-
-
-def _plane_args(frames):
-    """Host arrays of plane addresses / row strides of device frames of ONE format, as the native entries take them; the second item
-    keeps alive what had to be made contiguous."""
-    fmt = frames[0].fmt
-    if any(f.fmt != fmt for f in frames):
-        raise ValueError('the frames of one call share a plane layout (use Yuv420Frame.as_format)')
-    n, keep = len(frames), []
-
-    def rows_ok(p, unit):
-        return p.stride(-1) == 1 and (p.dim() == 2 or p.stride(1) == 2) and p.stride(0) >= unit
-    ys = [f.y if rows_ok(f.y, f.w) else f.y.contiguous() for f in frames]
-    if fmt == 'i420':
-        us = [f.u if rows_ok(f.u, f.w // 2) else f.u.contiguous() for f in frames]
-        vs = [f.v if rows_ok(f.v, f.w // 2) else f.v.contiguous() for f in frames]
-    else:
-        us = [f.uv if rows_ok(f.uv, f.w) else f.uv.contiguous() for f in frames]
-        vs = None
-    keep = [ys, us, vs]
-    ptr = lambda ps: (ctypes.c_void_p * n)(*[p.data_ptr() for p in ps])
-    row = lambda ps: (ctypes.c_long * n)(*[p.stride(0) for p in ps])
-    hw = (ctypes.c_int * (2 * n))(*[v for f in frames for v in f.size])
-    args = (ptr(ys), ptr(us), ptr(vs) if vs else None, row(ys), row(us), row(vs) if vs else None, hw)
-    return fmt, args, keep
-
-
-class Yuv420Batch:
-    """B 4:2:0 frames on one device that share a canvas (H, W) >= their own sizes, with the colour parameters of their conversion: the
-    utils.image.U8Batch counterpart that CodecBase.compress_yuv420 hands to compress_batch as `u8=`.  `shape` is the fp32 tensor's;
-    `fill(dst, start, n)` converts frames start .. start + n straight into `dst` -- an (n, 3, H, W) fp32 view of an encode plan's input --
-    with one launch on the current stream."""
-
-    def __init__(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear'):
-        _check(matrix, range, chroma)
-        fs = [_as_frame(f) for f in frames]
-        if not fs:
-            raise ValueError('no frames')
-        self.sizes = [f.size for f in fs]
-        H, W = _canvas(self.sizes, div)
-        self.shape = (len(fs), 3, H, W)
-        self.device = torch.device(device)
-        self.matrix, self.range, self.chroma = matrix, range, chroma
-        self.frames = [f.to(self.device, non_blocking=True) for f in fs]      # 1.5 bytes per pixel cross the bus, unpadded
-
-    def fill(self, dst, start=0, n=None):
-        from .. import _native
-        n = len(self.frames) - start if n is None else n
-        _, _, H, W = self.shape
-        assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
-        fmt, args, keep = _plane_args(self.frames[start:start + n])
-        with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _native.check(_native.lib().lvae_image_yuv420_to_f32(
-                *args, n, FORMATS.index(fmt), MATRICES.index(self.matrix), RANGES.index(self.range), CHROMA.index(self.chroma),
-                dst.data_ptr(), dst.stride(0) if n > 1 else 3 * H * W, H, W, st), 'image_yuv420_to_f32')
-        del keep
-
-
-def to_rgb01(frames, div=1, device=None, matrix='bt709', range='limited', chroma='bilinear'):
-    """A list of Yuv420Frame -> ((B, 3, H, W) fp32 RGB in [0, 1], [(h, w)]): chroma upsampled ('nearest' | 'bilinear', centre siting),
-    the inverse matrix applied, clamped, every frame replicate-padded on the right / bottom to the common canvas, the smallest (H, W) of
-    multiples of `div` that holds them all.  CPU frames with device=None: the defining expression on the host.  Otherwise: one upload
-    of each frame's bytes (none for device frames) and one kernel launch for the batch, on `device` (default: the frames' device)."""
-    fs = [_as_frame(f) for f in frames]
-    if not fs:
-        raise ValueError('no frames')
-    if device is None and all(f.device.type == 'cpu' for f in fs):
-        _check(matrix, range, chroma)
-        sizes = [f.size for f in fs]
-        H, W = _canvas(sizes, div)
-        out = []
-        for f in fs:
-            x = yuv_to_rgb_expr(f.y, f.u, f.v, matrix, range, chroma)
-            out.append(F.pad(x.unsqueeze(0), (0, W - f.w, 0, H - f.h), mode='replicate')[0] if f.size != (H, W) else x)
-        return torch.stack(out), sizes
-    if device is None:
-        device = next(f.device for f in fs if f.device.type != 'cpu')
-    batch = Yuv420Batch(fs, div, device, matrix, range, chroma)
-    out = torch.empty(batch.shape, dtype=torch.float32, device=batch.device)
-    batch.fill(out)
-    return out, batch.sizes
-
-
-def from_rgb01(x, sizes=None, fmt='i420', matrix='bt709', range='limited'):
-    """The inverse: fp32 RGB images in [0, 1] -> a list of Yuv420Frame of layout `fmt` on the same device.  Values are clamped to [0, 1]
-    (NaN -> 0), the forward matrix is applied per pixel, a chroma sample is the mean of its 2x2 block, bytes are rounded with ties to
-    even.  x: a (B, 3, H, W) tensor or a list of (1, 3, h, w) / (3, h, w) tensors (crops of a decoder's padded batch are read in place);
-    sizes: per-image valid extents [(h, w)] (default: every item whole); odd extents raise ValueError.  Device tensors: one kernel launch
-    for the batch on the current stream; CPU tensors: the defining expression."""
-    from .views import items, strided_batch
-    _check(matrix, range, fmt=fmt)
-    xs = items(x, 'x')
-    if sizes is not None:
-        if len(sizes) != len(xs):
-            raise ValueError(f'from_rgb01: {len(sizes)} sizes for {len(xs)} images')
-        xs = [v[:, :h, :w] for v, (h, w) in zip(xs, sizes)]
-    if not xs or any(v.shape[0] != 3 or v.shape[1] == 0 or v.shape[2] == 0 for v in xs):
-        raise ValueError('from_rgb01: expected 3-channel, non-empty images')
-    if any(v.shape[1] % 2 or v.shape[2] % 2 for v in xs):
-        raise ValueError(f'from_rgb01: a 4:2:0 frame has even sides, got {[tuple(v.shape[1:]) for v in xs]}')
-    device = xs[0].device
-    if device.type == 'cpu':
-        return [Yuv420Frame('i420', *rgb_to_yuv_expr(v, matrix, range)).as_format(fmt) for v in xs]
-    from .. import _native
-    B = len(xs)
-    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
-    hmax, wmax = max(h for h, _ in hw), max(w for _, w in hw)
-    with torch.cuda.device(device):
-        keep, px, (s_img, s_plane, s_row) = strided_batch(xs, hmax, wmax, device)
-        span = (hmax - 1) * s_row + wmax             # views whose common strides do not hold the largest extent are packed instead
-        if s_row < wmax or s_plane < span or (B > 1 and s_img < 2 * s_plane + span):
-            keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in xs], hmax, wmax, device)
-        new = lambda *s: torch.empty(*s, dtype=torch.uint8, device=device)
-        if fmt == 'i420':
-            outs = [Yuv420Frame('i420', new(h, w), new(h // 2, w // 2), new(h // 2, w // 2)) for h, w in hw]
-        else:
-            outs = [Yuv420Frame('nv12', new(h, w), uv=new(h // 2, w // 2, 2)) for h, w in hw]
-        _, args, _ = _plane_args(outs)
-        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _native.check(_native.lib().lvae_image_f32_to_yuv420(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[6], B,
-                                                             FORMATS.index(fmt), MATRICES.index(matrix), RANGES.index(range), *args[:6], st),
-                      'image_f32_to_yuv420')
-    del keep
-    return outs
 
 
 # =============================================================================================== 8 / 10 / 12 bits, 4:2:0 / 4:2:2 / 4:4:4
@@ -419,19 +240,6 @@ def read_yuv(path, width, height, subsampling='420', depth=8, frames=None, start
     _check2(depth, subsampling)
     if not _extent_ok(height, width, subsampling):
         raise ValueError(f'read_yuv: {width} x {height} does not fit subsampling {subsampling}')
-    per = frame_bytes2(width, height, subsampling, depth)
-    size = os.path.getsize(path)
-    if size == 0 or size % per:
-        raise ValueError(f'read_yuv: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
-    n = size // per - int(start) if frames is None else min(int(frames), size // per - int(start))
-    if n <= 0 or start < 0:
-        raise ValueError(f'read_yuv: frames={frames}, start={start} of {size // per}')
-    buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-    with open(path, 'rb') as f:
-        f.seek(int(start) * per)
-        got = f.readinto(buf.numpy())
-    if got != n * per:
-        raise ValueError(f'read_yuv: short read of {path}')
     sx, sy = SHIFTS[subsampling]
     bps = 1 if depth == 8 else 2
     ny, nc = width * height * bps, (width >> sx) * (height >> sy) * bps
@@ -439,8 +247,7 @@ def read_yuv(path, width, height, subsampling='420', depth=8, frames=None, start
     def plane(b, h, w):
         return (b if depth == 8 else b.view(torch.int16)).view(h, w)
     out = []
-    for i in range(n):
-        fr = buf[i * per:(i + 1) * per]
+    for fr in _read_raw(path, frame_bytes2(width, height, subsampling, depth), frames, start, 'read_yuv'):
         out.append(YuvFrame(plane(fr[:ny], height, width), plane(fr[ny:ny + nc], height >> sy, width >> sx),
                             plane(fr[ny + nc:], height >> sy, width >> sx), depth, subsampling))
     return out
@@ -523,23 +330,9 @@ def read_yuv_sp(path, width, height, depth=10, subsampling='420', frames=None, s
         raise ValueError(f'read_yuv_sp: semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth!r} bits at {subsampling!r}')
     if not _extent_ok(height, width, subsampling):
         raise ValueError(f'read_yuv_sp: {width} x {height} does not fit subsampling {subsampling}')
-    per = frame_bytes2(width, height, subsampling, depth)    # as many samples as the planar layout
-    size = os.path.getsize(path)
-    if size == 0 or size % per:
-        raise ValueError(f'read_yuv_sp: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
-    n = size // per - int(start) if frames is None else min(int(frames), size // per - int(start))
-    if n <= 0 or start < 0:
-        raise ValueError(f'read_yuv_sp: frames={frames}, start={start} of {size // per}')
-    buf = torch.empty(n * per, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-    with open(path, 'rb') as f:
-        f.seek(int(start) * per)
-        got = f.readinto(buf.numpy())
-    if got != n * per:
-        raise ValueError(f'read_yuv_sp: short read of {path}')
     ny, ch = 2 * width * height, height >> SHIFTS[subsampling][1]
     out = []
-    for i in range(n):
-        fr = buf[i * per:(i + 1) * per]
+    for fr in _read_raw(path, frame_bytes2(width, height, subsampling, depth), frames, start, 'read_yuv_sp'):   # as many samples as the planar layout
         out.append(YuvSpFrame(fr[:ny].view(torch.int16).view(height, width), fr[ny:].view(torch.int16).view(ch, width), depth, subsampling))
     return out
 
@@ -553,6 +346,10 @@ def write_yuv_sp(frames, path, append=False):
 
 
 # ----------------------------------------------------------------------------------------------- the defining expressions (CPU, fp32)
+def _f32(v):
+    return torch.tensor(v, dtype=torch.float32)
+
+
 def _scales2(depth, range):
     """fp32 luma offset, luma scale, chroma offset, chroma scale and the largest code (all integers: exact)."""
     s, peak = float(1 << (depth - 8)), float((1 << depth) - 1)
@@ -594,7 +391,7 @@ def _upsample2(c, depth, subsampling, siting, chroma):
 
 def yuv_to_rgb_expr2(y, u, v, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', chroma='bilinear'):
     """THE DEFINITION of lvae_image_yuv_to_f32 inside a frame's extent: the planes of a YuvFrame on the CPU -> (3, h, w) fp32 RGB in
-    [0, 1].  At depth 8, '420', 'center' and the matrices of yuv_to_rgb_expr it is that expression, bit for bit."""
+    [0, 1]."""
     _check2(depth, subsampling, siting, matrix, range, chroma)
     _, _, _, a, b, d, e = (_f32(k) for k in COEF[matrix])
     yo, ys, co, cs, _ = _scales2(depth, range)
@@ -639,49 +436,65 @@ def rgb_to_yuv_expr2(x, depth=8, subsampling='420', siting='center', matrix='bt7
     return (code(yn * ys + yo), code(_downsample2(cb, subsampling, siting) * cs + co), code(_downsample2(cr, subsampling, siting) * cs + co))
 
 
+def yuv_to_rgb_expr(y, u, v, matrix='bt709', range='limited', chroma='bilinear'):
+    """THE DEFINITION of lvae_image_yuv420_to_f32 inside a frame's extent: uint8 planes y (h, w), u, v (h/2, w/2) on the CPU -> (3, h, w)
+    fp32 RGB in [0, 1]: yuv_to_rgb_expr2 at depth 8, '420', 'center', for BT.601 / BT.709."""
+    _check(matrix, range, chroma)
+    return yuv_to_rgb_expr2(y, u, v, 8, '420', 'center', matrix, range, chroma)
+
+
+def rgb_to_yuv_expr(x, matrix='bt709', range='limited'):
+    """THE DEFINITION of lvae_image_f32_to_yuv420: (3, h, w) fp32 RGB on the CPU, h and w even -> uint8 planes y (h, w), u, v (h/2, w/2):
+    rgb_to_yuv_expr2 at depth 8, '420', 'center', for BT.601 / BT.709.  Values are clamped to [0, 1] first and a NaN counts as 0."""
+    _check(matrix, range)
+    return rgb_to_yuv_expr2(x, 8, '420', 'center', matrix, range)
+
+
 # ----------------------------------------------------------------------------------------------- batches and the kernel path
-def _as_frame2(f):
-    if not isinstance(f, YuvFrame):
-        raise ValueError(f'expected a YuvFrame, got {type(f).__name__}')
-    return f
+def _as_frames(frames, frame_type):
+    fs = list(frames)
+    for f in fs:
+        if not isinstance(f, frame_type):
+            raise ValueError(f'expected a {frame_type.__name__}, got {type(f).__name__}')
+    if not fs:
+        raise ValueError('no frames')
+    return fs
 
 
-def _plane_args2(frames):
-    """Host arrays of plane addresses / row strides IN SAMPLES of device frames of one depth and subsampling, as lvae_image_yuv_to_f32 /
-    lvae_image_f32_to_yuv take them; the second item keeps alive what had to be made contiguous."""
+def _share_layout(fs):
+    if any((f.depth, f.subsampling) != (fs[0].depth, fs[0].subsampling) for f in fs):
+        raise ValueError('the frames of one call share depth and subsampling')
+
+
+def _plane_args(frames, names):
+    """Host arrays, as the native entries take them, of device frames' planes `names` (None: an argument the entry does not read):
+    addresses, row strides in samples, the (h, w) pairs -- and, last, what had to be made contiguous, to be kept alive."""
     n = len(frames)
-    rows_ok = lambda p: p.stride(1) == 1 and p.stride(0) >= p.shape[1]
-    ps = [[p if rows_ok(p) else p.contiguous() for p in (getattr(f, k) for f in frames)] for k in 'yuv']
-    ptr = lambda q: (ctypes.c_void_p * n)(*[p.data_ptr() for p in q])
-    row = lambda q: (ctypes.c_long * n)(*[p.stride(0) for p in q])
+    # a plane is read where it lies if its rows are dense -- (h, w), or (h, w / 2, 2) for the uv of NV12 -- and do not overlap
+    # (strides and sizes only: indexing a tensor here costs more host time than the launch)
+    rows_ok = lambda p: p.stride(-1) == 1 and (p.dim() == 2 or p.stride(1) == 2) and p.stride(0) >= p.size(1) * (p.dim() - 1)
+    ps = [k and [p if rows_ok(p) else p.contiguous() for p in (getattr(f, k) for f in frames)] for k in names]
+    ptrs = [q and (ctypes.c_void_p * n)(*[p.data_ptr() for p in q]) for q in ps]
+    rows = [q and (ctypes.c_long * n)(*[p.stride(0) for p in q]) for q in ps]
     hw = (ctypes.c_int * (2 * n))(*[v for f in frames for v in f.size])
-    return (ptr(ps[0]), ptr(ps[1]), ptr(ps[2]), row(ps[0]), row(ps[1]), row(ps[2]), hw), ps
+    return ptrs, rows, hw, ps
 
 
-class YuvBatch:
-    """B YuvFrames of one depth and subsampling on one device that share a canvas (H, W) >= their own sizes, with the parameters of their
-    conversion: what CodecBase.compress_yuv hands to compress_batch as `u8=` (the Yuv420Batch of this path).  `shape` is the fp32 tensor's;
-    `fill(dst, start, n)` converts frames start .. start + n straight into `dst` -- an (n, 3, H, W) fp32 view of an encode plan's input --
-    with one launch on the current stream."""
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
-    frame_type = YuvFrame
 
-    def __init__(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
-        fs = list(frames)
-        for f in fs:
-            if not isinstance(f, self.frame_type):
-                raise ValueError(f'expected a {self.frame_type.__name__}, got {type(f).__name__}')
-        if not fs:
-            raise ValueError('no frames')
-        self.depth, self.subsampling = fs[0].depth, fs[0].subsampling
-        if any((f.depth, f.subsampling) != (self.depth, self.subsampling) for f in fs):
-            raise ValueError('the frames of one call share depth and subsampling')
-        _check2(self.depth, self.subsampling, siting, matrix, range, chroma)
+class _Batch:
+    """B frames on one device that share a canvas (H, W) >= their own sizes, with the parameters of their conversion: the
+    utils.image.U8Batch counterpart that the codecs hand to compress_batch as `u8=`.  `shape` is the fp32 tensor's; `fill(dst, start, n)`
+    converts frames start .. start + n straight into `dst` -- an (n, 3, H, W) fp32 view of an encode plan's input -- with one launch on
+    the current stream.  A subclass's `_entry(frames)` says which entry that is: its name, the planes it takes and the codes before `dst`."""
+
+    def __init__(self, fs, div, device):
         self.sizes = [f.size for f in fs]
         H, W = _canvas(self.sizes, div)
         self.shape = (len(fs), 3, H, W)
         self.device = torch.device(device)
-        self.matrix, self.range, self.chroma, self.siting = matrix, range, chroma, siting
         self.frames = [f.to(self.device, non_blocking=True) for f in fs]      # the file's bytes cross the bus, unpadded
 
     def fill(self, dst, start=0, n=None):
@@ -689,45 +502,83 @@ class YuvBatch:
         n = len(self.frames) - start if n is None else n
         _, _, H, W = self.shape
         assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
-        args, keep = _plane_args2(self.frames[start:start + n])
+        entry, names, codes = self._entry(self.frames[start:start + n])
+        ptrs, rows, hw, keep = _plane_args(self.frames[start:start + n], names)
         with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _native.check(_native.lib().lvae_image_yuv_to_f32(
-                *args, n, self.depth, SUBSAMPLINGS.index(self.subsampling), SITINGS.index(self.siting), MATRICES2.index(self.matrix),
-                RANGES.index(self.range), CHROMA.index(self.chroma), dst.data_ptr(), dst.stride(0) if n > 1 else 3 * H * W, H, W, st),
-                'image_yuv_to_f32')
+            _native.check(getattr(_native.lib(), 'lvae_' + entry)(*ptrs, *rows, hw, n, *codes, CHROMA.index(self.chroma), dst.data_ptr(),
+                                                                 dst.stride(0) if n > 1 else 3 * H * W, H, W, _stream(self.device)), entry)
         del keep
 
 
-def _plane_args_sp(frames):
-    """_plane_args2 for YuvSpFrames, as lvae_image_yuvsp_to_f32 / lvae_image_f32_to_yuvsp take them: (y, uv, y_row, uv_row, hw)."""
-    n = len(frames)
-    rows_ok = lambda p: p.stride(1) == 1 and p.stride(0) >= p.shape[1]
-    ps = [[p if rows_ok(p) else p.contiguous() for p in (getattr(f, k) for f in frames)] for k in ('y', 'uv')]
-    ptr = lambda q: (ctypes.c_void_p * n)(*[p.data_ptr() for p in q])
-    row = lambda q: (ctypes.c_long * n)(*[p.stride(0) for p in q])
-    hw = (ctypes.c_int * (2 * n))(*[v for f in frames for v in f.size])
-    return (ptr(ps[0]), ptr(ps[1]), row(ps[0]), row(ps[1]), hw), ps
+def _fmt_names(frames):
+    """The planes of Yuv420Frames of ONE format as lvae_image_yuv420_to_f32 / lvae_image_f32_to_yuv420 take them: NV12 has no v."""
+    if any(f.fmt != frames[0].fmt for f in frames):
+        raise ValueError('the frames of one call share a plane layout (use Yuv420Frame.as_format)')
+    return ('y', 'u', 'v') if frames[0].fmt == 'i420' else ('y', 'uv', None)
+
+
+class Yuv420Batch(_Batch):
+    """_Batch of Yuv420Frames: what CodecBase.compress_yuv420 hands to compress_batch; 1.5 bytes per pixel cross the bus."""
+
+    def __init__(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear'):
+        _check(matrix, range, chroma)
+        self.matrix, self.range, self.chroma = matrix, range, chroma
+        super().__init__(_as_frames(frames, Yuv420Frame), div, device)
+
+    def _entry(self, frames):
+        return 'image_yuv420_to_f32', _fmt_names(frames), (FORMATS.index(frames[0].fmt), MATRICES.index(self.matrix), RANGES.index(self.range))
+
+
+class YuvBatch(_Batch):
+    """_Batch of YuvFrames of one depth and subsampling: what CodecBase.compress_yuv hands to compress_batch."""
+
+    frame_type, entry, names = YuvFrame, 'image_yuv_to_f32', ('y', 'u', 'v')
+
+    def __init__(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
+        fs = _as_frames(frames, self.frame_type)
+        self.depth, self.subsampling = fs[0].depth, fs[0].subsampling
+        _share_layout(fs)
+        _check2(self.depth, self.subsampling, siting, matrix, range, chroma)
+        self.matrix, self.range, self.chroma, self.siting = matrix, range, chroma, siting
+        super().__init__(fs, div, device)
+
+    def _entry(self, frames):
+        return self.entry, self.names, (self.depth, SUBSAMPLINGS.index(self.subsampling), SITINGS.index(self.siting),
+                                        MATRICES2.index(self.matrix), RANGES.index(self.range))
 
 
 class YuvSpBatch(YuvBatch):
     """YuvBatch for YuvSpFrames: the two planes of every frame go to the device as the file holds them, and `fill` is one
     lvae_image_yuvsp_to_f32 launch -- no deinterleaved or shifted copy exists anywhere."""
-    frame_type = YuvSpFrame
+    frame_type, entry, names = YuvSpFrame, 'image_yuvsp_to_f32', ('y', 'uv')
 
-    def fill(self, dst, start=0, n=None):
-        from .. import _native
-        n = len(self.frames) - start if n is None else n
-        _, _, H, W = self.shape
-        assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
-        args, keep = _plane_args_sp(self.frames[start:start + n])
-        with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _native.check(_native.lib().lvae_image_yuvsp_to_f32(
-                *args, n, self.depth, SUBSAMPLINGS.index(self.subsampling), SITINGS.index(self.siting), MATRICES2.index(self.matrix),
-                RANGES.index(self.range), CHROMA.index(self.chroma), dst.data_ptr(), dst.stride(0) if n > 1 else 3 * H * W, H, W, st),
-                'image_yuvsp_to_f32')
-        del keep
+
+def _to_rgb(fs, div, device, expr, batch):
+    """The two paths of to_rgb01 / to_rgb01_any.  CPU frames with device=None: expr(frame), replicate-padded to the canvas and stacked.
+    Otherwise batch(device) filled into a new tensor on `device` (default: the first frame's that is not the CPU)."""
+    if device is None and all(f.device.type == 'cpu' for f in fs):
+        sizes = [f.size for f in fs]
+        H, W = _canvas(sizes, div)
+        out = []
+        for f in fs:
+            x = expr(f)
+            out.append(F.pad(x.unsqueeze(0), (0, W - f.w, 0, H - f.h), mode='replicate')[0] if f.size != (H, W) else x)
+        return torch.stack(out), sizes
+    b = batch(next(f.device for f in fs if f.device.type != 'cpu') if device is None else device)
+    out = torch.empty(b.shape, dtype=torch.float32, device=b.device)
+    b.fill(out)
+    return out, b.sizes
+
+
+def to_rgb01(frames, div=1, device=None, matrix='bt709', range='limited', chroma='bilinear'):
+    """A list of Yuv420Frame -> ((B, 3, H, W) fp32 RGB in [0, 1], [(h, w)]): chroma upsampled ('nearest' | 'bilinear', centre siting),
+    the inverse matrix applied, clamped, every frame replicate-padded on the right / bottom to the common canvas, the smallest (H, W) of
+    multiples of `div` that holds them all.  CPU frames with device=None: the defining expression on the host.  Otherwise: one upload
+    of each frame's bytes (none for device frames) and one kernel launch for the batch, on `device` (default: the frames' device)."""
+    fs = _as_frames(frames, Yuv420Frame)
+    _check(matrix, range, chroma)
+    return _to_rgb(fs, div, device, lambda f: yuv_to_rgb_expr(f.y, f.u, f.v, matrix, range, chroma),
+                   lambda dev: Yuv420Batch(fs, div, dev, matrix, range, chroma))
 
 
 def to_rgb01_any(frames, div=1, device=None, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
@@ -735,35 +586,68 @@ def to_rgb01_any(frames, div=1, device=None, matrix='bt709', range='limited', ch
     'left' (where the chroma samples lie horizontally; see the module docstring); matrix also 'bt2020'.  CPU frames with device=None: the
     defining expression on the host.  Otherwise one upload of each frame's bytes and one kernel launch for the batch.  A list of
     YuvSpFrame is taken too: on the host through to_planar (the definition), on the device by its own kernel."""
-    frames = list(frames)
-    if frames and all(isinstance(f, YuvSpFrame) for f in frames):
-        if device is None and all(f.device.type == 'cpu' for f in frames):
-            return to_rgb01_any([f.to_planar() for f in frames], div, None, matrix, range, chroma, siting)
-        batch = YuvSpBatch(frames, div, next(f.device for f in frames if f.device.type != 'cpu') if device is None else device,
-                           matrix, range, chroma, siting)
-        out = torch.empty(batch.shape, dtype=torch.float32, device=batch.device)
-        batch.fill(out)
-        return out, batch.sizes
-    fs = [_as_frame2(f) for f in frames]
-    if not fs:
-        raise ValueError('no frames')
-    if device is None and all(f.device.type == 'cpu' for f in fs):
-        if any((f.depth, f.subsampling) != (fs[0].depth, fs[0].subsampling) for f in fs):
-            raise ValueError('the frames of one call share depth and subsampling')
-        _check2(fs[0].depth, fs[0].subsampling, siting, matrix, range, chroma)
-        sizes = [f.size for f in fs]
-        H, W = _canvas(sizes, div)
-        out = []
-        for f in fs:
-            x = yuv_to_rgb_expr2(f.y, f.u, f.v, f.depth, f.subsampling, siting, matrix, range, chroma)
-            out.append(F.pad(x.unsqueeze(0), (0, W - f.w, 0, H - f.h), mode='replicate')[0] if f.size != (H, W) else x)
-        return torch.stack(out), sizes
-    if device is None:
-        device = next(f.device for f in fs if f.device.type != 'cpu')
-    batch = YuvBatch(fs, div, device, matrix, range, chroma, siting)
-    out = torch.empty(batch.shape, dtype=torch.float32, device=batch.device)
-    batch.fill(out)
-    return out, batch.sizes
+    fs = list(frames)
+    sp = bool(fs) and all(isinstance(f, YuvSpFrame) for f in fs)
+    if sp and device is None and all(f.device.type == 'cpu' for f in fs):
+        fs, sp = [f.to_planar() for f in fs], False
+    fs = _as_frames(fs, YuvSpFrame if sp else YuvFrame)
+    _share_layout(fs)
+    _check2(fs[0].depth, fs[0].subsampling, siting, matrix, range, chroma)
+    return _to_rgb(fs, div, device, lambda f: yuv_to_rgb_expr2(f.y, f.u, f.v, f.depth, f.subsampling, siting, matrix, range, chroma),
+                   lambda dev: (YuvSpBatch if sp else YuvBatch)(fs, div, dev, matrix, range, chroma, siting))
+
+
+def _rgb_items(x, sizes, who):
+    """The prelude of from_rgb01 / from_rgb01_any: x as a list of (3, h, w) views cut to `sizes`."""
+    from .views import items
+    xs = items(x, 'x')
+    if sizes is not None:
+        if len(sizes) != len(xs):
+            raise ValueError(f'{who}: {len(sizes)} sizes for {len(xs)} images')
+        xs = [v[:, :h, :w] for v, (h, w) in zip(xs, sizes)]
+    if not xs or any(v.shape[0] != 3 or v.shape[1] == 0 or v.shape[2] == 0 for v in xs):
+        raise ValueError(f'{who}: expected 3-channel, non-empty images')
+    return xs
+
+
+def _from_rgb(xs, outs, names, entry, codes):
+    """Device images xs -> the planes `names` of the frames `outs` (of the images' sizes), by one launch of `entry` on the current stream."""
+    from .. import _native
+    from .views import strided_batch
+    B, device = len(xs), xs[0].device
+    hmax, wmax = max(f.h for f in outs), max(f.w for f in outs)
+    with torch.cuda.device(device):
+        keep, px, (s_img, s_plane, s_row) = strided_batch(xs, hmax, wmax, device)
+        span = (hmax - 1) * s_row + wmax             # views whose common strides do not hold the largest extent are packed instead
+        if s_row < wmax or s_plane < span or (B > 1 and s_img < 2 * s_plane + span):
+            keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in xs], hmax, wmax, device)
+        ptrs, rows, hw, _ = _plane_args(outs, names)
+        _native.check(getattr(_native.lib(), 'lvae_' + entry)(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, hw, B, *codes,
+                                                             *ptrs, *rows, _stream(device)), entry)
+    del keep
+    return outs
+
+
+def from_rgb01(x, sizes=None, fmt='i420', matrix='bt709', range='limited'):
+    """The inverse: fp32 RGB images in [0, 1] -> a list of Yuv420Frame of layout `fmt` on the same device.  Values are clamped to [0, 1]
+    (NaN -> 0), the forward matrix is applied per pixel, a chroma sample is the mean of its 2x2 block, bytes are rounded with ties to
+    even.  x: a (B, 3, H, W) tensor or a list of (1, 3, h, w) / (3, h, w) tensors (crops of a decoder's padded batch are read in place);
+    sizes: per-image valid extents [(h, w)] (default: every item whole); odd extents raise ValueError.  Device tensors: one kernel launch
+    for the batch on the current stream; CPU tensors: the defining expression."""
+    _check(matrix, range, fmt=fmt)
+    xs = _rgb_items(x, sizes, 'from_rgb01')
+    if any(v.shape[1] % 2 or v.shape[2] % 2 for v in xs):
+        raise ValueError(f'from_rgb01: a 4:2:0 frame has even sides, got {[tuple(v.shape[1:]) for v in xs]}')
+    device = xs[0].device
+    if device.type == 'cpu':
+        return [Yuv420Frame('i420', *rgb_to_yuv_expr(v, matrix, range)).as_format(fmt) for v in xs]
+    new = lambda *s: torch.empty(*s, dtype=torch.uint8, device=device)
+    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
+    if fmt == 'i420':
+        outs = [Yuv420Frame('i420', new(h, w), new(h // 2, w // 2), new(h // 2, w // 2)) for h, w in hw]
+    else:
+        outs = [Yuv420Frame('nv12', new(h, w), uv=new(h // 2, w // 2, 2)) for h, w in hw]
+    return _from_rgb(xs, outs, _fmt_names(outs), 'image_f32_to_yuv420', (FORMATS.index(fmt), MATRICES.index(matrix), RANGES.index(range)))
 
 
 def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar'):
@@ -771,50 +655,25 @@ def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', m
     chroma sampled for `siting`.  x, sizes: as in from_rgb01; extents that do not fit the subsampling raise ValueError.  Device tensors: one
     kernel launch for the batch on the current stream; CPU tensors: the defining expression.  layout 'semiplanar' (depth 10 | 12, '420' |
     '422'): a list of YuvSpFrame holding the same codes, written by lvae_image_f32_to_yuvsp (CPU: to_semiplanar of the expression's frame)."""
-    from .views import items, strided_batch
     _check2(depth, subsampling, siting, matrix, range)
     if layout not in LAYOUTS:
         raise ValueError(f'layout is one of {LAYOUTS}, got {layout!r}')
     sp = layout == 'semiplanar'
     if sp and (depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS):
         raise ValueError(f'semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth} bits at {subsampling}')
-    xs = items(x, 'x')
-    if sizes is not None:
-        if len(sizes) != len(xs):
-            raise ValueError(f'from_rgb01_any: {len(sizes)} sizes for {len(xs)} images')
-        xs = [v[:, :h, :w] for v, (h, w) in zip(xs, sizes)]
-    if not xs or any(v.shape[0] != 3 or v.shape[1] == 0 or v.shape[2] == 0 for v in xs):
-        raise ValueError('from_rgb01_any: expected 3-channel, non-empty images')
+    xs = _rgb_items(x, sizes, 'from_rgb01_any')
     if any(not _extent_ok(int(v.shape[1]), int(v.shape[2]), subsampling) for v in xs):
         raise ValueError(f'from_rgb01_any: sizes {[tuple(v.shape[1:]) for v in xs]} do not fit subsampling {subsampling}')
     device = xs[0].device
     if device.type == 'cpu':
         outs = [YuvFrame(*rgb_to_yuv_expr2(v, depth, subsampling, siting, matrix, range), depth, subsampling) for v in xs]
         return [f.to_semiplanar() for f in outs] if sp else outs
-    from .. import _native
-    B = len(xs)
-    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
-    hmax, wmax = max(h for h, _ in hw), max(w for _, w in hw)
     sx, sy = SHIFTS[subsampling]
-    with torch.cuda.device(device):
-        keep, px, (s_img, s_plane, s_row) = strided_batch(xs, hmax, wmax, device)
-        span = (hmax - 1) * s_row + wmax             # views whose common strides do not hold the largest extent are packed instead
-        if s_row < wmax or s_plane < span or (B > 1 and s_img < 2 * s_plane + span):
-            keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in xs], hmax, wmax, device)
-        new = lambda *s: torch.empty(*s, dtype=torch.uint8 if depth == 8 else torch.int16, device=device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        codes = (depth, SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix), RANGES.index(range))
-        if sp:
-            outs = [YuvSpFrame(new(h, w), new(h >> sy, w), depth, subsampling) for h, w in hw]
-            args, _ = _plane_args_sp(outs)
-            _native.check(_native.lib().lvae_image_f32_to_yuvsp(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[4], B, *codes,
-                                                                *args[:4], st), 'image_f32_to_yuvsp')
-            del keep
-            return outs
-        outs = [YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling) for h, w in hw]
-        args, _ = _plane_args2(outs)
-        _native.check(_native.lib().lvae_image_f32_to_yuv(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hmax, wmax, args[6], B, depth,
-                                                          SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix),
-                                                          RANGES.index(range), *args[:6], st), 'image_f32_to_yuv')
-    del keep
-    return outs
+    new = lambda *s: torch.empty(*s, dtype=torch.uint8 if depth == 8 else torch.int16, device=device)
+    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
+    codes = (depth, SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix), RANGES.index(range))
+    if sp:
+        return _from_rgb(xs, [YuvSpFrame(new(h, w), new(h >> sy, w), depth, subsampling) for h, w in hw], YuvSpBatch.names, 'image_f32_to_yuvsp', codes)
+    outs = [YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling) for h, w in hw]
+    return _from_rgb(xs, outs, YuvBatch.names, 'image_f32_to_yuv', codes)
+

@@ -114,12 +114,7 @@ def test_yuv420_to_f32_all_values():
 @pytest.fixture(scope='module')
 def f32_batch():
     """(5, 3, 128, 192) fp32 in [-0.1, 1.1] with exact 0 / 1 / out-of-range values, a NaN and infinities in every image's corner."""
-    g = torch.Generator().manual_seed(6)
-    x = torch.rand(5, 3, 128, 192, generator=g) * 1.2 - 0.1
-    x[:, :, 0, :6] = torch.tensor([0.0, 1.0, 2.0, -1.0, 0.5, 0.25])
-    x[:, 0, 1, 0] = float('nan')
-    x[:, 1, 1, 1] = float('inf')
-    x[:, 2, 0, 1] = float('-inf')
+    x = yuv_ref.rgb_batch()
     return x, x.to(DEV)
 
 
@@ -180,6 +175,80 @@ def test_f32_to_yuv420_strided_misaligned_output(f32_batch):
             mask = torch.ones(buf.numel(), dtype=torch.bool)
             mask[1:].as_strided(tuple(v.shape), v.stride()).fill_(False)
             assert bool((buf.cpu()[mask] == 7).all()), (i, k)
+
+
+def test_f32_to_yuv420_nv12_every_store_path(f32_batch):
+    """The C entry with fmt NV12: planes that start 0, 1, 2 and 3 bytes past a 4-byte-aligned address, Y rows of w + 5 and UV rows of
+    w + 4 bytes.  Widths 2 and 6 end in a block with two valid columns; a UV block leaves as one dword, as two half-dwords or byte by
+    byte, as its address allows.  Every path writes the definition's bytes, and only the planes are written."""
+    from lvae import _native
+    x, xd = f32_batch
+    sizes = [(2, 2), (2, 6), (4, 8), (6, 10), (66, 130)]
+    n = len(sizes)
+    ref = _cpu_frames(x, sizes, 'nv12')
+    hw = (ctypes.c_int * (2 * n))(*[v for s in sizes for v in s])
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for off in range(4):
+        bufs, views = [], []
+        for h, w in sizes:
+            for ph, row in ((h, w + 5), (h // 2, w + 4)):
+                buf = torch.full((4 + ph * row,), 7, dtype=torch.uint8, device=DEV)
+                bufs.append(buf)
+                views.append(buf[off:].as_strided((ph, w), (row, 1)))
+                assert views[-1].data_ptr() % 4 == off
+        arr = lambda k: (ctypes.c_void_p * n)(*[views[2 * i + k].data_ptr() for i in range(n)])
+        row = lambda k: (ctypes.c_long * n)(*[views[2 * i + k].stride(0) for i in range(n)])
+        rc = _native.lib().lvae_image_f32_to_yuv420(xd.data_ptr(), 3 * 128 * 192, 128 * 192, 192, 128, 192, hw, n, 1, 1, 0, arr(0), arr(1), None,
+                                                    row(0), row(1), None, st)
+        assert rc == 0
+        torch.cuda.synchronize()
+        for i in range(n):
+            for k, p in enumerate((ref[i].y, ref[i].uv.flatten(1))):
+                v, buf = views[2 * i + k], bufs[2 * i + k]
+                assert torch.equal(v.cpu(), p), (off, i, k)
+                mask = torch.ones(buf.numel(), dtype=torch.bool)
+                mask[off:].as_strided(tuple(v.shape), v.stride()).fill_(False)
+                assert bool((buf.cpu()[mask] == 7).all()), (off, i, k)
+
+
+@pytest.mark.parametrize('chroma', ['nearest', 'bilinear'])
+@pytest.mark.parametrize('fmt', ['i420', 'nv12'])
+def test_yuv420_to_f32_edges_and_alignments(fmt, chroma):
+    """Frames narrower and lower than their 16 x 16 canvas -- widths 2 and 6 end in the right-edge path, 8 and 12 in whole quads, and the
+    rows below the extent repeat its last row -- read in place from planes 0, 1, 2 and 3 bytes past a 4-byte-aligned address."""
+    sizes = [(h, w) for h in (2, 6) for w in (2, 6, 8, 12)]
+    planes = [yuv_ref.noise_planes(h, w, 100 + i) for i, (h, w) in enumerate(sizes)]
+    ref, _ = to_rgb01([_frame(p) for p in planes], div=16, chroma=chroma)
+    assert tuple(ref.shape) == (8, 3, 16, 16)
+    for off in range(4):
+        def view(p):
+            p = torch.from_numpy(p)
+            row = p[0].numel() + 5
+            buf = torch.zeros(4 + p.shape[0] * row, dtype=torch.uint8, device=DEV)
+            v = buf[off:].as_strided(tuple(p.shape), (row,) + ((2, 1) if p.dim() == 3 else (1,)))
+            v.copy_(p)
+            assert v.data_ptr() % 4 == off
+            return v
+        if fmt == 'i420':
+            frames = [Yuv420Frame('i420', view(y), view(u), view(v)) for y, u, v in planes]
+        else:
+            frames = [Yuv420Frame('nv12', view(y), uv=view(yuv_ref.nv12_uv(u, v))) for y, u, v in planes]
+        b = Yuv420Batch(frames, 16, DEV, chroma=chroma)
+        out = torch.empty(b.shape, dtype=torch.float32, device=DEV)
+        b.fill(out)
+        assert torch.equal(out.cpu(), ref), off
+
+
+@pytest.mark.parametrize('fmt', ['i420', 'nv12'])
+def test_yuv420_seventeen_frames_cross_the_launch_chunk(fmt):
+    """B = 17 is one frame more than a launch takes: in and out, frames of 4 x 4, 6 x 8 and 8 x 12 mixed."""
+    sizes = [(4 + 2 * (i % 3), 4 + 4 * (i % 3)) for i in range(17)]
+    planes = [yuv_ref.noise_planes(h, w, 200 + i) for i, (h, w) in enumerate(sizes)]
+    ref, _ = to_rgb01([_frame(p) for p in planes])
+    x, got = to_rgb01([_frame(p, fmt) for p in planes], device=DEV)
+    assert got == sizes and tuple(x.shape) == (17, 3, 8, 12) and torch.equal(x.cpu(), ref)
+    out, want = from_rgb01(x, sizes, fmt=fmt), from_rgb01(ref, sizes, fmt=fmt)
+    assert len(out) == 17 and all(o.y.is_cuda and _planes_equal(o, w) for o, w in zip(out, want))
 
 
 # ----------------------------------------------------------------------------------------------- lvae_sse_u8

@@ -1,5 +1,5 @@
 """-m gpu: planar YUV frames of 8 / 10 / 12 bits at 4:2:0 / 4:2:2 / 4:4:4 with centre- or left-sited chroma, end to end.  The three kernels of
-csrc/yuv_hbd_io.hip against the CPU expressions that define them (lvae/utils/yuv.py; torch.equal / ==: every bit), then the model-level API
+csrc/yuv_io.hip against the CPU expressions that define them (lvae/utils/yuv.py; torch.equal / ==: every bit), then the model-level API
 against the float path spelled out here, yuv_evaluate against its per-frame loop, and scripts/lvae-codec.py encode-yuv / decode-yuv with
 --depth 10 against decompress_yuv."""
 import ctypes

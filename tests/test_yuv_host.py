@@ -49,7 +49,8 @@ def test_to_rgb01_cpu_pads_a_batch_to_one_canvas():
 
 def test_bilinear_taps_are_the_3_4_1_4_filter():
     """A chroma plane with one sample set: the separable (1/4, 3/4 | 3/4, 1/4) footprint around its 2x2 block, clamped at the edges."""
-    from lvae.utils.yuv import _upsample
+    from lvae.utils.yuv import _upsample2
+    _upsample = lambda c, chroma: _upsample2(c, 8, '420', 'center', chroma)      # the 8-bit 4:2:0 expressions' upsampling
     c = torch.zeros(3, 4, dtype=torch.uint8)
     c[1, 2] = 16
     up = _upsample(c, 'bilinear')
@@ -64,6 +65,39 @@ def test_bilinear_taps_are_the_3_4_1_4_filter():
     want[:3, :3] = 16 * w[:, None] * w[None]
     assert torch.equal(_upsample(c, 'bilinear'), want)
     assert torch.equal(_upsample(c, 'nearest')[:2, :2], torch.full((2, 2), 16.0))
+
+
+# ----------------------------------------------------------------------------------------------- the bits of the two expressions
+def _expr_digests():
+    """SHA-256 of the raw result bytes of yuv_to_rgb_expr (every colour combination, three inputs) and of the three planes of
+    rgb_to_yuv_expr (every matrix / range pair, the five images of yuv_ref.rgb_batch with NaN / +-inf replaced as the clamp does)."""
+    import hashlib
+    from lvae.utils.yuv import rgb_to_yuv_expr, yuv_to_rgb_expr
+    sha = lambda *ts: hashlib.sha256(b''.join(t.contiguous().numpy().tobytes() for t in ts)).hexdigest()
+    inputs = {'all_values': yuv_ref.all_values_planes(), 'noise_6x10': yuv_ref.noise_planes(6, 10, 1), 'noise_62x66': yuv_ref.noise_planes(62, 66, 2)}
+    out = {}
+    for name, planes in inputs.items():
+        y, u, v = (torch.from_numpy(p) for p in planes)
+        for matrix, rng, chroma in yuv_ref.COMBOS:
+            out[f'yuv_to_rgb/{name}/{matrix}/{rng}/{chroma}'] = sha(yuv_to_rgb_expr(y, u, v, matrix, rng, chroma))
+    z = torch.nan_to_num(yuv_ref.rgb_batch(), nan=0.0, posinf=1.0, neginf=0.0)
+    for matrix in ('bt601', 'bt709'):
+        for rng in ('limited', 'full'):
+            planes = [rgb_to_yuv_expr(img, matrix, rng) for img in z]
+            for k, p in enumerate('yuv'):
+                out[f'rgb_to_yuv/{matrix}/{rng}/{p}'] = sha(*[q[k] for q in planes])
+    return out
+
+
+def test_8_bit_420_expressions_keep_their_bits():
+    """tests/golden/yuv420_expr_sha256.json was written by _expr_digests when yuv_to_rgb_expr / rgb_to_yuv_expr were expressions of
+    their own, before they became the general ones at depth 8, '420', 'center': every result byte is still the same."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'yuv420_expr_sha256.json')) as f:
+        want = json.load(f)
+    assert len(want) == 3 * 8 + 4 * 3
+    assert _expr_digests() == want
 
 
 # ----------------------------------------------------------------------------------------------- from_rgb01 against the definition

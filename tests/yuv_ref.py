@@ -86,5 +86,17 @@ def noise_planes(h, w, seed):
             g.integers(0, 256, (h // 2, w // 2), dtype=np.uint8))
 
 
+def rgb_batch():
+    """(5, 3, 128, 192) fp32 torch tensor in [-0.1, 1.1] with exact 0 / 1 / out-of-range values, a NaN and infinities in every image's corner."""
+    import torch
+    g = torch.Generator().manual_seed(6)
+    x = torch.rand(5, 3, 128, 192, generator=g) * 1.2 - 0.1
+    x[:, :, 0, :6] = torch.tensor([0.0, 1.0, 2.0, -1.0, 0.5, 0.25])
+    x[:, 0, 1, 0] = float('nan')
+    x[:, 1, 1, 1] = float('inf')
+    x[:, 2, 0, 1] = float('-inf')
+    return x
+
+
 def nv12_uv(u, v):
     return np.ascontiguousarray(np.stack([u, v], -1))
