@@ -164,7 +164,16 @@ typedef struct {
                                              the Python host passes 0; tests/test_gpu_gemm_configs.py forces the others).  The two
                                              64-deep candidates (k = 11, 12) exist for prec 0 without split-K only: elsewhere they
                                              run the 32-deep tile of the same shape (k = 3, 2), and k = 8 (128 x 256) runs k = 4
-                                             (256 x 256) under prec 2.  prec 4 / 3 read their own codes here (see `prec`) */
+                                             (256 x 256) under prec 2.  prec 3 reads its own codes here (see `prec`).
+                                             prec 4 (every choice gives the same bits; tests/test_gpu_h2_instances.py forces each):
+                                             a_h2 = 0: 0 = the library chooses kernel and tile; 1 / 2 = gemm_h2_kernel with
+                                             128 x 64 / 128 x 128 tiles (TN = 1 / 2; -22 where K % 32 != 0); 3 = gemm_h2n_kernel
+                                             wherever it applies (N <= 96, one PLAIN / CONV3 source, no a_gelu / out_h2), else as 0.
+                                             a_h2 = 1 (csrc/gemm_h2p.hip, rows x columns): 42 = 256 x 128, 41 = 256 x 64,
+                                             22 = 128 x 128, 21 = 128 x 64 with three LDS stages, 23 = 128 x 64 with two; any other
+                                             value = the library's choice; ignored under ksplit > 1, where the serial form runs
+                                             128 x 64 tiles with loader waves while ceil(M/128) * ceil(N/64) <= CU count and
+                                             without them beyond */
     int  ksplit;                          /* split-K: S > 1 cuts K into S equal slices (K % (32*S) == 0) computed by S x tiles
                                              workgroups into `ws`, then reduced IN SLICE ORDER and passed through the epilogue by a
                                              second kernel -- deterministic; for the few-tile, long-K layers (stride 32/64 MLPs, 3x3
