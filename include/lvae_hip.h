@@ -526,6 +526,33 @@ int lvae_msssim_f32(const float* x, long x_img, long x_plane, long x_row, const 
 /* Bytes of scratch lvae_msssim_f32 needs for these arguments; 0 when they are not acceptable (B, C <= 0, Hmax or Wmax <= 160). */
 size_t lvae_msssim_workspace_bytes(int B, int C, int Hmax, int Wmax);
 
+/* ---- SSIM / MS-SSIM of n PLANE pairs in one call (the same kernels behind another sample loader): every pair is an image of one
+ * channel with its own size, so the Y, U and V planes of video frames -- of different sizes -- go in one call, read where they lie.
+ * x, y, x_row, y_row, hw, pixstride: HOST arrays of n entries (hw: int[n][2] = (h_k, w_k)), read before the call returns: pair k is the
+ * planes at the DEVICE addresses x[k], y[k], rows x_row[k] / y_row[k] SAMPLES apart, pixel q of a row at sample q * pixstride[k]
+ * (1, or 2 for one half of an interleaved chroma plane: the UV plane of NV12 / P010 read at the address of its first U or V sample).
+ * kind, for the whole call: LVAE_SAMPLE_F32 (floats; depth is not read), LVAE_SAMPLE_U8 (bytes; depth 8), LVAE_SAMPLE_U16_LOW (16-bit words,
+ * the code in the low bits: word & (2^depth - 1), as lvae_image_yuv_to_f32 reads them), LVAE_SAMPLE_U16_HIGH (the code in the high bits:
+ * word >> (16 - depth), the P010 family).  depth: 8, 10 or 12.
+ * data_range: L > 0 in the units of the samples (1 for floats in [0, 1], 2^depth - 1 for codes); C1 = (0.01 L)^2, C2 = (0.03 L)^2.  The
+ * samples are NOT divided by L: the arithmetic is lvae_msssim_f32's on the codes (exact as floats), fp64 moments and sums.
+ * scales: 5 = MS-SSIM as above, min(h_k, w_k) > 160; 1 = the mean of the SSIM map (Wang et al. 2004, the Gaussian window above) over
+ * the (h - 10) x (w - 10) valid pixels, min(h_k, w_k) >= 11: one scale launch and the finishing launch.
+ * out[k] (device, double): the value of pair k.  scale_means (device, double[n][scales]): as scale_means of lvae_msssim_f32; with
+ * scales = 1 it repeats out.  ws: device scratch of at least lvae_msssim_planes_workspace_bytes(n, max h_k, max w_k, scales) bytes,
+ * 8-byte aligned.  One small host-to-device copy (hw and the plane table), `scales` scale launches, 1 finishing launch; no atomics; a
+ * value depends on its own pair alone.
+ * -22 before any HIP call: a null pointer (an entry of x / y included), n <= 0, a side below the minimum, w_k * pixstride[k] beyond a
+ * row stride, a pixel stride other than 1 or 2, an unknown kind, a depth other than 8, 10, 12 (other than 8 for bytes), scales other than
+ * 1 or 5, data_range <= 0, above 65535 or not a number, ws_bytes too small.
+ * Both entries were added without a change to lvae_abi_version(). */
+enum { LVAE_SAMPLE_F32 = 0, LVAE_SAMPLE_U8 = 1, LVAE_SAMPLE_U16_LOW = 2, LVAE_SAMPLE_U16_HIGH = 3 };
+int lvae_msssim_planes(const void* const* x, const long* x_row, const void* const* y, const long* y_row, const int* hw,
+                       const int* pixstride, int n, int kind, int depth, double data_range, int scales, double* out, double* scale_means,
+                       void* ws, size_t ws_bytes, void* stream);
+/* Bytes of scratch lvae_msssim_planes needs; 0 when the arguments are not acceptable. */
+size_t lvae_msssim_planes_workspace_bytes(int n, int Hmax, int Wmax, int scales);
+
 /* ---- 8-bit images in and out of the codec (csrc/image_io.hip).  Both entries take B images whose 8-bit side is interleaved RGB
  * (HWC, 3 bytes per pixel) and whose fp32 side is NCHW planes with unit column stride, and read HOST arrays describing the 8-bit side:
  * image b at the DEVICE address u8[b], its rows u8_row[b] bytes apart (>= 3 * w_b), its valid extent hw[2b], hw[2b + 1] = (h_b, w_b) --

@@ -78,6 +78,7 @@ YUV_FORMATS, YUV_MATRICES, YUV_RANGES, YUV_CHROMA = ('i420', 'nv12'), ('bt601', 
 YUV_SUBSAMPLINGS, YUV_SITINGS, YUV_MATRICES2 = ('420', '422', '444'), ('center', 'left'), ('bt601', 'bt709', 'bt2020')   # LVAE_YUV_SUB_* / LVAE_YUV_SITING_* / the matrices of lvae_image_yuv_to_f32 / lvae_image_f32_to_yuv
 YUV_DEPTHS = (8, 10, 12)
 YUV_LAYOUTS = ('planar', 'semiplanar')                  # LVAE_YUV_LAYOUT_*
+SAMPLE_KINDS = ('f32', 'u8', 'u16_low', 'u16_high')     # LVAE_SAMPLE_*: the sample loaders of lvae_msssim_planes
 EVAL_CHUNKS = 256               # LVAE_EVAL_CHUNKS: lvae_rd_image_f32 / lvae_pixel_nll_f32 take ws = double[B][EVAL_CHUNKS][2]
 
 _vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
@@ -139,6 +140,8 @@ SIGNATURES = {
     'lvae_sqerr_partials_f32': (_i, [_vp, _vp, _vp, _i, _l, _vp]),
     'lvae_msssim_f32': (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'lvae_msssim_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'lvae_msssim_planes': (_i, [_vp] * 6 + [_i, _i, _i, _d, _i, _vp, _vp, _vp, _sz, _vp]),
+    'lvae_msssim_planes_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'lvae_image_u8_to_f32': (_i, [_vp, _vp, _vp, _i, _vp, _l, _i, _i, _vp]),
     'lvae_image_f32_to_u8': (_i, [_vp, _l, _l, _l, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'lvae_image_yuv420_to_f32': (_i, [_vp] * 7 + [_i] * 5 + [_vp, _l, _i, _i, _vp]),

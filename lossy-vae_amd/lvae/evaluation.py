@@ -216,9 +216,12 @@ def rate_map_evaluate(model, dataset, out_dir=None, lmb=None):
     return rows
 
 
+YUV_METRICS = ('psnr', 'ssim', 'ms-ssim')
+
+
 @torch.no_grad()
 def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, depth=8, subsampling='420', siting='center',
-                 layout='planar', **colour):
+                 layout='planar', metrics=('psnr',), **colour):
     """A raw 8-bit 4:2:0 file coded frame by frame (an image codec as an intra-frame coder) -> dict of means over its frames: 'bpp'
     (8 * len(blob) / (h * w)) and the keys of lvae.metrics.psnr_yuv420 ('mse-y' ... 'psnr-yuv'), computed between the file's bytes and
     decompress_yuv420's.  colour: matrix / range / chroma of compress_yuv420 (matrix and range also go to decompress_yuv420).  Every frame
@@ -228,14 +231,23 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
     subsampling (utils.yuv.read_yuv; fmt must stay 'i420'), coded by compress_yuv / decompress_yuv with that siting and measured by
     lvae.metrics.psnr_yuv, whose key 'psnr-avg' joins the result; matrix may then be 'bt2020'.  layout 'semiplanar': a P010 / P012 / P210 /
     P212 file (utils.yuv.read_yuv_sp; depth 10 | 12, subsampling '420' | '422'), coded and reconstructed in that layout and measured on its
-    codes."""
-    from .metrics import PSNR_YUV_KEYS, PSNR_YUV_KEYS2, psnr_yuv, psnr_yuv420
+    codes.
+    metrics: 'psnr' (always reported: the keys above), 'ssim' adds 'ssim-y', 'ssim-u', 'ssim-v' (lvae.metrics.ssim_yuv) and 'ms-ssim' adds
+    'ms-ssim-y' (lvae.metrics.ms_ssim_yuv on the luma plane; ValueError for frames with min(h, w) <= 160), both on the codes of the file's
+    and the reconstruction's planes where they lie on the device, with data range 2^depth - 1; one more launch sequence per batch.  The
+    other keys keep their values."""
+    from .metrics import PSNR_YUV_KEYS, PSNR_YUV_KEYS2, ms_ssim_yuv, psnr_yuv, psnr_yuv420, ssim_yuv
     from .utils.yuv import read_yuv, read_yuv420, read_yuv_sp
     if layout not in ('planar', 'semiplanar'):
         raise ValueError(f"yuv_evaluate: layout is 'planar' or 'semiplanar', got {layout!r}")
     unknown = set(colour) - {'matrix', 'range', 'chroma'}
     if unknown:
         raise TypeError(f'yuv_evaluate: unexpected arguments {sorted(unknown)}')
+    bad = [m for m in metrics if m not in YUV_METRICS]
+    if bad:
+        raise ValueError(f'unknown metrics {bad}; known: {YUV_METRICS}')
+    if 'ms-ssim' in metrics and min(height, width) <= 160:
+        raise ValueError(f'yuv_evaluate: frames of {height}x{width}; MS-SSIM needs min(h, w) > 160 (5 scales of an 11-tap window)')
     dev = next(model.parameters()).device
     dec = {k: v for k, v in colour.items() if k != 'chroma'}
     general = (depth, subsampling, siting) != (8, '420', 'center') or layout == 'semiplanar'
@@ -263,8 +275,19 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
             enc['lmb'] = lmb if isinstance(lmb, (int, float)) else list(lmb)[o:o + step]
         blobs = compress(chunk, **enc)
         recs = decompress(blobs)
-        for blob, stats in zip(blobs, measure(chunk, recs)):
-            rows.append(dict(stats, bpp=float(8 * len(blob) / float(height * width))))
+        stats = [dict(r) for r in measure(chunk, recs)]
+        if 'ssim' in metrics:
+            for r, extra in zip(stats, ssim_yuv(chunk, recs)):
+                r.update(extra)
+        if 'ms-ssim' in metrics:
+            for r, extra in zip(stats, ms_ssim_yuv(chunk, recs)):
+                r.update(extra)
+        for blob, r in zip(blobs, stats):
+            rows.append(dict(r, bpp=float(8 * len(blob) / float(height * width))))
+    if 'ssim' in metrics:
+        keys = keys + ('ssim-y', 'ssim-u', 'ssim-v')
+    if 'ms-ssim' in metrics:
+        keys = keys + ('ms-ssim-y',)
     out = {}
     for k in ('bpp',) + keys:
         acc = 0.0

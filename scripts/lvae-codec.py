@@ -15,6 +15,7 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]   # yuv420p10le ...
     python scripts/lvae-codec.py encode-yuv IN.yuv OUT.lvys --size 1920 1080 --container [--layout p010] [--siting left] [--matrix bt2020]
     python scripts/lvae-codec.py decode-yuv IN.lvys OUT.yuv [--layout p010]          # no colour flags: the container holds them
+    python scripts/lvae-codec.py eval-yuv IN.yuv --size 1920 1080 [--depth 10 | --layout p010 ...] [--ssim] [--ms-ssim]   # bpp, PSNR-YUV, SSIM as JSON
     python scripts/lvae-codec.py ratemap IMAGES/ MAPS/ -m qarv_base [--lmb 256]      # where the bits go: <stem>.npy + <stem>.png per image
 
 Images whose sizes padded to the model's stride agree are coded as batches of up to --batch (lvae.evaluation.batch_same_size).  A .bits
@@ -34,6 +35,10 @@ semi-planar with the value in the high bits (what hardware decoders deliver); th
 encode-yuv writes ONE self-describing file (CodecBase.compress_yuv_sequence, the LVYS container of lvae/utils/yuvseq.py) instead of a
 folder; decode-yuv recognises it by its magic, takes every parameter from its header and writes the source's layout unless --layout
 / --format asks for another.
+eval-yuv codes the frames of a raw file as encode-yuv would (the same --size / --format / --depth / --subsampling / --siting / --layout /
+colour flags, --frames, --batch, --lmb; --synthetic N writes seeded frames first), decodes them and prints lvae.evaluation.yuv_evaluate's
+dict of means as one JSON line: bpp and the PSNR keys, with --ssim also ssim-y / ssim-u / ssim-v, with --ms-ssim also ms-ssim-y (frames
+with min(h, w) > 160 only).  It takes no DST.
 ratemap writes, for every image of IMAGES/, the per-pixel bit allocation of the model's rate estimate (lvae.evaluation.rate_map_evaluate:
 CodecBase.rate_map on the image's bytes) as MAPS/<stem>.npy (fp32, bits per pixel at each pixel) and a grey MAPS/<stem>.png, and prints
 each image's estimated bits and the share of every latent block; nothing is entropy-coded.  --synthetic N writes seeded PNGs first, as encode."""
@@ -168,6 +173,15 @@ def decode_yuv(model, src, dst, fmt, batch, colour, layout=None, sp=False):
     print(f'decoded {len(paths)} frames')
 
 
+def eval_yuv(model, src, size, fmt, frames, lmb, batch, colour, layout=None, sp=False, metrics=('psnr',)):
+    import json
+    from lvae.evaluation import yuv_evaluate
+    res = yuv_evaluate(model, src, size[0], size[1], fmt=fmt, max_frames=frames, batch=batch, lmb=lmb, metrics=metrics,
+                       layout='semiplanar' if sp else 'planar', **(layout or {}), **colour)
+    print(json.dumps(res))
+    return res
+
+
 def synthetic_yuv(path, n, size, fmt, colour, layout=None, sp=False):
     """N seeded frames of size (w, h) as a raw .yuv file: seeded RGB images through the defining host conversion."""
     import seeded_init
@@ -193,9 +207,9 @@ def ratemap(model, src, dst, lmb):
 
 def build_parser():
     ap = argparse.ArgumentParser()
-    ap.add_argument('command', choices=['encode', 'decode', 'region', 'encode-yuv', 'decode-yuv', 'ratemap'])
+    ap.add_argument('command', choices=['encode', 'decode', 'region', 'encode-yuv', 'decode-yuv', 'eval-yuv', 'ratemap'])
     ap.add_argument('src')
-    ap.add_argument('dst')
+    ap.add_argument('dst', nargs='?', default=None, help='every command but eval-yuv')
     ap.add_argument('-m', '--model', type=str, default='qarv_base')
     ap.add_argument('--lmb', type=float, default=None, help='variable-rate models: the lambda to code at (default: the model\'s)')
     ap.add_argument('--batch', type=int, default=8)
@@ -218,6 +232,8 @@ def build_parser():
     ap.add_argument('--chroma', type=str, default='bilinear', choices=['nearest', 'bilinear'], help='encode-yuv: the chroma upsampling filter')
     ap.add_argument('--layout', type=str, default=None, choices=['p010', 'p012', 'p210', 'p212'],
                     help='encode-yuv / decode-yuv: the raw file is semi-planar with the value in the high bits; sets --depth and --subsampling')
+    ap.add_argument('--ssim', action='store_true', help='eval-yuv: also report ssim-y / ssim-u / ssim-v')
+    ap.add_argument('--ms-ssim', action='store_true', help='eval-yuv: also report ms-ssim-y')
     ap.add_argument('--container', action='store_true', help='encode-yuv: write one self-describing .lvys file to DST instead of a folder of .bits files')
     return ap
 
@@ -226,7 +242,9 @@ def build_parser():
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.command in ('encode-yuv', 'decode-yuv'):
+    if (args.dst is None) != (args.command == 'eval-yuv'):
+        ap.error('eval-yuv takes IN.yuv alone' if args.dst is not None else f'{args.command} needs SRC and DST')
+    if args.command in ('encode-yuv', 'decode-yuv', 'eval-yuv'):
         if args.command == 'decode-yuv' and _is_sequence(args.src):      # every parameter comes from the container's header
             model = load_model(args.model, args.synthetic, torch.device(args.device))
             decode_yuv_container(model, args.src, args.dst, args.batch,
@@ -244,7 +262,15 @@ def main(argv=None):
             if args.format != 'i420':
                 ap.error('--depth / --subsampling / --siting / --matrix bt2020 apply to planar files (--format i420)')
             layout = dict(depth=args.depth, subsampling=args.subsampling, siting=args.siting)
-        if args.command == 'encode-yuv':
+        if args.command == 'eval-yuv':
+            if args.size is None:
+                ap.error('eval-yuv needs --size W H')
+            if args.synthetic:
+                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour, layout, sp)
+            model = load_model(args.model, args.synthetic, torch.device(args.device))
+            eval_yuv(model, args.src, args.size, args.format, args.frames, args.lmb, args.batch, colour, layout, sp,
+                     ('psnr',) + (('ssim',) if args.ssim else ()) + (('ms-ssim',) if args.ms_ssim else ()))
+        elif args.command == 'encode-yuv':
             if args.size is None:
                 ap.error('encode-yuv needs --size W H')
             if not args.container:
