@@ -708,6 +708,25 @@ int lvae_tile_stitch(const float* const* tiles, long tile_plane, long tile_row, 
                      long dst_row, int out_u8, void* ws, size_t ws_bytes, void* stream);
 /* Bytes of scratch lvae_tile_stitch needs; 0 when rows or cols <= 0. */
 size_t lvae_tile_stitch_workspace_bytes(int rows, int cols);
+/* lvae_tile_stitch_yuv (csrc/tile_stitch_yuv.hip): the window of a tiled image as the planes of a YUV frame, with no fp32 image in between.
+ * The tile arguments, the grid rule, the window and the scratch (lvae_tile_stitch_workspace_bytes; one small copy and one launch) are
+ * lvae_tile_stitch's; depth, subsampling, siting, matrix and range are lvae_image_f32_to_yuv's.  layout LVAE_YUV_LAYOUT_PLANAR: y, u, v
+ * are the planes; LVAE_YUV_LAYOUT_SEMIPLANAR: u is the interleaved UV plane and v / v_row are not read -- at depth 8 that is NV12 (4:2:0,
+ * centre siting, BT.601 / BT.709: what lvae_image_f32_to_yuv420 has), at depth 10 / 12 P010 / P012 / P210 / P212 with the code in the high
+ * bits.  The destination is the WINDOW's frame: y holds (hh, ww) samples, the chroma planes (hh >> sy, ww >> sx) (the UV plane
+ * (hh >> sy, ww) samples); row strides in samples, which may exceed the extent; nothing outside the window's planes is written.
+ * The contract is bit equality with the composition: lvae_tile_stitch(..., out_u8 = 0) of the image into fp32 planes, then the matching
+ * lvae_image_f32_to_yuv / _yuvsp / _yuv420 entry -- blends of up to 9 covering tiles, NaN -> 0 and ties to even included -- and a window is
+ * the crop of the whole frame.  So with left-sited chroma the column before a window with x0 > 0 is column x0 - 1 OF THE IMAGE, blended
+ * like any other pixel (not a copy of column x0), and the tiles that hold it must have been decoded.
+ * -22 before any HIP call: whatever lvae_tile_stitch refuses; a null plane; y0 or hh odd at 4:2:0, x0 or ww odd at 4:2:0 / 4:2:2; an unknown
+ * depth / subsampling / siting / matrix / range / layout, or a semi-planar layout the entries named above do not have; row strides that do
+ * not hold the window; a null entry of `tiles` for a tile that meets the window widened, where left-sited and x0 > 0, by column x0 - 1.
+ * Added without a change to lvae_abi_version(); it has no launch-plan kind. */
+int lvae_tile_stitch_yuv(const float* const* tiles, long tile_plane, long tile_row, const int* oy, const int* ox, int rows, int cols, int th,
+                         int tw, int overlap, int h, int w, int y0, int x0, int hh, int ww, int depth, int subsampling, int siting, int matrix,
+                         int range, int layout, void* y, void* u, void* v, long y_row, long u_row, long v_row, void* ws, size_t ws_bytes,
+                         void* stream);
 
 /* ---- Reduced-resolution coding: a separable, antialiased resampler (csrc/resample.hip; lvae/utils/resample.py states the window rule,
  * the filters and the tables, and holds the fp64 reference).  All B images of a call share the geometry (h_in, w_in) -> (h_out, w_out)

@@ -154,6 +154,7 @@ SIGNATURES = {
     'lvae_sse_u16': (_i, [_vp] * 5 + [_i, _vp, _vp]),
     'lvae_tile_stitch': (_i, [_vp, _l, _l, _vp, _vp] + [_i] * 11 + [_vp, _l, _l, _i, _vp, _sz, _vp]),
     'lvae_tile_stitch_workspace_bytes': (_sz, [_i, _i]),
+    'lvae_tile_stitch_yuv': (_i, [_vp, _l, _l, _vp, _vp] + [_i] * 17 + [_vp, _vp, _vp, _l, _l, _l, _vp, _sz, _vp]),
     'lvae_resample_u8_to_f32': (_i, [_vp, _vp] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp, _l, _i, _i, _vp]),
     'lvae_resample_f32_to_u8': (_i, [_vp, _l, _l, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp, _vp, _vp]),
     'lvae_resample_f32': (_i, [_vp, _l, _l, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_i, _vp, _l, _i, _i, _vp]),

@@ -221,7 +221,7 @@ YUV_METRICS = ('psnr', 'ssim', 'ms-ssim')
 
 @torch.no_grad()
 def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, depth=8, subsampling='420', siting='center',
-                 layout='planar', metrics=('psnr',), **colour):
+                 layout='planar', metrics=('psnr',), tile=None, overlap=0, **colour):
     """A raw 8-bit 4:2:0 file coded frame by frame (an image codec as an intra-frame coder) -> dict of means over its frames: 'bpp'
     (8 * len(blob) / (h * w)) and the keys of lvae.metrics.psnr_yuv420 ('mse-y' ... 'psnr-yuv'), computed between the file's bytes and
     decompress_yuv420's.  colour: matrix / range / chroma of compress_yuv420 (matrix and range also go to decompress_yuv420).  Every frame
@@ -235,7 +235,9 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
     metrics: 'psnr' (always reported: the keys above), 'ssim' adds 'ssim-y', 'ssim-u', 'ssim-v' (lvae.metrics.ssim_yuv) and 'ms-ssim' adds
     'ms-ssim-y' (lvae.metrics.ms_ssim_yuv on the luma plane; ValueError for frames with min(h, w) <= 160), both on the codes of the file's
     and the reconstruction's planes where they lie on the device, with data range 2^depth - 1; one more launch sequence per batch.  The
-    other keys keep their values."""
+    other keys keep their values.
+    tile = (th, tw), overlap: every frame is coded in tiles (compress_yuv_tiled / decompress_yuv_tiled, `batch` tiles at a time); 'bpp'
+    then counts the whole tiled container.  Only 'psnr' is measured on frames coded in tiles."""
     from .metrics import PSNR_YUV_KEYS, PSNR_YUV_KEYS2, ms_ssim_yuv, psnr_yuv, psnr_yuv420, ssim_yuv
     from .utils.yuv import read_yuv, read_yuv420, read_yuv_sp
     if layout not in ('planar', 'semiplanar'):
@@ -266,6 +268,16 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
         compress = model.compress_yuv420
         decompress = lambda blobs: model.decompress_yuv420(blobs, fmt=fmt, **dec)
         measure, keys = psnr_yuv420, PSNR_YUV_KEYS
+    if tile is not None:
+        if set(metrics) - {'psnr'}:
+            raise ValueError(f"yuv_evaluate: frames coded in tiles are measured by 'psnr' only, got metrics={tuple(metrics)}")
+        sit = {'siting': siting} if general else {}
+        tiled_out = dict(depth=depth, subsampling=subsampling, siting=siting, layout=layout) if general else dict(layout=fmt)
+
+        def compress(chunk, lmb=None, **enc):
+            per = lmb if isinstance(lmb, list) else [lmb] * len(chunk)
+            return [model.compress_yuv_tiled(f, tile=tile, overlap=overlap, lmb=v, max_batch=batch, **sit, **enc) for f, v in zip(chunk, per)]
+        decompress = lambda blobs: [model.decompress_yuv_tiled(b, max_batch=batch, **tiled_out, **dec) for b in blobs]
     frames = [f.to(dev, non_blocking=True) for f in frames]
     rows, step = [], max(1, int(batch))
     for o in range(0, len(frames), step):

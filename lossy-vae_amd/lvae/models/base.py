@@ -694,14 +694,17 @@ class CodecBase(nn.Module):
 
     @torch.no_grad()
     def compress_yuv_sequence(self, frames_or_path, width=None, height=None, depth=8, subsampling='420', layout='planar', siting='center',
-                              matrix='bt709', range='limited', chroma='bilinear', frames=None, lmb=None, max_batch=8):
+                              matrix='bt709', range='limited', chroma='bilinear', frames=None, lmb=None, max_batch=8, tile=None, overlap=0):
         """A sequence of frames -> the bytes of one self-describing container (utils.yuvseq.pack_sequence).  frames_or_path: a list of
         frames of ONE kind and size -- utils.yuv.YuvFrame, YuvSpFrame or Yuv420Frame; depth, subsampling and layout are then the frames' --
         or the path of a raw file of `width` x `height` frames of `depth`, `subsampling` and `layout` ('planar' | 'semiplanar' | 'i420' |
         'nv12'), of which `max_batch` at a time are read, uploaded and coded (all of them, or the first `frames`).  Frame k's blob is
         compress_yuv([frame k], ...)[0] (compress_yuv420 for 'i420' / 'nv12'), whatever max_batch: batch rows are bit-equal to single calls.
         lmb: None, one value or -- variable-rate models -- one value per frame.  The header records size, depth, subsampling, siting,
-        matrix, range, chroma, the layout, this model's registry name and its GEMM precision: decompress_yuv_sequence needs nothing else."""
+        matrix, range, chroma, the layout, this model's registry name and its GEMM precision: decompress_yuv_sequence needs nothing else.
+        tile = (th, tw), overlap: every frame is coded in tiles and its entry is compress_yuv_tiled(frame k, tile, overlap, ...), a tiled
+        container (the tiles of ONE frame then share a batch, `max_batch` at a time); the header does not change -- a frame's entry is
+        opaque bytes behind the length table -- and with tile=None every byte is as before."""
         from ..utils import yuv, yuvseq
         if lmb is not None and not self.variable_rate:
             raise ValueError(f'{type(self).__name__} is a fixed-rate model: it takes no lmb')
@@ -743,6 +746,13 @@ class CodecBase(nn.Module):
             compress = lambda chunk, **kw: self.compress_yuv420(chunk, matrix=matrix, range=range, chroma=chroma, **kw)
         else:
             compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
+        if tile is not None:
+            self._tile_args(tile, overlap)
+
+            def compress(chunk, lmb=None):
+                per = lmb if isinstance(lmb, list) else [lmb] * len(chunk)
+                return [self.compress_yuv_tiled(f, tile=tile, overlap=overlap, lmb=v, max_batch=max_batch, matrix=matrix, range=range,
+                                                chroma=chroma, siting=siting) for f, v in zip(chunk, per)]
         blobs = yuvseq.code_sequence(compress, source, max_batch, lmb)
         meta = dict(width=width, height=height, depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range, chroma=chroma,
                     layout=layout, model=self._registry_name, gemm=self._prec)
@@ -750,10 +760,11 @@ class CodecBase(nn.Module):
 
     def yuv_sequence_info(self, blob):
         """utils.yuvseq.yuv_sequence_info (header parsing only, no GPU) plus 'lmb': the frames' lambdas from their blobs' own headers on
-        variable-rate models (as tiled_info), else None."""
-        from ..utils import yuvseq
+        variable-rate models (as tiled_info), else None; a frame that was coded in tiles has tiled_info's (rows, cols) nested list."""
+        from ..utils import tiling, yuvseq
         info = yuvseq.yuv_sequence_info(blob)
-        info['lmb'] = [self._blob_lmb(yuvseq.frame_blob(blob, info, k)) for k in range(info['frames'])] if self.variable_rate else None
+        lmb_of = lambda fb: self.tiled_info(fb)['lmb'] if tiling.is_tiled(fb) else self._blob_lmb(fb)
+        info['lmb'] = [lmb_of(yuvseq.frame_blob(blob, info, k)) for k in range(info['frames'])] if self.variable_rate else None
         return info
 
     @torch.no_grad()
@@ -764,8 +775,9 @@ class CodecBase(nn.Module):
         for 8-bit 4:2:0 centre-sited sequences, 'i420' / 'nv12' (Yuv420Frame).  out_path: write the frames to that raw file instead and
         return their number.  ValueError: a malformed container (utils.yuvseq.yuv_sequence_info), a header whose model name or GEMM
         precision is not this model's (both names are in the message; set_gemm_precision selects the arithmetic), a layout the header's
-        parameters do not have."""
-        from ..utils import yuv, yuvseq
+        parameters do not have.  A frame entry that is a tiled container (compress_yuv_sequence(tile=...)) is recognised by its magic and
+        decoded by decompress_yuv_tiled."""
+        from ..utils import tiling, yuv, yuvseq
         info = yuvseq.yuv_sequence_info(blob)
         if info['model'] != self._registry_name:
             raise ValueError(f"decompress_yuv_sequence: the sequence was written by model {info['model']!r}, this model is {self._registry_name!r}")
@@ -780,9 +792,14 @@ class CodecBase(nn.Module):
         else:
             decode = lambda bl: self.decompress_yuv(bl, depth=depth, subsampling=sub, siting=siting, matrix=matrix, range=rng, layout=layout)
             write = yuv.write_yuv_sp if layout == 'semiplanar' else yuv.write_yuv
+        decode_tiled = lambda b: self.decompress_yuv_tiled(b, depth=depth, subsampling=sub, siting=siting, matrix=matrix, range=rng, layout=layout,
+                                                           max_batch=max_batch)
         idxs, step, out = yuvseq.frame_indexes(info, frames), max(1, int(max_batch)), []
         for o in range(0, len(idxs), step):
-            got = decode([yuvseq.frame_blob(blob, info, k) for k in idxs[o:o + step]])
+            entries = [yuvseq.frame_blob(blob, info, k) for k in idxs[o:o + step]]
+            whole = [b for b in entries if not tiling.is_tiled(b)]
+            got = iter(decode(whole) if whole else [])
+            got = [decode_tiled(b) if tiling.is_tiled(b) else next(got) for b in entries]       # a frame coded in tiles: a tiled container
             for f in got:
                 if f.size != (info['height'], info['width']):
                     raise ValueError(f"YUV sequence container: a frame holds {f.size[1]} x {f.size[0]} pixels, the header says {info['width']} x {info['height']}")
@@ -936,22 +953,26 @@ class CodecBase(nn.Module):
         img = _as_u8(image).to(self._dummy.device, non_blocking=True)
         h, w = int(img.shape[0]), int(img.shape[1])
         ys, xs = tiling.tile_grid(h, w, th, tw, overlap)
-        n = len(ys) * len(xs)
+        views = [img[y:y + th, x:x + tw] for y in ys for x in xs]
+        return tiling.pack_tiled(h, w, th, tw, overlap, self._code_tiles(self.compress_images, views, len(ys), len(xs), lmb, max_batch))
+
+    def _code_tiles(self, compress, views, rows, cols, lmb, max_batch):
+        """The tiles of a rows x cols grid (row-major `views`) -> their blobs, `max_batch` at a time through compress(chunk, lmb=...).
+        lmb: None, a number or a (rows, cols) array."""
         lmbs = None
         if lmb is not None and not isinstance(lmb, (int, float)):
             lmbs = np.asarray(lmb.detach().cpu() if isinstance(lmb, torch.Tensor) else lmb, dtype=np.float64)
             if lmbs.ndim == 0:
                 lmb, lmbs = float(lmbs), None
-            elif lmbs.shape != (len(ys), len(xs)):
-                raise ValueError(f'lmb map of shape {lmbs.shape} for a {len(ys)} x {len(xs)} tile grid')
+            elif lmbs.shape != (rows, cols):
+                raise ValueError(f'lmb map of shape {lmbs.shape} for a {rows} x {cols} tile grid')
             else:
                 lmbs = lmbs.reshape(-1).tolist()
-        views = [img[y:y + th, x:x + tw] for y in ys for x in xs]
         blobs, step = [], max(1, int(max_batch))
-        for o in range(0, n, step):
+        for o in range(0, len(views), step):
             kw = {} if lmb is None else {'lmb': lmbs[o:o + step] if lmbs is not None else lmb}
-            blobs += self.compress_images(views[o:o + step], **kw)
-        return tiling.pack_tiled(h, w, th, tw, overlap, blobs)
+            blobs += compress(views[o:o + step], **kw)
+        return blobs
 
     def tiled_info(self, blob):
         """Header parsing only (no GPU): dict(h, w, tile, overlap, rows, cols, ys, xs, lengths, lmb) of a tiled container; lmb: the
@@ -966,11 +987,11 @@ class CodecBase(nn.Module):
                     lengths=c['lengths'], lmb=lm)
 
     @torch.no_grad()
-    def _decode_tiled(self, blob, box, out, max_batch):
+    def _decode_tiles(self, blob, box, max_batch, before=0):
+        """The tile loop of every tiled decode: the tiles of a container that meet box = (y0, x0, hh, ww) (None: the image; `before`: the
+        box widened by that many columns on the left, for this purpose only), decoded `max_batch` at a time -> (the arguments of
+        stitch_tiles / stitch_tiles_yuv up to the box: tiles with None for those not decoded, h, w, th, tw, overlap; the box as ints)."""
         from ..utils import tiling
-        from ..utils.image import stitch_tiles
-        if out not in ('u8', 'f32'):
-            raise ValueError(f"out is 'u8' or 'f32', got {out!r}")
         c = tiling.unpack_tiled(blob)
         h, w, th, tw = c['h'], c['w'], c['th'], c['tw']
         self._tile_args((th, tw), c['overlap'])
@@ -981,8 +1002,9 @@ class CodecBase(nn.Module):
             raise ValueError(f'box {(y0, x0, hh, ww)} is not inside the {h} x {w} image')
         d = self.max_stride
         eth, etw = min(th, d * math.ceil(h / d)), min(tw, d * math.ceil(w / d))      # what a tile's reconstruction holds
-        need = tiling.tiles_in_box(c['ys'], c['xs'], th, tw, (y0, x0, hh, ww))
-        tiles, keep, step = [None] * len(c['tiles']), [], max(1, int(max_batch))
+        xl = max(x0 - before, 0)
+        need = tiling.tiles_in_box(c['ys'], c['xs'], th, tw, (y0, xl, hh, x0 + ww - xl))
+        tiles, step = [None] * len(c['tiles']), max(1, int(max_batch))
         for o in range(0, len(need), step):
             idxs = need[o:o + step]
             parsed = [self._unpack_blob(c['tiles'][k]) for k in idxs]
@@ -992,10 +1014,16 @@ class CodecBase(nn.Module):
             x = self.decompress_batch([p[0] for p in parsed])
             if tuple(x.shape[1:]) != (3, eth, etw):
                 raise ValueError(f'tiled container: tiles decode to {tuple(x.shape[2:])}, the header says {(eth, etw)}')
-            keep.append(x)
             for i, k in enumerate(idxs):
                 tiles[k] = x[i]
-        return stitch_tiles(tiles, h, w, eth, etw, c['overlap'], box=(y0, x0, hh, ww), out=out)
+        return (tiles, h, w, eth, etw, c['overlap']), (y0, x0, hh, ww)
+
+    def _decode_tiled(self, blob, box, out, max_batch):
+        from ..utils.image import stitch_tiles
+        if out not in ('u8', 'f32'):
+            raise ValueError(f"out is 'u8' or 'f32', got {out!r}")
+        args, box = self._decode_tiles(blob, box, max_batch)
+        return stitch_tiles(*args, box=box, out=out)
 
     def decompress_tiled(self, blob, out='u8', max_batch=8):
         """compress_tiled bytes -> the (h, w, 3) uint8 image on the model's device, or (out='f32') the (1, 3, h, w) fp32 one: tiles decoded
@@ -1006,6 +1034,76 @@ class CodecBase(nn.Module):
         """box = (y0, x0, hh, ww) of a tiled image: only the tiles that intersect the box are decoded and only the window is stitched;
         equal to decompress_tiled(blob)[y0:y0 + hh, x0:x0 + ww]."""
         return self._decode_tiled(blob, box, out, max_batch)
+
+    # ---- tiled coding of YUV frames: the tiles are views of the frame's planes on the way in (the YUV kernels read any row stride), and
+    # the blend of the decoded tiles writes YUV planes on the way out (csrc/tile_stitch_yuv.hip).  The container is compress_tiled's.
+    @torch.no_grad()
+    def compress_yuv_tiled(self, frame, tile=(512, 768), overlap=0, lmb=None, max_batch=8, matrix='bt709', range='limited', chroma='bilinear',
+                           siting='center'):
+        """One utils.yuv.YuvFrame, YuvSpFrame or Yuv420Frame -> the bytes of a tiled container (utils.tiling.pack_tiled, as compress_tiled).
+        The frame is uploaded once; its tiles (utils.tiling.tile_grid) are frames whose planes are views of its planes, coded `max_batch`
+        at a time through compress_yuv (compress_yuv420 for a Yuv420Frame), so tile k's blob is compress_yuv([that crop as a frame])[0].
+        tile, lmb, max_batch: as in compress_tiled.  overlap: even where the chroma is subsampled (both axes at '420', the width at
+        '422'), so that every tile starts on the chroma grid -- ValueError otherwise.  matrix .. siting: as in compress_yuv; a Yuv420Frame
+        takes siting='center' only.  Neither the colour parameters nor depth, subsampling and siting are stored."""
+        from ..utils import tiling, yuv
+        th, tw, overlap = self._tile_args(tile, overlap)
+        if lmb is not None and not self.variable_rate:
+            raise ValueError(f'{type(self).__name__} is a fixed-rate model: it takes no lmb')
+        if not isinstance(frame, (yuv.YuvFrame, yuv.YuvSpFrame, yuv.Yuv420Frame)):
+            raise ValueError(f'compress_yuv_tiled: expected one frame of utils.yuv, got {type(frame).__name__}')
+        is420 = isinstance(frame, yuv.Yuv420Frame)
+        if is420 and siting != 'center':
+            raise ValueError(f"compress_yuv_tiled: a Yuv420Frame has centre-sited chroma, got siting={siting!r}")
+        sx, sy = yuv.SHIFTS['420' if is420 else frame.subsampling]
+        if overlap % 2 and sx:
+            raise ValueError(f"compress_yuv_tiled: overlap {overlap} is odd: tiles of a {'420' if is420 else frame.subsampling} frame start on "
+                             'the chroma grid, so the overlap is even')
+        h, w = frame.size
+        ys, xs = tiling.tile_grid(h, w, th, tw, overlap)
+        fr = frame.to(self._dummy.device, non_blocking=True)
+        lum = lambda p, y, x: p[y:y + th, x:x + tw]
+        chr_ = lambda p, y, x: p[y >> sy:(y + th) >> sy, x >> sx:(x + tw) >> sx]
+        if is420 and fr.fmt == 'nv12':
+            crop = lambda y, x: yuv.Yuv420Frame('nv12', lum(fr.y, y, x), uv=chr_(fr.uv, y, x))
+        elif is420:
+            crop = lambda y, x: yuv.Yuv420Frame('i420', lum(fr.y, y, x), chr_(fr.u, y, x), chr_(fr.v, y, x))
+        elif isinstance(fr, yuv.YuvSpFrame):                 # a UV row holds w samples: chroma pixel x / 2 starts at sample x
+            crop = lambda y, x: yuv.YuvSpFrame(lum(fr.y, y, x), fr.uv[y >> sy:(y + th) >> sy, x:x + tw], fr.depth, fr.subsampling)
+        else:
+            crop = lambda y, x: yuv.YuvFrame(lum(fr.y, y, x), chr_(fr.u, y, x), chr_(fr.v, y, x), fr.depth, fr.subsampling)
+        if is420:
+            compress = lambda chunk, **kw: self.compress_yuv420(chunk, matrix=matrix, range=range, chroma=chroma, **kw)
+        else:
+            compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
+        views = [crop(y, x) for y in ys for x in xs]
+        return tiling.pack_tiled(h, w, th, tw, overlap, self._code_tiles(compress, views, len(ys), len(xs), lmb, max_batch))
+
+    def _decode_yuv_tiled(self, blob, box, depth, subsampling, siting, matrix, range, layout, max_batch):
+        from ..utils import tiling, yuv
+        who = 'decompress_yuv_tiled' if box is None else 'decompress_yuv_region'
+        yuv._yuv_layout(layout, depth, subsampling, siting, matrix, range, who)
+        c = tiling.unpack_tiled(blob)
+        if not yuv._extent_ok(c['h'], c['w'], subsampling):
+            raise ValueError(f"{who}: the container holds a {c['h']} x {c['w']} image, which does not fit subsampling {subsampling}")
+        if box is not None:
+            yuv.check_chroma_box(tuple(int(v) for v in box), subsampling, who)
+        args, box = self._decode_tiles(blob, box, max_batch, before=1 if siting == 'left' and yuv.SHIFTS[subsampling][0] else 0)
+        return yuv.stitch_tiles_yuv(*args, box=box, depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range, layout=layout)
+
+    def decompress_yuv_tiled(self, blob, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar', max_batch=8):
+        """compress_yuv_tiled (or compress_tiled) bytes -> the frame on the model's device: tiles decoded `max_batch` at a time with
+        decompress_batch, then blended, converted and written as YUV planes by one kernel (utils.yuv.stitch_tiles_yuv) -- the bits of
+        utils.yuv.from_rgb01_any on decompress_tiled(blob, out='f32'), without that image.  depth .. range: as in decompress_yuv, the
+        container does not record them; layout: 'planar' (YuvFrame), 'semiplanar' (YuvSpFrame), 'i420' / 'nv12' (Yuv420Frame)."""
+        return self._decode_yuv_tiled(blob, None, depth, subsampling, siting, matrix, range, layout, max_batch)
+
+    def decompress_yuv_region(self, blob, box, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar',
+                              max_batch=8):
+        """box = (y0, x0, hh, ww) of a tiled frame, on the chroma grid (ValueError otherwise): only the tiles the box touches are decoded
+        -- with siting='left' and x0 > 0 also those that hold column x0 - 1, which the first chroma column reads -- and only the window
+        is written; equal, plane by plane, to the crop of decompress_yuv_tiled's frame."""
+        return self._decode_yuv_tiled(blob, box, depth, subsampling, siting, matrix, range, layout, max_batch)
 
     def compress_file_tiled(self, img_path, out_path, tile=(512, 768), overlap=0, lmb=None, max_batch=8):
         blob = self.compress_tiled(img_path, tile=tile, overlap=overlap, lmb=lmb, max_batch=max_batch)

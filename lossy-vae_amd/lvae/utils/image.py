@@ -284,6 +284,28 @@ def resize(x, size, filter='lanczos3', clamp=False, out='f32', device=None):
     return _resample_f32([x01[i] for i in range(x01.shape[0])], (h, w), filter, clamp, out)
 
 
+def _stitch_args(tiles, h, w, th, tw, overlap, box, who):
+    """The tile side of a stitch call, checked: -> (ys, xs, box as ints, the first decoded tile, and the host arrays of the native entries:
+    tile addresses, row origins, column origins)."""
+    from .tiling import axis_origins
+    if min(h, w, th, tw) <= 0 or overlap < 0 or (h > th and overlap > th // 2) or (w > tw and overlap > tw // 2):
+        raise ValueError(f'{who}: image {(h, w)}, tiles {(th, tw)}, overlap {overlap}')
+    ys, xs = axis_origins(h, th, overlap), axis_origins(w, tw, overlap)
+    if len(tiles) != len(ys) * len(xs):
+        raise ValueError(f'{who}: {len(tiles)} tiles for a {len(ys)} x {len(xs)} grid')
+    box = (0, 0, h, w) if box is None else tuple(int(v) for v in box)
+    have = [t for t in tiles if t is not None]
+    if not have:
+        raise ValueError(f'{who}: no decoded tile')
+    t0 = have[0]
+    for t in have:
+        if (t.dtype != torch.float32 or t.device != t0.device or t.dim() != 3 or t.shape[0] != 3 or t.stride(2) != 1
+                or t.stride()[:2] != t0.stride()[:2]):
+            raise ValueError(f'{who}: tiles are (3, th, tw) fp32 tensors on one device with unit column stride and common strides')
+    addr = (ctypes.c_void_p * len(tiles))(*[None if t is None else t.data_ptr() for t in tiles])
+    return ys, xs, box, t0, addr, (ctypes.c_int * len(ys))(*ys), (ctypes.c_int * len(xs))(*xs)
+
+
 def stitch_tiles(tiles, h, w, th, tw, overlap, box=None, out='u8', strides=None):
     """A window of an (h, w) image from the fp32 reconstructions of its tiles (grid and weights: lvae/utils/tiling.py), on the GPU
     (lvae_tile_stitch: one small copy and one launch on the current stream).  tiles: row-major list with one entry per tile of
@@ -293,28 +315,11 @@ def stitch_tiles(tiles, h, w, th, tw, overlap, box=None, out='u8', strides=None)
     (out='u8': rint(clamp(v, 0, 1) * 255), ties to even) or (1, 3, hh, ww) fp32 (out='f32').  (th, tw) is the extent the tiles' buffers
     hold: for an image smaller than a tile along an axis, its padded size there."""
     from .. import _native
-    from .tiling import axis_origins
     if out not in ('u8', 'f32'):
         raise ValueError(f"stitch_tiles: out is 'u8' or 'f32', got {out!r}")
-    if min(h, w, th, tw) <= 0 or overlap < 0 or (h > th and overlap > th // 2) or (w > tw and overlap > tw // 2):
-        raise ValueError(f'stitch_tiles: image {(h, w)}, tiles {(th, tw)}, overlap {overlap}')
-    ys, xs = axis_origins(h, th, overlap), axis_origins(w, tw, overlap)
-    if len(tiles) != len(ys) * len(xs):
-        raise ValueError(f'stitch_tiles: {len(tiles)} tiles for a {len(ys)} x {len(xs)} grid')
-    y0, x0, hh, ww = (0, 0, h, w) if box is None else (int(v) for v in box)
-    have = [t for t in tiles if t is not None]
-    if not have:
-        raise ValueError('stitch_tiles: no decoded tile')
-    t0 = have[0]
+    ys, xs, (y0, x0, hh, ww), t0, addr, oy, ox = _stitch_args(tiles, h, w, th, tw, overlap, box, 'stitch_tiles')
     device = t0.device
-    for t in have:
-        if (t.dtype != torch.float32 or t.device != device or t.dim() != 3 or t.shape[0] != 3 or t.stride(2) != 1
-                or t.stride()[:2] != t0.stride()[:2]):
-            raise ValueError('stitch_tiles: tiles are (3, th, tw) fp32 tensors on one device with unit column stride and common strides')
     lib = _native.lib()
-    n = len(tiles)
-    addr = (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in tiles])
-    oy, ox = (ctypes.c_int * len(ys))(*ys), (ctypes.c_int * len(xs))(*xs)
     with torch.cuda.device(device):
         if out == 'u8':
             dst = torch.empty(hh, ww, 3, dtype=torch.uint8, device=device)

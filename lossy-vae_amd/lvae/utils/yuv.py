@@ -20,6 +20,9 @@ conversion IS the planar one -- the SP variants of csrc/yuv_io.hip give the bits
 planes -- so yuv_to_rgb_expr2 / rgb_to_yuv_expr2 define it too.  Not supported: 16-bit depth (P016), chroma sitings other than centre / left,
 8-bit semi-planar 4:2:2 / 4:4:4 (NV16 / NV24).  The colour parameters, the depth and the siting are the caller's on both sides: no stream
 stores them; the sequence container of utils/yuvseq.py does.
+
+`stitch_tiles_yuv` (the end of the file) writes a frame, or a window of one, straight from the decoded tiles of a tiled image
+(csrc/tile_stitch_yuv.hip): utils.image.stitch_tiles and from_rgb01_any as one kernel, with their bits.
 """
 import ctypes
 import os
@@ -677,3 +680,90 @@ def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', m
     outs = [YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling) for h, w in hw]
     return _from_rgb(xs, outs, YuvBatch.names, 'image_f32_to_yuv', codes)
 
+
+
+# ----------------------------------------------------------------------------------------------- tiled images straight into YUV planes
+def _yuv_layout(layout, depth, subsampling, siting, matrix, range, who):
+    """The frame kind of a `layout` name, checked against the other parameters -> (semi-planar?, Yuv420Frame fmt or None)."""
+    _check2(depth, subsampling, siting, matrix, range)
+    if layout in FORMATS:                                    # 'i420' / 'nv12': the 8-bit 4:2:0 API and its frame class
+        if (depth, subsampling, siting) != (8, '420', 'center') or matrix not in MATRICES:
+            raise ValueError(f"{who}: layout {layout!r} is 8 bits at '420' with 'center' siting and matrix in {MATRICES}, got {depth} bits at "
+                             f'{subsampling!r}, {siting!r}, {matrix!r}')
+        return layout == 'nv12', layout
+    if layout not in LAYOUTS:
+        raise ValueError(f'{who}: layout is one of {LAYOUTS + FORMATS}, got {layout!r}')
+    if layout == 'semiplanar' and (depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS):
+        raise ValueError(f'{who}: semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth} bits at {subsampling}')
+    return layout == 'semiplanar', None
+
+
+def check_chroma_box(box, subsampling, who):
+    """ValueError unless box = (y0, x0, hh, ww) starts and ends on the chroma grid of `subsampling`: its frame then has whole chroma
+    samples, and they are the full frame's."""
+    y0, x0, hh, ww = box
+    sx, sy = SHIFTS[subsampling]
+    if (sy and (y0 % 2 or hh % 2)) or (sx and (x0 % 2 or ww % 2)):
+        raise ValueError(f'{who}: box {tuple(box)} is off the chroma grid of {subsampling}: '
+                         f"{'rows and columns' if sy else 'columns'} must start and end on even numbers")
+
+
+def new_frame(h, w, device, depth=8, subsampling='420', layout='planar'):
+    """An uninitialised frame of the kind `layout` names ('planar' YuvFrame, 'semiplanar' YuvSpFrame, 'i420' / 'nv12' Yuv420Frame)."""
+    sx, sy = SHIFTS[subsampling]
+    new = lambda *s: torch.empty(*s, dtype=torch.uint8 if depth == 8 else torch.int16, device=device)
+    if layout == 'i420':
+        return Yuv420Frame('i420', new(h, w), new(h // 2, w // 2), new(h // 2, w // 2))
+    if layout == 'nv12':
+        return Yuv420Frame('nv12', new(h, w), uv=new(h // 2, w // 2, 2))
+    if layout == 'semiplanar':
+        return YuvSpFrame(new(h, w), new(h >> sy, w), depth, subsampling)
+    return YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling)
+
+
+def stitch_tiles_yuv(tiles, h, w, th, tw, overlap, box=None, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited',
+                     layout='planar', out=None):
+    """utils.image.stitch_tiles followed by from_rgb01_any, as ONE kernel (lvae_tile_stitch_yuv: one small copy and one launch on the
+    current stream) and with the same bits: a window of a tiled (h, w) image as a frame of the window's size on the tiles' device, with no
+    fp32 image in between.  tiles, h, w, th, tw, overlap, box: as in stitch_tiles.  depth .. range: as in from_rgb01_any.  layout: 'planar'
+    (-> YuvFrame), 'semiplanar' (-> YuvSpFrame: 10 | 12 bits at '420' | '422'), 'i420' / 'nv12' (-> Yuv420Frame: 8 bits, '420', 'center',
+    'bt601' | 'bt709').  A window is the crop of the whole frame: with siting='left' and x0 > 0 its first chroma column reads column x0 - 1
+    of the IMAGE, so the tiles holding that column must be there too.  out: a frame of that kind and size on the tiles' device to write
+    instead of a new one; its planes may be views of larger tensors (unit column stride), and nothing outside them is written.
+    ValueError: what stitch_tiles raises; a box off the chroma grid (odd y0 / hh at '420', odd x0 / ww at '420' / '422'); a layout the
+    depth, subsampling, siting or matrix does not have; a tile that is None but meets the box (widened by column x0 - 1 as above)."""
+    from .. import _native
+    from .image import _stitch_args
+    from .tiling import tiles_in_box
+    who = 'stitch_tiles_yuv'
+    sp, fmt = _yuv_layout(layout, depth, subsampling, siting, matrix, range, who)
+    box = (0, 0, int(h), int(w)) if box is None else tuple(int(v) for v in box)
+    check_chroma_box(box, subsampling, who)
+    ys, xs, (y0, x0, hh, ww), t0, addr, oy, ox = _stitch_args(tiles, h, w, th, tw, overlap, box, who)
+    if y0 < 0 or x0 < 0 or hh <= 0 or ww <= 0 or y0 + hh > h or x0 + ww > w:
+        raise ValueError(f'{who}: box {box} is not inside the {h} x {w} image')
+    xl = x0 - 1 if siting == 'left' and SHIFTS[subsampling][0] and x0 > 0 else x0
+    missing = [k for k in tiles_in_box(ys, xs, th, tw, (y0, xl, hh, x0 + ww - xl)) if tiles[k] is None]
+    if missing:
+        raise ValueError(f'{who}: tiles {missing} were not decoded but meet the box {box}' + (' widened by the column before it' if xl < x0 else ''))
+    device = t0.device
+    kind = Yuv420Frame if fmt else YuvSpFrame if sp else YuvFrame
+    if out is None:
+        out = new_frame(hh, ww, device, depth, subsampling, layout)
+    elif (type(out) is not kind or out.size != (hh, ww) or out.device != device or (fmt and out.fmt != fmt)
+          or (not fmt and (out.depth, out.subsampling) != (depth, subsampling))):
+        raise ValueError(f'{who}: out is a {kind.__name__} of {hh} x {ww} on {device} with the layout, depth and subsampling asked for')
+    y, u, v = out.y, (out.uv if sp else out.u), (None if sp else out.v)
+    for p in (y, u, v):
+        if p is not None and (p.stride(-1) != 1 or (p.dim() == 3 and p.stride(1) != 2)):
+            raise ValueError(f'{who}: the planes of out have unit column stride')
+    lib = _native.lib()
+    with torch.cuda.device(device):
+        nbytes = lib.lvae_tile_stitch_workspace_bytes(len(ys), len(xs))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+        _native.check(lib.lvae_tile_stitch_yuv(addr, t0.stride(0), t0.stride(1), oy, ox, len(ys), len(xs), th, tw, overlap, h, w, y0, x0, hh, ww,
+                                               depth, SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix),
+                                               RANGES.index(range), LAYOUTS.index('semiplanar' if sp else 'planar'), y.data_ptr(), u.data_ptr(),
+                                               None if sp else v.data_ptr(), y.stride(0), u.stride(0), 0 if sp else v.stride(0), ws.data_ptr(),
+                                               nbytes, _stream(device)), 'tile_stitch_yuv')
+    return out

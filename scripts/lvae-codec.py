@@ -15,6 +15,7 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv --depth 10 [--subsampling 422] [--siting left] [--matrix bt2020]   # yuv420p10le ...
     python scripts/lvae-codec.py encode-yuv IN.yuv OUT.lvys --size 1920 1080 --container [--layout p010] [--siting left] [--matrix bt2020]
     python scripts/lvae-codec.py decode-yuv IN.lvys OUT.yuv [--layout p010]          # no colour flags: the container holds them
+    python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 3840 2160 --depth 10 --tile 512 768 --overlap 32 [--container]   # frames in tiles
     python scripts/lvae-codec.py eval-yuv IN.yuv --size 1920 1080 [--depth 10 | --layout p010 ...] [--ssim] [--ms-ssim]   # bpp, PSNR-YUV, SSIM as JSON
     python scripts/lvae-codec.py ratemap IMAGES/ MAPS/ -m qarv_base [--lmb 256]      # where the bits go: <stem>.npy + <stem>.png per image
 
@@ -34,7 +35,9 @@ ask for another depth or subsampling on purpose: the reconstruction is fp32).  -
 semi-planar with the value in the high bits (what hardware decoders deliver); the name gives depth and subsampling.  --container:
 encode-yuv writes ONE self-describing file (CodecBase.compress_yuv_sequence, the LVYS container of lvae/utils/yuvseq.py) instead of a
 folder; decode-yuv recognises it by its magic, takes every parameter from its header and writes the source's layout unless --layout
-/ --format asks for another.
+/ --format asks for another.  encode-yuv --tile TH TW [--overlap OV] codes every frame in tiles (CodecBase.compress_yuv_tiled: one tiled
+container per frame, as a .bits file or as the frame's entry of the --container file; the overlap is even where the chroma is
+subsampled); decode-yuv recognises such frames by their magic and writes the planes straight from the blend of the tiles.
 eval-yuv codes the frames of a raw file as encode-yuv would (the same --size / --format / --depth / --subsampling / --siting / --layout /
 colour flags, --frames, --batch, --lmb; --synthetic N writes seeded frames first), decodes them and prints lvae.evaluation.yuv_evaluate's
 dict of means as one JSON line: bpp and the PSNR keys, with --ssim also ssim-y / ssim-u / ssim-v, with --ms-ssim also ms-ssim-y (frames
@@ -130,9 +133,9 @@ def _is_sequence(path):
         return f.read(4) == MAGIC
 
 
-def encode_yuv_container(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False):
+def encode_yuv_container(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False, tile=None, overlap=0):
     kw = dict(depth=8, subsampling='420', siting='center', layout=fmt) if layout is None else dict(layout, layout='semiplanar' if sp else 'planar')
-    blob = model.compress_yuv_sequence(src, size[0], size[1], frames=frames, lmb=lmb, max_batch=batch, **kw, **colour)
+    blob = model.compress_yuv_sequence(src, size[0], size[1], frames=frames, lmb=lmb, max_batch=batch, tile=tile, overlap=overlap, **kw, **colour)
     Path(dst).write_bytes(blob)
     print(f'encoded {model.yuv_sequence_info(blob)["frames"]} frames -> {len(blob)} bytes')
 
@@ -142,7 +145,7 @@ def decode_yuv_container(model, src, dst, batch, layout=None):
     print(f'decoded {n} frames')
 
 
-def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False):
+def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False, tile=None, overlap=0):
     from lvae.utils.yuv import read_yuv, read_yuv420, read_yuv_sp
     if layout is None:
         fs, compress = read_yuv420(src, size[0], size[1], fmt, frames=frames), model.compress_yuv420
@@ -150,6 +153,9 @@ def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=No
         fs = (read_yuv_sp(src, size[0], size[1], layout['depth'], layout['subsampling'], frames=frames) if sp
               else read_yuv(src, size[0], size[1], layout['subsampling'], layout['depth'], frames=frames))
         compress = lambda chunk, **kw: model.compress_yuv(chunk, siting=layout['siting'], **kw)
+    if tile is not None:                                     # every frame on its own, as a tiled container, its tiles --batch at a time
+        sit = {} if layout is None else {'siting': layout['siting']}
+        compress = lambda chunk, **kw: [model.compress_yuv_tiled(f, tile=tile, overlap=overlap, max_batch=batch, **sit, **kw) for f in chunk]
     total = 0
     for o in range(0, len(fs), batch):
         blobs = compress(fs[o:o + batch], **colour, **({'lmb': lmb} if lmb is not None else {}))
@@ -160,11 +166,16 @@ def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=No
 
 
 def decode_yuv(model, src, dst, fmt, batch, colour, layout=None, sp=False):
+    from lvae.utils.tiling import MAGIC as TILED_MAGIC
     from lvae.utils.yuv import write_yuv, write_yuv420, write_yuv_sp
     paths = sorted(Path(src).glob('*.bits'))
+    out = dict(layout=fmt) if layout is None else dict(layout, layout='semiplanar' if sp else 'planar')
+    write = write_yuv420 if layout is None else write_yuv_sp if sp else write_yuv
     for o in range(0, len(paths), batch):
         blobs = [p.read_bytes() for p in paths[o:o + batch]]
-        if layout is None:
+        if all(b[:4] == TILED_MAGIC for b in blobs):         # encode-yuv --tile wrote them: one tiled container per frame
+            write([model.decompress_yuv_tiled(b, matrix=colour['matrix'], range=colour['range'], max_batch=batch, **out) for b in blobs], dst, append=o > 0)
+        elif layout is None:
             write_yuv420(model.decompress_yuv420(blobs, fmt=fmt, matrix=colour['matrix'], range=colour['range']), dst, append=o > 0)
         elif sp:
             write_yuv_sp(model.decompress_yuv(blobs, matrix=colour['matrix'], range=colour['range'], layout='semiplanar', **layout), dst, append=o > 0)
@@ -214,7 +225,7 @@ def build_parser():
     ap.add_argument('--lmb', type=float, default=None, help='variable-rate models: the lambda to code at (default: the model\'s)')
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('-d', '--device', type=str, default='cuda:0')
-    ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='encode: code every image in tiles of this size')
+    ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='encode / encode-yuv: code every image (frame) in tiles of this size')
     ap.add_argument('--overlap', type=int, default=0, help='encode with --tile: pixels neighbouring tiles share')
     ap.add_argument('--scale', type=float, default=None, help='encode: code every image at SCALE times its size (a scaled container per image)')
     ap.add_argument('--filter', type=str, default='lanczos3', choices=['bilinear', 'bicubic', 'lanczos3'], help='encode with --scale: the resampling filter')
@@ -279,7 +290,8 @@ def main(argv=None):
                 synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour, layout, sp)
             model = load_model(args.model, args.synthetic, torch.device(args.device))
             (encode_yuv_container if args.container else encode_yuv)(model, args.src, args.dst, args.size, args.format, args.frames, args.lmb,
-                                                                     args.batch, colour, layout, sp)
+                                                                     args.batch, colour, layout, sp,
+                                                                     tuple(args.tile) if args.tile else None, args.overlap)
         else:
             model = load_model(args.model, args.synthetic, torch.device(args.device))
             decode_yuv(model, args.src, args.dst, args.format, args.batch, colour, layout, sp)
