@@ -231,7 +231,8 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
     subsampling (utils.yuv.read_yuv; fmt must stay 'i420'), coded by compress_yuv / decompress_yuv with that siting and measured by
     lvae.metrics.psnr_yuv, whose key 'psnr-avg' joins the result; matrix may then be 'bt2020'.  layout 'semiplanar': a P010 / P012 / P210 /
     P212 file (utils.yuv.read_yuv_sp; depth 10 | 12, subsampling '420' | '422'), coded and reconstructed in that layout and measured on its
-    codes.
+    codes.  fmt, depth, subsampling and layout are resolved ONCE, to a utils.yuv.FrameFormat that reads the file and names what
+    compress_yuv / decompress_yuv code (they take every frame kind); a caller that holds a FrameFormat may pass it as `fmt`.
     metrics: 'psnr' (always reported: the keys above), 'ssim' adds 'ssim-y', 'ssim-u', 'ssim-v' (lvae.metrics.ssim_yuv) and 'ms-ssim' adds
     'ms-ssim-y' (lvae.metrics.ms_ssim_yuv on the luma plane; ValueError for frames with min(h, w) <= 160), both on the codes of the file's
     and the reconstruction's planes where they lie on the device, with data range 2^depth - 1; one more launch sequence per batch.  The
@@ -239,7 +240,7 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
     tile = (th, tw), overlap: every frame is coded in tiles (compress_yuv_tiled / decompress_yuv_tiled, `batch` tiles at a time); 'bpp'
     then counts the whole tiled container.  Only 'psnr' is measured on frames coded in tiles."""
     from .metrics import PSNR_YUV_KEYS, PSNR_YUV_KEYS2, ms_ssim_yuv, psnr_yuv, psnr_yuv420, ssim_yuv
-    from .utils.yuv import read_yuv, read_yuv420, read_yuv_sp
+    from .utils.yuv import FORMATS, FrameFormat
     if layout not in ('planar', 'semiplanar'):
         raise ValueError(f"yuv_evaluate: layout is 'planar' or 'semiplanar', got {layout!r}")
     unknown = set(colour) - {'matrix', 'range', 'chroma'}
@@ -252,32 +253,26 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
         raise ValueError(f'yuv_evaluate: frames of {height}x{width}; MS-SSIM needs min(h, w) > 160 (5 scales of an 11-tap window)')
     dev = next(model.parameters()).device
     dec = {k: v for k, v in colour.items() if k != 'chroma'}
-    general = (depth, subsampling, siting) != (8, '420', 'center') or layout == 'semiplanar'
-    if general:
-        if fmt != 'i420':
-            raise ValueError(f'yuv_evaluate: depth / subsampling / siting apply to planar files, got fmt={fmt!r}')
-        if layout == 'semiplanar':
-            frames = read_yuv_sp(yuv_path, width, height, depth, subsampling, frames=max_frames)
-        else:
-            frames = read_yuv(yuv_path, width, height, subsampling, depth, frames=max_frames)
-        compress = lambda chunk, **enc: model.compress_yuv(chunk, siting=siting, **enc)
-        decompress = lambda blobs: model.decompress_yuv(blobs, depth=depth, subsampling=subsampling, siting=siting, layout=layout, **dec)
-        measure, keys = psnr_yuv, PSNR_YUV_KEYS2
-    else:
-        frames = read_yuv420(yuv_path, width, height, fmt, frames=max_frames)
-        compress = model.compress_yuv420
-        decompress = lambda blobs: model.decompress_yuv420(blobs, fmt=fmt, **dec)
-        measure, keys = psnr_yuv420, PSNR_YUV_KEYS
+    if isinstance(fmt, FrameFormat):
+        layout, depth, subsampling = fmt
+    elif (depth, subsampling, siting, layout) == (8, '420', 'center', 'planar'):
+        layout = fmt                                          # the 8-bit 4:2:0 file of `fmt`, as Yuv420Frames
+    elif fmt != 'i420':
+        raise ValueError(f'yuv_evaluate: depth / subsampling / siting apply to planar files, got fmt={fmt!r}')
+    fmt = FrameFormat(layout, depth, subsampling, siting, colour.get('matrix', 'bt709'))
+    frames = fmt.read(yuv_path, width, height, frames=max_frames, who='yuv_evaluate')
+    how = dict(fmt._asdict(), siting=siting, **dec)
+    compress = lambda chunk, **enc: model.compress_yuv(chunk, siting=siting, **enc)
+    decompress = lambda blobs: model.decompress_yuv(blobs, **how)
+    measure, keys = (psnr_yuv420, PSNR_YUV_KEYS) if fmt.layout in FORMATS else (psnr_yuv, PSNR_YUV_KEYS2)      # their keys differ
     if tile is not None:
         if set(metrics) - {'psnr'}:
             raise ValueError(f"yuv_evaluate: frames coded in tiles are measured by 'psnr' only, got metrics={tuple(metrics)}")
-        sit = {'siting': siting} if general else {}
-        tiled_out = dict(depth=depth, subsampling=subsampling, siting=siting, layout=layout) if general else dict(layout=fmt)
 
         def compress(chunk, lmb=None, **enc):
             per = lmb if isinstance(lmb, list) else [lmb] * len(chunk)
-            return [model.compress_yuv_tiled(f, tile=tile, overlap=overlap, lmb=v, max_batch=batch, **sit, **enc) for f, v in zip(chunk, per)]
-        decompress = lambda blobs: [model.decompress_yuv_tiled(b, max_batch=batch, **tiled_out, **dec) for b in blobs]
+            return [model.compress_yuv_tiled(f, tile=tile, overlap=overlap, lmb=v, max_batch=batch, siting=siting, **enc) for f, v in zip(chunk, per)]
+        decompress = lambda blobs: [model.decompress_yuv_tiled(b, max_batch=batch, **how) for b in blobs]
     frames = [f.to(dev, non_blocking=True) for f in frames]
     rows, step = [], max(1, int(batch))
     for o in range(0, len(frames), step):

@@ -636,18 +636,20 @@ class CodecBase(nn.Module):
         per pixel); chroma upsampling ('nearest' | 'bilinear', centre siting), the matrix ('bt601' | 'bt709'), the range ('limited' |
         'full') and the padding happen where each pipeline group's plan reads its input.  The colour parameters are NOT stored in the
         stream -- the containers do not change -- so decompress_yuv420 has to be given the same matrix and range."""
-        from ..utils.yuv import Yuv420Batch
-        return self._compress_byte_batch(Yuv420Batch(frames, self.max_stride, self._dummy.device, matrix, range, chroma), lmb, 'compress_yuv420')
+        from ..utils.yuv import Yuv420Frame, _as_frames
+        return self.compress_yuv(_as_frames(frames, Yuv420Frame), lmb, matrix, range, chroma)
 
     @torch.no_grad()
     def decompress_yuv420(self, blobs, fmt='i420', matrix='bt709', range='limited'):
         """compress_yuv420 (or compress_images / compress_file) bytes -> list of utils.yuv.Yuv420Frame of layout `fmt` on the model's device,
         each cropped to the size in its header (which must be even) and converted on the device (utils.yuv.from_rgb01: forward matrix,
         2x2 chroma mean, round-half-even).  matrix / range: the stream does not record them; pass what the encoder was given."""
-        from ..utils.yuv import from_rgb01
-        return self._decompress_blobs(blobs, lambda x, sizes: from_rgb01(x, sizes, fmt=fmt, matrix=matrix, range=range))
+        from ..utils.yuv import _check
+        _check(matrix, range, fmt=fmt)
+        return self.decompress_yuv(blobs, matrix=matrix, range=range, layout=fmt)
 
-    # ---- the same for planar frames of 8 / 10 / 12 bits at 4:2:0 / 4:2:2 / 4:4:4 with centre- or left-sited chroma (the same kernels)
+    # ---- THE pair for YUV frames of every kind (utils.yuv.FrameFormat): 8 / 10 / 12 bits at 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar,
+    # centre- or left-sited chroma; the 8-bit 4:2:0 pair above forwards here
     @torch.no_grad()
     def compress_yuv(self, frames, lmb=None, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
         """compress_yuv420 for a list of utils.yuv.YuvFrame that share depth and subsampling and whose sizes PADDED to multiples of
@@ -657,14 +659,11 @@ class CodecBase(nn.Module):
         subsampling and siting are stored in the stream: decompress_yuv has to be given the encoder's (compress_yuv_sequence stores them).
         A list of utils.yuv.YuvSpFrame (P010 / P012 / P210 / P212) is taken as well: its two planes are uploaded as they are and each
         pipeline group's plan input is filled by lvae_image_yuvsp_to_f32, so the blobs are byte for byte those of the frames' to_planar().
-        Planar and semi-planar frames may not be mixed in one call."""
-        from ..utils.yuv import YuvBatch, YuvSpBatch, YuvSpFrame
-        frames = list(frames)
-        sp = [isinstance(f, YuvSpFrame) for f in frames]
-        if any(sp) and not all(sp):
-            raise ValueError('compress_yuv: planar and semi-planar frames may not be mixed in one call')
-        batch = (YuvSpBatch if any(sp) else YuvBatch)(frames, self.max_stride, self._dummy.device, matrix, range, chroma, siting)
-        return self._compress_byte_batch(batch, lmb, 'compress_yuv')
+        So is a list of utils.yuv.Yuv420Frame (what compress_yuv420 passes on), which takes siting='center' and no 'bt2020'.  Frames of
+        different kinds may not be mixed in one call."""
+        from ..utils.yuv import FrameFormat
+        frames, fmt = FrameFormat.shared(frames, 'compress_yuv')
+        return self._compress_byte_batch(fmt.batch(frames, self.max_stride, self._dummy.device, matrix, range, chroma, siting), lmb, 'compress_yuv')
 
     @torch.no_grad()
     def decompress_yuv(self, blobs, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar'):
@@ -672,12 +671,11 @@ class CodecBase(nn.Module):
         model's device, each cropped to the size in its header and converted on the device (utils.yuv.from_rgb01_any).  A depth above 8
         keeps precision of the fp32 reconstruction that 8-bit codes drop.  ValueError: a header's size does not fit the subsampling.
         depth / siting / matrix / range: the stream does not record them; pass what the encoder was given.  layout 'semiplanar' (depth
-        10 | 12, subsampling '420' | '422'): utils.yuv.YuvSpFrames holding the same codes, written in that layout by the kernel."""
-        from ..utils.yuv import SP_DEPTHS, SP_SUBSAMPLINGS, _check2, _extent_ok, from_rgb01_any
-        _check2(depth, subsampling, siting, matrix, range)
-        if layout not in ('planar', 'semiplanar') or (layout == 'semiplanar' and (depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS)):
-            raise ValueError(f"decompress_yuv: layout is 'planar' or -- at {SP_DEPTHS} bits and {SP_SUBSAMPLINGS} -- 'semiplanar', got {layout!r} "
-                             f'at {depth} bits and {subsampling}')
+        10 | 12, subsampling '420' | '422'): utils.yuv.YuvSpFrames holding the same codes, written in that layout by the kernel.  layout
+        'i420' | 'nv12' (depth 8, '420', 'center', no 'bt2020'): utils.yuv.Yuv420Frames, what decompress_yuv420 returns."""
+        from ..utils.yuv import _check2, _extent_ok, check_layout, from_rgb01_any
+        _check2(range=range)
+        check_layout(layout, depth, subsampling, siting, matrix)
         for i, b in enumerate(blobs):
             h, w = self._unpack_blob(b)[1]
             if not _extent_ok(h, w, subsampling):
@@ -699,7 +697,7 @@ class CodecBase(nn.Module):
         frames of ONE kind and size -- utils.yuv.YuvFrame, YuvSpFrame or Yuv420Frame; depth, subsampling and layout are then the frames' --
         or the path of a raw file of `width` x `height` frames of `depth`, `subsampling` and `layout` ('planar' | 'semiplanar' | 'i420' |
         'nv12'), of which `max_batch` at a time are read, uploaded and coded (all of them, or the first `frames`).  Frame k's blob is
-        compress_yuv([frame k], ...)[0] (compress_yuv420 for 'i420' / 'nv12'), whatever max_batch: batch rows are bit-equal to single calls.
+        compress_yuv([frame k], ...)[0], whatever max_batch: batch rows are bit-equal to single calls.
         lmb: None, one value or -- variable-rate models -- one value per frame.  The header records size, depth, subsampling, siting,
         matrix, range, chroma, the layout, this model's registry name and its GEMM precision: decompress_yuv_sequence needs nothing else.
         tile = (th, tw), overlap: every frame is coded in tiles and its entry is compress_yuv_tiled(frame k, tile, overlap, ...), a tiled
@@ -711,41 +709,20 @@ class CodecBase(nn.Module):
         if isinstance(frames_or_path, (str, os.PathLike)):
             if width is None or height is None:
                 raise ValueError('compress_yuv_sequence: a raw file needs width and height')
-            yuvseq.check_layout(layout, depth, subsampling, siting, matrix)
+            fmt = yuv.FrameFormat(layout, depth, subsampling, siting, matrix)
             path, limit = frames_or_path, None if frames is None else int(frames)
-            if layout in ('i420', 'nv12'):
-                per = yuv.frame_bytes(width, height)
-                read = lambda start, n: yuv.read_yuv420(path, width, height, layout, frames=n, start=start)
-            else:
-                per = yuv.frame_bytes2(width, height, subsampling, depth)
-                read = ((lambda start, n: yuv.read_yuv_sp(path, width, height, depth, subsampling, frames=n, start=start)) if layout == 'semiplanar'
-                        else (lambda start, n: yuv.read_yuv(path, width, height, subsampling, depth, frames=n, start=start)))
-            size = os.path.getsize(path)
+            per, size = fmt.frame_bytes(width, height), os.path.getsize(path)
             if size == 0 or size % per:
                 raise ValueError(f'compress_yuv_sequence: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
             total = size // per if limit is None else min(limit, size // per)
-            source = lambda start, n: read(start, min(n, total - start)) if start < total else []
+            source = lambda start, n: fmt.read(path, width, height, frames=min(n, total - start), start=start) if start < total else []
         else:
-            source = list(frames_or_path)
-            if not source:
-                raise ValueError('compress_yuv_sequence: no frames')
-            f0 = source[0]
-            if any(type(f) is not type(f0) or f.size != f0.size for f in source):
-                raise ValueError('compress_yuv_sequence: the frames of a sequence share one kind and one size')
-            if isinstance(f0, yuv.Yuv420Frame):
-                if any(f.fmt != f0.fmt for f in source):
-                    raise ValueError('compress_yuv_sequence: the frames of a sequence share one plane layout')
-                depth, subsampling, layout = 8, '420', f0.fmt
-            elif isinstance(f0, (yuv.YuvFrame, yuv.YuvSpFrame)):
-                depth, subsampling, layout = f0.depth, f0.subsampling, 'semiplanar' if isinstance(f0, yuv.YuvSpFrame) else 'planar'
-            else:
-                raise ValueError(f'compress_yuv_sequence: expected frames of utils.yuv, got {type(f0).__name__}')
-            (height, width) = f0.size
-            yuvseq.check_layout(layout, depth, subsampling, siting, matrix)
-        if layout in ('i420', 'nv12'):
-            compress = lambda chunk, **kw: self.compress_yuv420(chunk, matrix=matrix, range=range, chroma=chroma, **kw)
-        else:
-            compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
+            source, fmt = yuv.FrameFormat.shared(frames_or_path, 'compress_yuv_sequence')
+            (height, width) = source[0].size
+            if any(yuv.FrameFormat.of(f) != fmt or f.size != (height, width) for f in source):
+                raise ValueError('compress_yuv_sequence: the frames of a sequence share one kind, one plane layout and one size')
+            yuvseq.check_layout(*fmt, siting, matrix)
+        compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
         if tile is not None:
             self._tile_args(tile, overlap)
 
@@ -754,8 +731,8 @@ class CodecBase(nn.Module):
                 return [self.compress_yuv_tiled(f, tile=tile, overlap=overlap, lmb=v, max_batch=max_batch, matrix=matrix, range=range,
                                                 chroma=chroma, siting=siting) for f, v in zip(chunk, per)]
         blobs = yuvseq.code_sequence(compress, source, max_batch, lmb)
-        meta = dict(width=width, height=height, depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range, chroma=chroma,
-                    layout=layout, model=self._registry_name, gemm=self._prec)
+        meta = dict(fmt._asdict(), width=width, height=height, siting=siting, matrix=matrix, range=range, chroma=chroma,
+                    model=self._registry_name, gemm=self._prec)
         return yuvseq.pack_sequence(meta, blobs)
 
     def yuv_sequence_info(self, blob):
@@ -784,16 +761,11 @@ class CodecBase(nn.Module):
         if info['gemm'] != self._prec:
             raise ValueError(f"decompress_yuv_sequence: the sequence was written under GEMM precision {info['gemm']!r}, this model runs "
                              f"{self._prec!r}; call set_gemm_precision({info['gemm']!r}) first")
-        layout = info['layout'] if layout is None else layout
-        depth, sub, siting, matrix, rng = (info[k] for k in ('depth', 'subsampling', 'siting', 'matrix', 'range'))
-        yuvseq.check_layout(layout, depth, sub, siting, matrix)
-        if layout in ('i420', 'nv12'):
-            decode, write = (lambda bl: self.decompress_yuv420(bl, fmt=layout, matrix=matrix, range=rng)), yuv.write_yuv420
-        else:
-            decode = lambda bl: self.decompress_yuv(bl, depth=depth, subsampling=sub, siting=siting, matrix=matrix, range=rng, layout=layout)
-            write = yuv.write_yuv_sp if layout == 'semiplanar' else yuv.write_yuv
-        decode_tiled = lambda b: self.decompress_yuv_tiled(b, depth=depth, subsampling=sub, siting=siting, matrix=matrix, range=rng, layout=layout,
-                                                           max_batch=max_batch)
+        how = {k: info[k] for k in ('depth', 'subsampling', 'siting', 'matrix', 'range')}
+        how['layout'] = info['layout'] if layout is None else layout
+        yuvseq.check_layout(**{k: v for k, v in how.items() if k != 'range'})
+        decode = lambda bl: self.decompress_yuv(bl, **how)
+        decode_tiled = lambda b: self.decompress_yuv_tiled(b, max_batch=max_batch, **how)
         idxs, step, out = yuvseq.frame_indexes(info, frames), max(1, int(max_batch)), []
         for o in range(0, len(idxs), step):
             entries = [yuvseq.frame_blob(blob, info, k) for k in idxs[o:o + step]]
@@ -806,7 +778,7 @@ class CodecBase(nn.Module):
             if out_path is None:
                 out += got
             else:
-                write(got, out_path, append=o > 0)
+                yuv.write_frames(got, out_path, append=o > 0)
         return out if out_path is None else len(idxs)
 
     @torch.no_grad()
@@ -1042,7 +1014,7 @@ class CodecBase(nn.Module):
                            siting='center'):
         """One utils.yuv.YuvFrame, YuvSpFrame or Yuv420Frame -> the bytes of a tiled container (utils.tiling.pack_tiled, as compress_tiled).
         The frame is uploaded once; its tiles (utils.tiling.tile_grid) are frames whose planes are views of its planes, coded `max_batch`
-        at a time through compress_yuv (compress_yuv420 for a Yuv420Frame), so tile k's blob is compress_yuv([that crop as a frame])[0].
+        at a time through compress_yuv, so tile k's blob is compress_yuv([that crop as a frame])[0].
         tile, lmb, max_batch: as in compress_tiled.  overlap: even where the chroma is subsampled (both axes at '420', the width at
         '422'), so that every tile starts on the chroma grid -- ValueError otherwise.  matrix .. siting: as in compress_yuv; a Yuv420Frame
         takes siting='center' only.  Neither the colour parameters nor depth, subsampling and siting are stored."""
@@ -1050,39 +1022,23 @@ class CodecBase(nn.Module):
         th, tw, overlap = self._tile_args(tile, overlap)
         if lmb is not None and not self.variable_rate:
             raise ValueError(f'{type(self).__name__} is a fixed-rate model: it takes no lmb')
-        if not isinstance(frame, (yuv.YuvFrame, yuv.YuvSpFrame, yuv.Yuv420Frame)):
-            raise ValueError(f'compress_yuv_tiled: expected one frame of utils.yuv, got {type(frame).__name__}')
-        is420 = isinstance(frame, yuv.Yuv420Frame)
-        if is420 and siting != 'center':
-            raise ValueError(f"compress_yuv_tiled: a Yuv420Frame has centre-sited chroma, got siting={siting!r}")
-        sx, sy = yuv.SHIFTS['420' if is420 else frame.subsampling]
-        if overlap % 2 and sx:
-            raise ValueError(f"compress_yuv_tiled: overlap {overlap} is odd: tiles of a {'420' if is420 else frame.subsampling} frame start on "
-                             'the chroma grid, so the overlap is even')
+        fmt = yuv.FrameFormat.of(frame)
+        yuv.check_layout(*fmt, siting, matrix)
+        if overlap % 2 and yuv.SHIFTS[fmt.subsampling][0]:
+            raise ValueError(f'compress_yuv_tiled: overlap {overlap} is odd: tiles of a {fmt.subsampling} frame start on the chroma grid, so '
+                             'the overlap is even')
         h, w = frame.size
         ys, xs = tiling.tile_grid(h, w, th, tw, overlap)
         fr = frame.to(self._dummy.device, non_blocking=True)
-        lum = lambda p, y, x: p[y:y + th, x:x + tw]
-        chr_ = lambda p, y, x: p[y >> sy:(y + th) >> sy, x >> sx:(x + tw) >> sx]
-        if is420 and fr.fmt == 'nv12':
-            crop = lambda y, x: yuv.Yuv420Frame('nv12', lum(fr.y, y, x), uv=chr_(fr.uv, y, x))
-        elif is420:
-            crop = lambda y, x: yuv.Yuv420Frame('i420', lum(fr.y, y, x), chr_(fr.u, y, x), chr_(fr.v, y, x))
-        elif isinstance(fr, yuv.YuvSpFrame):                 # a UV row holds w samples: chroma pixel x / 2 starts at sample x
-            crop = lambda y, x: yuv.YuvSpFrame(lum(fr.y, y, x), fr.uv[y >> sy:(y + th) >> sy, x:x + tw], fr.depth, fr.subsampling)
-        else:
-            crop = lambda y, x: yuv.YuvFrame(lum(fr.y, y, x), chr_(fr.u, y, x), chr_(fr.v, y, x), fr.depth, fr.subsampling)
-        if is420:
-            compress = lambda chunk, **kw: self.compress_yuv420(chunk, matrix=matrix, range=range, chroma=chroma, **kw)
-        else:
-            compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
-        views = [crop(y, x) for y in ys for x in xs]
+        compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
+        views = [fmt.crop(fr, y, x, th, tw) for y in ys for x in xs]
         return tiling.pack_tiled(h, w, th, tw, overlap, self._code_tiles(compress, views, len(ys), len(xs), lmb, max_batch))
 
     def _decode_yuv_tiled(self, blob, box, depth, subsampling, siting, matrix, range, layout, max_batch):
         from ..utils import tiling, yuv
         who = 'decompress_yuv_tiled' if box is None else 'decompress_yuv_region'
-        yuv._yuv_layout(layout, depth, subsampling, siting, matrix, range, who)
+        yuv._check2(range=range)
+        yuv.check_layout(layout, depth, subsampling, siting, matrix)
         c = tiling.unpack_tiled(blob)
         if not yuv._extent_ok(c['h'], c['w'], subsampling):
             raise ValueError(f"{who}: the container holds a {c['h']} x {c['w']} image, which does not fit subsampling {subsampling}")

@@ -21,17 +21,24 @@ planes -- so yuv_to_rgb_expr2 / rgb_to_yuv_expr2 define it too.  Not supported: 
 8-bit semi-planar 4:2:2 / 4:4:4 (NV16 / NV24).  The colour parameters, the depth and the siting are the caller's on both sides: no stream
 stores them; the sequence container of utils/yuvseq.py does.
 
+What the three frame classes differ in is one value, `FrameFormat(layout, depth, subsampling)`: it reads, allocates, crops and batches
+frames of its kind, `to_rgb01_any` / `from_rgb01_any` take every kind through it (`to_rgb01` / `from_rgb01` forward to them), and which
+layout exists at which depth, subsampling, siting and matrix is the rule of utils.yuvseq.check_layout, stated nowhere else.
+
 `stitch_tiles_yuv` (the end of the file) writes a frame, or a window of one, straight from the decoded tiles of a tiled image
 (csrc/tile_stitch_yuv.hip): utils.image.stitch_tiles and from_rgb01_any as one kernel, with their bits.
 """
 import ctypes
+import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from .image import _canvas
+from .yuvseq import _extent_ok, check_layout
 
 from .._native import YUV_CHROMA as CHROMA, YUV_FORMATS as FORMATS, YUV_MATRICES as MATRICES, YUV_RANGES as RANGES   # index = LVAE_YUV_* code
 from .._native import YUV_DEPTHS as DEPTHS, YUV_MATRICES2 as MATRICES2, YUV_SITINGS as SITINGS, YUV_SUBSAMPLINGS as SUBSAMPLINGS
@@ -103,7 +110,7 @@ class Yuv420Frame:
 
 
 def frame_bytes(width, height):
-    return width * height * 3 // 2
+    return FrameFormat('i420').frame_bytes(width, height)
 
 
 def _read_raw(path, per, frames, start, who):
@@ -132,22 +139,7 @@ def read_yuv420(path, width, height, fmt='i420', frames=None, start=0):
     _check('bt709', 'limited', fmt=fmt)
     if width <= 0 or height <= 0 or width % 2 or height % 2:
         raise ValueError(f'read_yuv420: a 4:2:0 frame has even, positive sides, got {width} x {height}')
-    out, ny, nc = [], width * height, (width // 2) * (height // 2)
-    for fr in _read_raw(path, frame_bytes(width, height), frames, start, 'read_yuv420'):
-        y = fr[:ny].view(height, width)
-        if fmt == 'i420':
-            out.append(Yuv420Frame('i420', y, fr[ny:ny + nc].view(height // 2, width // 2), fr[ny + nc:].view(height // 2, width // 2)))
-        else:
-            out.append(Yuv420Frame('nv12', y, uv=fr[ny:].view(height // 2, width // 2, 2)))
-    return out
-
-
-def write_yuv420(frames, path, append=False):
-    """Write frames (any device) to a raw .yuv file, each in its own plane layout, one after the other."""
-    with open(path, 'ab' if append else 'wb') as f:
-        for fr in frames:
-            for p in fr.planes():
-                f.write(p.cpu().contiguous().numpy().tobytes())
+    return FrameFormat(fmt).read(path, width, height, frames, start, 'read_yuv420')
 
 
 # =============================================================================================== 8 / 10 / 12 bits, 4:2:0 / 4:2:2 / 4:4:4
@@ -161,19 +153,15 @@ def _check2(depth=8, subsampling='420', siting='center', matrix='bt709', range='
             raise ValueError(f'{what} is one of {known}, got {v!r}')
 
 
-def _extent_ok(h, w, subsampling):
-    sx, sy = SHIFTS[subsampling]
-    return h > 0 and w > 0 and h % (1 << sy) == 0 and w % (1 << sx) == 0
-
-
 class YuvFrame:
     """One planar frame of `depth` 8 | 10 | 12 bits at `subsampling` '420' | '422' | '444': planes y (h, w) and u, v of (h/2, w/2), (h, w/2)
     or (h, w) on one device -- torch.uint8 at depth 8, torch.int16 above it: the 16 bits of the container with the value in the LOW bits,
     as in yuv420p10le / yuv422p12le.  numpy arrays become CPU tensors (uint16 arrays are reinterpreted, not copied).  Both sides are even
     for 4:2:0, the width for 4:2:2.  A CPU frame with a code outside 0 .. 2^depth - 1 raises ValueError; frames on a device are not scanned:
-    the kernels mask every sample they read to `depth` bits (as does the defining expression)."""
+    the kernels mask every sample they read to `depth` bits (as does the defining expression).  scan=False: nor is this one, whose planes
+    are yet to be written."""
 
-    def __init__(self, y, u, v, depth=8, subsampling='420'):
+    def __init__(self, y, u, v, depth=8, subsampling='420', scan=True):
         _check2(depth, subsampling)
 
         def t(a):
@@ -192,7 +180,7 @@ class YuvFrame:
         cs = (h >> sy, w >> sx)
         if any(p.dtype != dtype or tuple(p.shape) != cs or p.device != y.device for p in (u, v)):
             raise ValueError(f'u and v are {cs} {dtype} planes on the device of y')
-        if depth > 8 and y.device.type == 'cpu':
+        if scan and depth > 8 and y.device.type == 'cpu':
             for name, p in zip('yuv', (y, u, v)):
                 if int(p.min()) < 0 or int(p.max()) > (1 << depth) - 1:
                     raise ValueError(f'plane {name} holds codes outside 0 .. {(1 << depth) - 1} (the value belongs in the low {depth} bits)')
@@ -224,16 +212,14 @@ class YuvFrame:
     def to_semiplanar(self):
         """The same codes as a YuvSpFrame (depth 10 | 12, '420' | '422'): word = code << (16 - depth), U and V interleaved.  Plain torch ops
         on the frame's device: a copy."""
-        if self.depth not in SP_DEPTHS or self.subsampling not in SP_SUBSAMPLINGS:
-            raise ValueError(f'semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {self.depth} bits at {self.subsampling}')
+        check_layout('semiplanar', self.depth, self.subsampling)
         mask, sh = (1 << self.depth) - 1, 16 - self.depth
         word = lambda p: ((p.to(torch.int32) & mask) << sh).to(torch.int16)
         return YuvSpFrame(word(self.y), torch.stack([word(self.u), word(self.v)], -1).flatten(1), self.depth, self.subsampling)
 
 
 def frame_bytes2(width, height, subsampling='420', depth=8):
-    sx, sy = SHIFTS[subsampling]
-    return (width * height + 2 * (width >> sx) * (height >> sy)) * (1 if depth == 8 else 2)
+    return FrameFormat('planar', depth, subsampling).frame_bytes(width, height)
 
 
 def read_yuv(path, width, height, subsampling='420', depth=8, frames=None, start=0):
@@ -241,28 +227,7 @@ def read_yuv(path, width, height, subsampling='420', depth=8, frames=None, start
     them, or the first `frames`; from frame `start` on).  As read_yuv420: ONE buffer, pinned when a GPU is there, the planes views of it.  ValueError: sides that do
     not fit the subsampling, a file size that is not a whole number of frames, an unknown depth / subsampling, a code beyond the depth."""
     _check2(depth, subsampling)
-    if not _extent_ok(height, width, subsampling):
-        raise ValueError(f'read_yuv: {width} x {height} does not fit subsampling {subsampling}')
-    sx, sy = SHIFTS[subsampling]
-    bps = 1 if depth == 8 else 2
-    ny, nc = width * height * bps, (width >> sx) * (height >> sy) * bps
-
-    def plane(b, h, w):
-        return (b if depth == 8 else b.view(torch.int16)).view(h, w)
-    out = []
-    for fr in _read_raw(path, frame_bytes2(width, height, subsampling, depth), frames, start, 'read_yuv'):
-        out.append(YuvFrame(plane(fr[:ny], height, width), plane(fr[ny:ny + nc], height >> sy, width >> sx),
-                            plane(fr[ny + nc:], height >> sy, width >> sx), depth, subsampling))
-    return out
-
-
-def write_yuv(frames, path, append=False):
-    """Write YuvFrames (any device) to a raw planar .yuv file, one after the other; 16-bit samples little-endian."""
-    with open(path, 'ab' if append else 'wb') as f:
-        for fr in frames:
-            for p in fr.planes():
-                a = p.cpu().contiguous().numpy()
-                f.write((a if a.dtype == np.uint8 else a.astype('<i2', copy=False)).tobytes())
+    return FrameFormat('planar', depth, subsampling).read(path, width, height, frames, start, 'read_yuv')
 
 
 # ----------------------------------------------------------------------------------------------- semi-planar 10 / 12 bits: P010 and kin
@@ -277,8 +242,7 @@ class YuvSpFrame:
     The low bits are ignored, whatever they hold.  numpy uint16 arrays are reinterpreted, not copied.  w is even, and h for 4:2:0."""
 
     def __init__(self, y, uv, depth=10, subsampling='420'):
-        if depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS:
-            raise ValueError(f'semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth!r} bits at {subsampling!r}')
+        check_layout('semiplanar', depth, subsampling)
 
         def t(a):
             if isinstance(a, torch.Tensor):
@@ -331,21 +295,116 @@ def read_yuv_sp(path, width, height, depth=10, subsampling='420', frames=None, s
     views of it.  ValueError: sides that do not fit, a file size that is not a whole number of frames, an unsupported depth / subsampling."""
     if depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS:
         raise ValueError(f'read_yuv_sp: semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth!r} bits at {subsampling!r}')
-    if not _extent_ok(height, width, subsampling):
-        raise ValueError(f'read_yuv_sp: {width} x {height} does not fit subsampling {subsampling}')
-    ny, ch = 2 * width * height, height >> SHIFTS[subsampling][1]
-    out = []
-    for fr in _read_raw(path, frame_bytes2(width, height, subsampling, depth), frames, start, 'read_yuv_sp'):   # as many samples as the planar layout
-        out.append(YuvSpFrame(fr[:ny].view(torch.int16).view(height, width), fr[ny:].view(torch.int16).view(ch, width), depth, subsampling))
-    return out
+    return FrameFormat('semiplanar', depth, subsampling).read(path, width, height, frames, start, 'read_yuv_sp')
 
 
-def write_yuv_sp(frames, path, append=False):
-    """Write YuvSpFrames (any device) to a raw P010-family file, one after the other: Y plane, UV plane, little-endian words."""
+# ----------------------------------------------------------------------------------------------- one description of a frame's format
+class FrameFormat(namedtuple('FrameFormat', 'layout depth subsampling')):
+    """What the three frame classes differ in, as one immutable value: `layout` 'planar' (YuvFrame), 'semiplanar' (YuvSpFrame), 'i420' /
+    'nv12' (Yuv420Frame), `depth` and `subsampling`.  ValueError for a combination that does not exist (utils.yuvseq.check_layout; `siting`
+    and `matrix` are checked with it where the caller has them, not kept).  Whatever depends on the kind of a frame -- its bytes in a file,
+    reading, allocating, cropping, batching -- is a method here, so that no caller branches on a frame's class."""
+    __slots__ = ()
+
+    def __new__(cls, layout='planar', depth=8, subsampling='420', siting='center', matrix='bt709'):
+        check_layout(layout, depth, subsampling, siting, matrix)
+        return super().__new__(cls, layout, depth, subsampling)
+
+    @classmethod
+    def of(cls, frame):
+        """The format of a frame (not checked again: the frame's class did that when the frame was made)."""
+        if isinstance(frame, Yuv420Frame):
+            return cls._make((frame.fmt, 8, '420'))
+        if isinstance(frame, (YuvFrame, YuvSpFrame)):
+            return cls._make(('semiplanar' if isinstance(frame, YuvSpFrame) else 'planar', frame.depth, frame.subsampling))
+        raise ValueError(f'expected a frame of utils.yuv, got {type(frame).__name__}')
+
+    @classmethod
+    def shared(cls, frames, who):
+        """(list(frames), the format of the first).  ValueError: no frames, something that is not a frame, kinds, depths or subsamplings
+        mixed in one call.  I420 and NV12 frames may meet in a list: the host expressions take both, and a launch refuses them itself."""
+        fs = list(frames)
+        if not fs:
+            raise ValueError(f'{who}: no frames')
+        fmts = [cls.of(f) for f in fs]
+        if any(f != fmts[0] and not (f.layout in FORMATS and fmts[0].layout in FORMATS) for f in fmts):
+            raise ValueError(f'{who}: frames of different kinds, depths or subsamplings may not be mixed in one call, got '
+                             f'{sorted(set(map(tuple, fmts)))}')
+        return fs, fmts[0]
+
+    @property
+    def dtype(self):
+        return torch.uint8 if self.depth == 8 else torch.int16
+
+    @property
+    def interleaved(self):
+        """One chroma plane of (U, V) pairs behind y, not a u and a v plane."""
+        return self.layout in ('semiplanar', 'nv12')
+
+    def _chroma_shapes(self, h, w):
+        sx, sy = SHIFTS[self.subsampling]
+        return ((h >> sy, w >> sx, 2),) if self.interleaved else ((h >> sy, w >> sx),) * 2
+
+    def frame(self, y, *chroma, scan=True):
+        """The frame of this format on planes given in file order: (y, u, v) or (y, uv)."""
+        if self.layout == 'i420':
+            return Yuv420Frame('i420', y, *chroma)
+        if self.layout == 'nv12':
+            return Yuv420Frame('nv12', y, uv=chroma[0])
+        if self.layout == 'semiplanar':
+            return YuvSpFrame(y, chroma[0], self.depth, self.subsampling)
+        return YuvFrame(y, *chroma, self.depth, self.subsampling, scan=scan)
+
+    def frame_bytes(self, width, height):
+        """The bytes of one frame in a raw file; a semi-planar frame holds as many samples as the planar one."""
+        sx, sy = SHIFTS[self.subsampling]
+        return (width * height + 2 * (width >> sx) * (height >> sy)) * (1 if self.depth == 8 else 2)
+
+    def read(self, path, width, height, frames=None, start=0, who='FrameFormat.read'):
+        """A raw file of `width` x `height` frames of this format -> list of frames on the CPU (all of them, or the first `frames`; from
+        frame `start` on).  The file is read into ONE buffer -- pinned when a GPU is there, so a frame's upload is an asynchronous copy
+        -- and the planes are views of it.  ValueError: sides that do not fit the subsampling, a file size that is not a whole number of
+        frames, a planar code beyond the depth."""
+        if not _extent_ok(height, width, self.subsampling):
+            raise ValueError(f'{who}: {width} x {height} does not fit subsampling {self.subsampling}')
+        shapes = ((height, width),) + self._chroma_shapes(height, width)
+        counts = [math.prod(s) for s in shapes]
+        return [self.frame(*(p.view(s) for p, s in zip(fr.view(self.dtype).split(counts), shapes)))
+                for fr in _read_raw(path, self.frame_bytes(width, height), frames, start, who)]
+
+    def new(self, h, w, device):
+        """An uninitialised (h, w) frame of this format on `device`."""
+        empty = lambda s: torch.empty(s, dtype=self.dtype, device=device)
+        return self.frame(empty((h, w)), *(empty(s) for s in self._chroma_shapes(h, w)), scan=False)
+
+    def crop(self, frame, y, x, th, tw):
+        """The window (y, x, th, tw) of a frame of this format -- on the chroma grid -- as a frame whose planes are views of the frame's."""
+        sx, sy = SHIFTS[self.subsampling]
+        rows = slice(y >> sy, (y + th) >> sy)
+        # a semi-planar UV row holds w samples: chroma pixel x / 2 starts at sample x (the uv of NV12 is indexed by chroma pixel, as u and v)
+        cols = slice(x, x + tw) if self.layout == 'semiplanar' else slice(x >> sx, (x + tw) >> sx)
+        return self.frame(frame.y[y:y + th, x:x + tw], *(p[rows, cols] for p in frame.planes()[1:]), scan=False)
+
+    def batch(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
+        """The _Batch of frames of this format that the codecs hand to compress_batch: Yuv420Batch (which takes no siting: ValueError
+        unless it is 'center'), YuvBatch or YuvSpBatch."""
+        check_layout(*self, siting, matrix)
+        if self.layout in FORMATS:
+            return Yuv420Batch(frames, div, device, matrix, range, chroma)
+        return (YuvSpBatch if self.layout == 'semiplanar' else YuvBatch)(frames, div, device, matrix, range, chroma, siting)
+
+
+def write_frames(frames, path, append=False):
+    """Write frames of any kind (any device) to a raw file, each in its own plane layout, one after the other; 16-bit samples
+    little-endian."""
     with open(path, 'ab' if append else 'wb') as f:
         for fr in frames:
             for p in fr.planes():
-                f.write(p.cpu().contiguous().numpy().astype('<i2', copy=False).tobytes())
+                a = p.cpu().contiguous().numpy()
+                f.write((a if a.dtype == np.uint8 else a.astype('<i2', copy=False)).tobytes())
+
+
+write_yuv420 = write_yuv = write_yuv_sp = write_frames
 
 
 # ----------------------------------------------------------------------------------------------- the defining expressions (CPU, fp32)
@@ -580,24 +639,23 @@ def to_rgb01(frames, div=1, device=None, matrix='bt709', range='limited', chroma
     of each frame's bytes (none for device frames) and one kernel launch for the batch, on `device` (default: the frames' device)."""
     fs = _as_frames(frames, Yuv420Frame)
     _check(matrix, range, chroma)
-    return _to_rgb(fs, div, device, lambda f: yuv_to_rgb_expr(f.y, f.u, f.v, matrix, range, chroma),
-                   lambda dev: Yuv420Batch(fs, div, dev, matrix, range, chroma))
+    return to_rgb01_any(fs, div, device, matrix, range, chroma)
 
 
 def to_rgb01_any(frames, div=1, device=None, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
     """to_rgb01 for a list of YuvFrame of one depth and subsampling -> ((B, 3, H, W) fp32 RGB in [0, 1], [(h, w)]).  siting: 'center' |
     'left' (where the chroma samples lie horizontally; see the module docstring); matrix also 'bt2020'.  CPU frames with device=None: the
     defining expression on the host.  Otherwise one upload of each frame's bytes and one kernel launch for the batch.  A list of
-    YuvSpFrame is taken too: on the host through to_planar (the definition), on the device by its own kernel."""
-    fs = list(frames)
-    sp = bool(fs) and all(isinstance(f, YuvSpFrame) for f in fs)
-    if sp and device is None and all(f.device.type == 'cpu' for f in fs):
-        fs, sp = [f.to_planar() for f in fs], False
-    fs = _as_frames(fs, YuvSpFrame if sp else YuvFrame)
-    _share_layout(fs)
-    _check2(fs[0].depth, fs[0].subsampling, siting, matrix, range, chroma)
-    return _to_rgb(fs, div, device, lambda f: yuv_to_rgb_expr2(f.y, f.u, f.v, f.depth, f.subsampling, siting, matrix, range, chroma),
-                   lambda dev: (YuvSpBatch if sp else YuvBatch)(fs, div, dev, matrix, range, chroma, siting))
+    YuvSpFrame is taken too: on the host through to_planar (the definition), on the device by its own kernel.  So is a list of
+    Yuv420Frame, which has siting 'center' and no 'bt2020': the call to_rgb01 makes."""
+    fs, fmt = FrameFormat.shared(frames, 'to_rgb01_any')
+    check_layout(*fmt, siting, matrix)
+    _check2(range=range, chroma=chroma)
+
+    def expr(f):
+        p = f.to_planar() if fmt.layout == 'semiplanar' else f
+        return yuv_to_rgb_expr2(p.y, p.u, p.v, fmt.depth, fmt.subsampling, siting, matrix, range, chroma)
+    return _to_rgb(fs, div, device, expr, lambda dev: fmt.batch(fs, div, dev, matrix, range, chroma, siting))
 
 
 def _rgb_items(x, sizes, who):
@@ -641,63 +699,37 @@ def from_rgb01(x, sizes=None, fmt='i420', matrix='bt709', range='limited'):
     xs = _rgb_items(x, sizes, 'from_rgb01')
     if any(v.shape[1] % 2 or v.shape[2] % 2 for v in xs):
         raise ValueError(f'from_rgb01: a 4:2:0 frame has even sides, got {[tuple(v.shape[1:]) for v in xs]}')
-    device = xs[0].device
-    if device.type == 'cpu':
-        return [Yuv420Frame('i420', *rgb_to_yuv_expr(v, matrix, range)).as_format(fmt) for v in xs]
-    new = lambda *s: torch.empty(*s, dtype=torch.uint8, device=device)
-    hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
-    if fmt == 'i420':
-        outs = [Yuv420Frame('i420', new(h, w), new(h // 2, w // 2), new(h // 2, w // 2)) for h, w in hw]
-    else:
-        outs = [Yuv420Frame('nv12', new(h, w), uv=new(h // 2, w // 2, 2)) for h, w in hw]
-    return _from_rgb(xs, outs, _fmt_names(outs), 'image_f32_to_yuv420', (FORMATS.index(fmt), MATRICES.index(matrix), RANGES.index(range)))
+    return from_rgb01_any(xs, matrix=matrix, range=range, layout=fmt)
 
 
 def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar'):
     """from_rgb01 for YuvFrames: fp32 RGB images in [0, 1] -> a list of YuvFrame of `depth` and `subsampling` on the same device, the
     chroma sampled for `siting`.  x, sizes: as in from_rgb01; extents that do not fit the subsampling raise ValueError.  Device tensors: one
     kernel launch for the batch on the current stream; CPU tensors: the defining expression.  layout 'semiplanar' (depth 10 | 12, '420' |
-    '422'): a list of YuvSpFrame holding the same codes, written by lvae_image_f32_to_yuvsp (CPU: to_semiplanar of the expression's frame)."""
-    _check2(depth, subsampling, siting, matrix, range)
-    if layout not in LAYOUTS:
-        raise ValueError(f'layout is one of {LAYOUTS}, got {layout!r}')
-    sp = layout == 'semiplanar'
-    if sp and (depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS):
-        raise ValueError(f'semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth} bits at {subsampling}')
+    '422'): a list of YuvSpFrame holding the same codes, written by lvae_image_f32_to_yuvsp (CPU: to_semiplanar of the expression's frame).
+    layout 'i420' / 'nv12' (depth 8, '420', 'center', 'bt601' | 'bt709'): a list of Yuv420Frame, written by lvae_image_f32_to_yuv420 -- the
+    call from_rgb01 makes.  ValueError: a layout that these parameters do not have (utils.yuvseq.check_layout)."""
+    _check2(range=range)
+    fmt = FrameFormat(layout, depth, subsampling, siting, matrix)
     xs = _rgb_items(x, sizes, 'from_rgb01_any')
-    if any(not _extent_ok(int(v.shape[1]), int(v.shape[2]), subsampling) for v in xs):
-        raise ValueError(f'from_rgb01_any: sizes {[tuple(v.shape[1:]) for v in xs]} do not fit subsampling {subsampling}')
-    device = xs[0].device
-    if device.type == 'cpu':
-        outs = [YuvFrame(*rgb_to_yuv_expr2(v, depth, subsampling, siting, matrix, range), depth, subsampling) for v in xs]
-        return [f.to_semiplanar() for f in outs] if sp else outs
-    sx, sy = SHIFTS[subsampling]
-    new = lambda *s: torch.empty(*s, dtype=torch.uint8 if depth == 8 else torch.int16, device=device)
     hw = [(int(v.shape[1]), int(v.shape[2])) for v in xs]
+    if any(not _extent_ok(h, w, subsampling) for h, w in hw):
+        raise ValueError(f'from_rgb01_any: sizes {hw} do not fit subsampling {subsampling}')
+    device, sp = xs[0].device, layout == 'semiplanar'
+    if device.type == 'cpu':
+        planes = [rgb_to_yuv_expr2(v, depth, subsampling, siting, matrix, range) for v in xs]
+        if layout in FORMATS:
+            return [Yuv420Frame('i420', *p).as_format(layout) for p in planes]
+        outs = [YuvFrame(*p, depth, subsampling) for p in planes]
+        return [f.to_semiplanar() for f in outs] if sp else outs
+    outs = [fmt.new(h, w, device) for h, w in hw]
+    if layout in FORMATS:
+        return _from_rgb(xs, outs, _fmt_names(outs), 'image_f32_to_yuv420', (FORMATS.index(layout), MATRICES.index(matrix), RANGES.index(range)))
     codes = (depth, SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix), RANGES.index(range))
-    if sp:
-        return _from_rgb(xs, [YuvSpFrame(new(h, w), new(h >> sy, w), depth, subsampling) for h, w in hw], YuvSpBatch.names, 'image_f32_to_yuvsp', codes)
-    outs = [YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling) for h, w in hw]
-    return _from_rgb(xs, outs, YuvBatch.names, 'image_f32_to_yuv', codes)
-
+    return _from_rgb(xs, outs, (YuvSpBatch if sp else YuvBatch).names, 'image_f32_to_yuvsp' if sp else 'image_f32_to_yuv', codes)
 
 
 # ----------------------------------------------------------------------------------------------- tiled images straight into YUV planes
-def _yuv_layout(layout, depth, subsampling, siting, matrix, range, who):
-    """The frame kind of a `layout` name, checked against the other parameters -> (semi-planar?, Yuv420Frame fmt or None)."""
-    _check2(depth, subsampling, siting, matrix, range)
-    if layout in FORMATS:                                    # 'i420' / 'nv12': the 8-bit 4:2:0 API and its frame class
-        if (depth, subsampling, siting) != (8, '420', 'center') or matrix not in MATRICES:
-            raise ValueError(f"{who}: layout {layout!r} is 8 bits at '420' with 'center' siting and matrix in {MATRICES}, got {depth} bits at "
-                             f'{subsampling!r}, {siting!r}, {matrix!r}')
-        return layout == 'nv12', layout
-    if layout not in LAYOUTS:
-        raise ValueError(f'{who}: layout is one of {LAYOUTS + FORMATS}, got {layout!r}')
-    if layout == 'semiplanar' and (depth not in SP_DEPTHS or subsampling not in SP_SUBSAMPLINGS):
-        raise ValueError(f'{who}: semi-planar frames are {SP_DEPTHS} bits at {SP_SUBSAMPLINGS}, got {depth} bits at {subsampling}')
-    return layout == 'semiplanar', None
-
-
 def check_chroma_box(box, subsampling, who):
     """ValueError unless box = (y0, x0, hh, ww) starts and ends on the chroma grid of `subsampling`: its frame then has whole chroma
     samples, and they are the full frame's."""
@@ -709,16 +741,8 @@ def check_chroma_box(box, subsampling, who):
 
 
 def new_frame(h, w, device, depth=8, subsampling='420', layout='planar'):
-    """An uninitialised frame of the kind `layout` names ('planar' YuvFrame, 'semiplanar' YuvSpFrame, 'i420' / 'nv12' Yuv420Frame)."""
-    sx, sy = SHIFTS[subsampling]
-    new = lambda *s: torch.empty(*s, dtype=torch.uint8 if depth == 8 else torch.int16, device=device)
-    if layout == 'i420':
-        return Yuv420Frame('i420', new(h, w), new(h // 2, w // 2), new(h // 2, w // 2))
-    if layout == 'nv12':
-        return Yuv420Frame('nv12', new(h, w), uv=new(h // 2, w // 2, 2))
-    if layout == 'semiplanar':
-        return YuvSpFrame(new(h, w), new(h >> sy, w), depth, subsampling)
-    return YuvFrame(new(h, w), new(h >> sy, w >> sx), new(h >> sy, w >> sx), depth, subsampling)
+    """FrameFormat(layout, depth, subsampling).new(h, w, device)."""
+    return FrameFormat(layout, depth, subsampling).new(h, w, device)
 
 
 def stitch_tiles_yuv(tiles, h, w, th, tw, overlap, box=None, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited',
@@ -736,7 +760,8 @@ def stitch_tiles_yuv(tiles, h, w, th, tw, overlap, box=None, depth=8, subsamplin
     from .image import _stitch_args
     from .tiling import tiles_in_box
     who = 'stitch_tiles_yuv'
-    sp, fmt = _yuv_layout(layout, depth, subsampling, siting, matrix, range, who)
+    _check2(range=range)
+    fmt = FrameFormat(layout, depth, subsampling, siting, matrix)
     box = (0, 0, int(h), int(w)) if box is None else tuple(int(v) for v in box)
     check_chroma_box(box, subsampling, who)
     ys, xs, (y0, x0, hh, ww), t0, addr, oy, ox = _stitch_args(tiles, h, w, th, tw, overlap, box, who)
@@ -747,13 +772,12 @@ def stitch_tiles_yuv(tiles, h, w, th, tw, overlap, box=None, depth=8, subsamplin
     if missing:
         raise ValueError(f'{who}: tiles {missing} were not decoded but meet the box {box}' + (' widened by the column before it' if xl < x0 else ''))
     device = t0.device
-    kind = Yuv420Frame if fmt else YuvSpFrame if sp else YuvFrame
     if out is None:
-        out = new_frame(hh, ww, device, depth, subsampling, layout)
-    elif (type(out) is not kind or out.size != (hh, ww) or out.device != device or (fmt and out.fmt != fmt)
-          or (not fmt and (out.depth, out.subsampling) != (depth, subsampling))):
-        raise ValueError(f'{who}: out is a {kind.__name__} of {hh} x {ww} on {device} with the layout, depth and subsampling asked for')
-    y, u, v = out.y, (out.uv if sp else out.u), (None if sp else out.v)
+        out = fmt.new(hh, ww, device)
+    elif FrameFormat.of(out) != fmt or out.size != (hh, ww) or out.device != device:
+        raise ValueError(f'{who}: out is a frame of {hh} x {ww} on {device} with the layout, depth and subsampling asked for')
+    sp = fmt.interleaved                                     # NV12 as well: for the kernel both are a plane of (U, V) pairs
+    y, u, v = out.planes() + ((None,) if sp else ())
     for p in (y, u, v):
         if p is not None and (p.stride(-1) != 1 or (p.dim() == 3 and p.stride(1) != 2)):
             raise ValueError(f'{who}: the planes of out have unit column stride')

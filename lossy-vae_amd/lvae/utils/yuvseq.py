@@ -1,5 +1,5 @@
 """The self-describing container of a coded YUV sequence, `LVYS`, host side.  Pure Python, no GPU (as utils/tiling.py for `LVTL`): the
-models' compress_yuv_sequence / decompress_yuv_sequence (lvae/models/base.py) code each frame through compress_yuv / compress_yuv420 and
+models' compress_yuv_sequence / decompress_yuv_sequence (lvae/models/base.py) code each frame through compress_yuv / decompress_yuv and
 keep the frames' blobs -- the models' own containers, unchanged -- inside this one, next to everything a decoder otherwise has to be
 told: frame size, depth, subsampling, siting, matrix, range, the encoder's chroma filter, the plane layout of the source, the model's name
 and the GEMM arithmetic that wrote the streams.  A table of byte lengths in front of the blobs gives random access to a frame.
@@ -31,14 +31,17 @@ def is_yuv_sequence(blob):
 
 
 def check_layout(layout, depth, subsampling, siting='center', matrix='bt709'):
-    """ValueError unless frames of `layout` exist at these parameters (the rule of utils.yuv's three frame classes)."""
-    if layout not in LAYOUTS:
-        raise ValueError(f'layout is one of {LAYOUTS}, got {layout!r}')
+    """ValueError unless frames of `layout` exist at these parameters.  THE statement of that rule: utils.yuv.FrameFormat, the models'
+    YUV entry points and this container all ask here."""
+    for v, known, what in ((layout, LAYOUTS, 'layout'), (depth, DEPTHS, 'depth'), (subsampling, SUBSAMPLINGS, 'subsampling'),
+                           (siting, SITINGS, 'siting'), (matrix, MATRICES, 'matrix')):
+        if v not in known:
+            raise ValueError(f'{what} is one of {known}, got {v!r}')
     if layout == 'semiplanar' and (depth not in (10, 12) or subsampling not in ('420', '422')):
         raise ValueError(f'semi-planar frames are 10 / 12 bits at 4:2:0 / 4:2:2, got {depth} bits at {subsampling}')
     if layout in ('i420', 'nv12') and ((depth, subsampling, siting) != (8, '420', 'center') or matrix == 'bt2020'):
-        raise ValueError(f'{layout} frames are 8 bits at 4:2:0 with centre-sited chroma and bt601 / bt709, got {depth} bits at {subsampling}, '
-                         f'{siting}, {matrix}')
+        raise ValueError(f"{layout} frames are 8 bits at 4:2:0 with siting 'center' and bt601 / bt709, got {depth} bits at {subsampling}, "
+                         f'siting {siting!r}, {matrix}')
 
 
 def _extent_ok(h, w, subsampling):

@@ -133,9 +133,14 @@ def _is_sequence(path):
         return f.read(4) == MAGIC
 
 
-def encode_yuv_container(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False, tile=None, overlap=0):
-    kw = dict(depth=8, subsampling='420', siting='center', layout=fmt) if layout is None else dict(layout, layout='semiplanar' if sp else 'planar')
-    blob = model.compress_yuv_sequence(src, size[0], size[1], frames=frames, lmb=lmb, max_batch=batch, tile=tile, overlap=overlap, **kw, **colour)
+def _decode_kw(fmt, colour):
+    """What decompress_yuv / decompress_yuv_tiled / from_rgb01_any take: the format and the colour parameters but the encoder's filter."""
+    return dict(fmt._asdict(), **{k: v for k, v in colour.items() if k != 'chroma'})
+
+
+def encode_yuv_container(model, src, dst, size, fmt, frames, lmb, batch, colour, tile=None, overlap=0):
+    blob = model.compress_yuv_sequence(src, size[0], size[1], frames=frames, lmb=lmb, max_batch=batch, tile=tile, overlap=overlap,
+                                       **fmt._asdict(), **colour)
     Path(dst).write_bytes(blob)
     print(f'encoded {model.yuv_sequence_info(blob)["frames"]} frames -> {len(blob)} bytes')
 
@@ -145,17 +150,10 @@ def decode_yuv_container(model, src, dst, batch, layout=None):
     print(f'decoded {n} frames')
 
 
-def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=None, sp=False, tile=None, overlap=0):
-    from lvae.utils.yuv import read_yuv, read_yuv420, read_yuv_sp
-    if layout is None:
-        fs, compress = read_yuv420(src, size[0], size[1], fmt, frames=frames), model.compress_yuv420
-    else:
-        fs = (read_yuv_sp(src, size[0], size[1], layout['depth'], layout['subsampling'], frames=frames) if sp
-              else read_yuv(src, size[0], size[1], layout['subsampling'], layout['depth'], frames=frames))
-        compress = lambda chunk, **kw: model.compress_yuv(chunk, siting=layout['siting'], **kw)
+def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, tile=None, overlap=0):
+    fs, compress = fmt.read(src, size[0], size[1], frames=frames), model.compress_yuv
     if tile is not None:                                     # every frame on its own, as a tiled container, its tiles --batch at a time
-        sit = {} if layout is None else {'siting': layout['siting']}
-        compress = lambda chunk, **kw: [model.compress_yuv_tiled(f, tile=tile, overlap=overlap, max_batch=batch, **sit, **kw) for f in chunk]
+        compress = lambda chunk, **kw: [model.compress_yuv_tiled(f, tile=tile, overlap=overlap, max_batch=batch, **kw) for f in chunk]
     total = 0
     for o in range(0, len(fs), batch):
         blobs = compress(fs[o:o + batch], **colour, **({'lmb': lmb} if lmb is not None else {}))
@@ -165,46 +163,35 @@ def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, layout=No
     print(f'encoded {len(fs)} frames -> {total} bytes')
 
 
-def decode_yuv(model, src, dst, fmt, batch, colour, layout=None, sp=False):
+def decode_yuv(model, src, dst, fmt, batch, colour):
     from lvae.utils.tiling import MAGIC as TILED_MAGIC
-    from lvae.utils.yuv import write_yuv, write_yuv420, write_yuv_sp
-    paths = sorted(Path(src).glob('*.bits'))
-    out = dict(layout=fmt) if layout is None else dict(layout, layout='semiplanar' if sp else 'planar')
-    write = write_yuv420 if layout is None else write_yuv_sp if sp else write_yuv
+    from lvae.utils.yuv import write_frames
+    paths, how = sorted(Path(src).glob('*.bits')), _decode_kw(fmt, colour)
     for o in range(0, len(paths), batch):
         blobs = [p.read_bytes() for p in paths[o:o + batch]]
         if all(b[:4] == TILED_MAGIC for b in blobs):         # encode-yuv --tile wrote them: one tiled container per frame
-            write([model.decompress_yuv_tiled(b, matrix=colour['matrix'], range=colour['range'], max_batch=batch, **out) for b in blobs], dst, append=o > 0)
-        elif layout is None:
-            write_yuv420(model.decompress_yuv420(blobs, fmt=fmt, matrix=colour['matrix'], range=colour['range']), dst, append=o > 0)
-        elif sp:
-            write_yuv_sp(model.decompress_yuv(blobs, matrix=colour['matrix'], range=colour['range'], layout='semiplanar', **layout), dst, append=o > 0)
+            got = [model.decompress_yuv_tiled(b, max_batch=batch, **how) for b in blobs]
         else:
-            write_yuv(model.decompress_yuv(blobs, matrix=colour['matrix'], range=colour['range'], **layout), dst, append=o > 0)
+            got = model.decompress_yuv(blobs, **how)
+        write_frames(got, dst, append=o > 0)
     print(f'decoded {len(paths)} frames')
 
 
-def eval_yuv(model, src, size, fmt, frames, lmb, batch, colour, layout=None, sp=False, metrics=('psnr',)):
+def eval_yuv(model, src, size, fmt, frames, lmb, batch, colour, metrics=('psnr',)):
     import json
     from lvae.evaluation import yuv_evaluate
-    res = yuv_evaluate(model, src, size[0], size[1], fmt=fmt, max_frames=frames, batch=batch, lmb=lmb, metrics=metrics,
-                       layout='semiplanar' if sp else 'planar', **(layout or {}), **colour)
+    res = yuv_evaluate(model, src, size[0], size[1], fmt=fmt, max_frames=frames, batch=batch, lmb=lmb, metrics=metrics, **colour)
     print(json.dumps(res))
     return res
 
 
-def synthetic_yuv(path, n, size, fmt, colour, layout=None, sp=False):
+def synthetic_yuv(path, n, size, fmt, colour):
     """N seeded frames of size (w, h) as a raw .yuv file: seeded RGB images through the defining host conversion."""
     import seeded_init
-    from lvae.utils.yuv import from_rgb01, from_rgb01_any, write_yuv, write_yuv420, write_yuv_sp
+    from lvae.utils.yuv import from_rgb01_any, write_frames
     w, h = size
     rgb = [torch.from_numpy(seeded_init.synthetic_image_u8(h, w, 300 + i)).permute(2, 0, 1).float().div(255) for i in range(n)]
-    if layout is None:
-        write_yuv420(from_rgb01(rgb, fmt=fmt, matrix=colour['matrix'], range=colour['range']), path)
-    elif sp:
-        write_yuv_sp(from_rgb01_any(rgb, matrix=colour['matrix'], range=colour['range'], layout='semiplanar', **layout), path)
-    else:
-        write_yuv(from_rgb01_any(rgb, matrix=colour['matrix'], range=colour['range'], **layout), path)
+    write_frames(from_rgb01_any(rgb, **_decode_kw(fmt, colour)), path)
 
 
 def ratemap(model, src, dst, lmb):
@@ -261,25 +248,25 @@ def main(argv=None):
             decode_yuv_container(model, args.src, args.dst, args.batch,
                                  'semiplanar' if args.layout else args.format if args.format != 'i420' else None)
             return
-        colour = dict(matrix=args.matrix, range=args.range, chroma=args.chroma)
-        sp = args.layout is not None
-        if sp:
-            from lvae.utils.yuv import SP_LAYOUTS
+        from lvae.utils.yuv import SP_LAYOUTS, FrameFormat
+        colour = dict(matrix=args.matrix, range=args.range, chroma=args.chroma, siting=args.siting)
+        layout = args.format                                 # Yuv420Frames, the 8-bit 4:2:0 centre-sited path, unless one option asks for more
+        if args.layout is not None:
             if args.format != 'i420':
                 ap.error('--layout and --format nv12 exclude each other')
-            args.depth, args.subsampling = SP_LAYOUTS[args.layout]
-        layout = None                                        # the 8-bit 4:2:0 centre-sited path unless one option asks for more
-        if (args.depth, args.subsampling, args.siting) != (8, '420', 'center') or args.matrix == 'bt2020':
+            layout, (args.depth, args.subsampling) = 'semiplanar', SP_LAYOUTS[args.layout]
+        elif (args.depth, args.subsampling, args.siting) != (8, '420', 'center') or args.matrix == 'bt2020':
             if args.format != 'i420':
                 ap.error('--depth / --subsampling / --siting / --matrix bt2020 apply to planar files (--format i420)')
-            layout = dict(depth=args.depth, subsampling=args.subsampling, siting=args.siting)
+            layout = 'planar'
+        fmt = FrameFormat(layout, args.depth, args.subsampling, args.siting, args.matrix)
         if args.command == 'eval-yuv':
             if args.size is None:
                 ap.error('eval-yuv needs --size W H')
             if args.synthetic:
-                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour, layout, sp)
+                synthetic_yuv(args.src, args.synthetic, args.size, fmt, colour)
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            eval_yuv(model, args.src, args.size, args.format, args.frames, args.lmb, args.batch, colour, layout, sp,
+            eval_yuv(model, args.src, args.size, fmt, args.frames, args.lmb, args.batch, colour,
                      ('psnr',) + (('ssim',) if args.ssim else ()) + (('ms-ssim',) if args.ms_ssim else ()))
         elif args.command == 'encode-yuv':
             if args.size is None:
@@ -287,14 +274,13 @@ def main(argv=None):
             if not args.container:
                 os.makedirs(args.dst, exist_ok=True)
             if args.synthetic:
-                synthetic_yuv(args.src, args.synthetic, args.size, args.format, colour, layout, sp)
+                synthetic_yuv(args.src, args.synthetic, args.size, fmt, colour)
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            (encode_yuv_container if args.container else encode_yuv)(model, args.src, args.dst, args.size, args.format, args.frames, args.lmb,
-                                                                     args.batch, colour, layout, sp,
+            (encode_yuv_container if args.container else encode_yuv)(model, args.src, args.dst, args.size, fmt, args.frames, args.lmb, args.batch, colour,
                                                                      tuple(args.tile) if args.tile else None, args.overlap)
         else:
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            decode_yuv(model, args.src, args.dst, args.format, args.batch, colour, layout, sp)
+            decode_yuv(model, args.src, args.dst, fmt, args.batch, colour)
         return
     os.makedirs(args.dst, exist_ok=True)
     if args.synthetic and args.command in ('encode', 'ratemap'):

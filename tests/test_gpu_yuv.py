@@ -358,6 +358,21 @@ def test_per_frame_lambdas(qarv):
         assert struct.unpack('f', blobs[i][4:8])[0] == lmb
 
 
+def test_the_general_entry_points_take_yuv420_frames(qarv):
+    """compress_yuv / decompress_yuv on Yuv420Frames are compress_yuv420 / decompress_yuv420: two 66 x 70 frames on one 128 x 128 canvas."""
+    for fmt in ('i420', 'nv12'):
+        frames = [_natural_frame(66, 70, 70 + i, fmt) for i in range(2)]
+        blobs = qarv.compress_yuv(frames)
+        assert all(isinstance(b, bytes) for b in blobs) and blobs == qarv.compress_yuv420(frames)
+        got, want = qarv.decompress_yuv(blobs, layout=fmt), qarv.decompress_yuv420(blobs, fmt=fmt)
+        assert len(got) == len(want) == 2
+        for g, w in zip(got, want):
+            assert type(g) is Yuv420Frame and g.fmt == fmt and g.size == (66, 70) and g.y.is_cuda
+            assert len(g.planes()) == len(w.planes()) and all(torch.equal(p, q) for p, q in zip(g.planes(), w.planes()))
+        with pytest.raises(ValueError, match='siting'):
+            qarv.compress_yuv(frames, siting='left')
+
+
 # ----------------------------------------------------------------------------------------------- yuv_evaluate
 @pytest.mark.parametrize('fmt', ['i420', 'nv12'])
 def test_yuv_evaluate_is_the_per_frame_loop(qarv, tmp_path, fmt):

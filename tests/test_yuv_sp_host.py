@@ -1,6 +1,7 @@
 """not-gpu: semi-planar high-bit-depth frames (P010 / P012 / P210 / P212) and the LVYS sequence container on the host -- the layout as torch
 ops (YuvSpFrame.to_planar / YuvFrame.to_semiplanar, which the GPU tests use as their reference), the raw files, the container's header and
-its refusals, and the argument checks of the two native entries (they return before any HIP call)."""
+its refusals, the rule of which layouts exist (utils.yuvseq.check_layout) with utils.yuv.FrameFormat for every frame kind, and the argument
+checks of the two native entries (they return before any HIP call)."""
 import ctypes
 import struct
 
@@ -10,8 +11,8 @@ import torch
 
 from lvae import _native
 from lvae.utils import yuvseq
-from lvae.utils.yuv import (SP_LAYOUTS, YuvFrame, YuvSpFrame, from_rgb01_any, frame_bytes2, read_yuv, read_yuv_sp, to_rgb01_any, write_yuv,
-                            write_yuv_sp)
+from lvae.utils.yuv import (SP_LAYOUTS, FrameFormat, Yuv420Frame, YuvFrame, YuvSpFrame, from_rgb01_any, frame_bytes2, read_yuv, read_yuv_sp,
+                            to_rgb01, to_rgb01_any, write_frames, write_yuv, write_yuv_sp)
 
 CASES = [(10, '420'), (12, '420'), (10, '422'), (12, '422')]
 
@@ -196,6 +197,105 @@ def test_container_does_not_depend_on_max_batch():
         yuvseq.code_sequence(compress, frames, 2, lmbs[:4])
     with pytest.raises(ValueError):
         yuvseq.code_sequence(compress, reader, 2, lmbs + [1])
+
+
+# ----------------------------------------------------------------------------------------------- which layouts exist, and FrameFormat
+def _layout_exists(layout, depth, sub, siting, matrix):
+    """The rule, written out: planar frames at any depth and subsampling; semi-planar ones at 10 or 12 bits and '420' or '422'; 'i420' /
+    'nv12' at 8 bits, '420', 'center' and bt601 or bt709."""
+    if layout == 'planar':
+        return True
+    if layout == 'semiplanar':
+        return depth in (10, 12) and sub in ('420', '422')
+    return depth == 8 and sub == '420' and siting == 'center' and matrix in ('bt601', 'bt709')
+
+
+def test_check_layout_is_the_rule_at_all_216_combinations():
+    import itertools
+    combos = list(itertools.product(('planar', 'semiplanar', 'i420', 'nv12'), (8, 10, 12), ('420', '422', '444'), ('center', 'left'),
+                                    ('bt601', 'bt709', 'bt2020')))
+    assert len(combos) == 216
+    for c in combos:
+        if _layout_exists(*c):
+            yuvseq.check_layout(*c)
+            assert tuple(FrameFormat(*c)) == c[:3]           # the constructor asks the same rule; siting and matrix are not kept
+        else:
+            with pytest.raises(ValueError):
+                yuvseq.check_layout(*c)
+            with pytest.raises(ValueError):
+                FrameFormat(*c)
+    assert sum(_layout_exists(*c) for c in combos) == 54 + 24 + 2 + 2
+    ok = ('planar', 10, '420', 'left', 'bt2020')
+    for k, bad in ((0, 'p010'), (0, None), (1, 9), (1, 16), (1, '10'), (2, '440'), (2, 420), (3, 'top'), (4, 'bt470')):   # outside the enumerations
+        with pytest.raises(ValueError):
+            yuvseq.check_layout(*ok[:k], bad, *ok[k + 1:])
+
+
+def test_the_one_byte_codes_of_the_container_keep_their_values():
+    """The header stores indexes into these tuples: their values and their order ARE the file format."""
+    assert yuvseq.DEPTHS == (8, 10, 12) and yuvseq.SUBSAMPLINGS == ('420', '422', '444') and yuvseq.SITINGS == ('center', 'left')
+    assert yuvseq.MATRICES == ('bt601', 'bt709', 'bt2020') and yuvseq.RANGES == ('limited', 'full') and yuvseq.CHROMA == ('nearest', 'bilinear')
+    assert yuvseq.LAYOUTS == ('planar', 'semiplanar', 'i420', 'nv12')
+    blob = yuvseq.pack_sequence(META, [])
+    assert tuple(blob[14:21]) == (1, 0, 1, 2, 1, 0, 1)       # META's depth 10, '420', 'left', 'bt2020', 'full', 'nearest', 'semiplanar'
+
+
+FORMAT_CASES = [('planar', 8, '444'), ('planar', 10, '422'), ('planar', 12, '420'), ('semiplanar', 10, '420'), ('semiplanar', 12, '422'),
+                ('i420', 8, '420'), ('nv12', 8, '420')]
+FRAME_KIND = {'planar': YuvFrame, 'semiplanar': YuvSpFrame, 'i420': Yuv420Frame, 'nv12': Yuv420Frame}
+
+
+def _seeded_frame(fmt, h, w, seed):
+    """fmt.new(...) with seeded codes in its planes: bytes, codes of `depth` bits, or -- semi-planar -- 16-bit words, low bits and all."""
+    fr, g = fmt.new(h, w, 'cpu'), np.random.default_rng(seed)
+    for p in fr.planes():
+        hi = 65536 if fmt.layout == 'semiplanar' else 1 << fmt.depth
+        p.copy_(torch.from_numpy(g.integers(0, hi, tuple(p.shape)).astype(np.uint8 if fmt.depth == 8 else np.uint16).view(np.uint8 if fmt.depth == 8 else np.int16)))
+    return fr
+
+
+def _same_planes(a, b):
+    return type(a) is type(b) and a.size == b.size and len(a.planes()) == len(b.planes()) and \
+        all(p.dtype == q.dtype and torch.equal(p, q) for p, q in zip(a.planes(), b.planes()))
+
+
+@pytest.mark.parametrize('case', FORMAT_CASES, ids=lambda c: '-'.join(map(str, c)))
+def test_frame_format_new_files_and_crop(tmp_path, case):
+    h, w = 12, 16
+    fmt = FrameFormat(*case)
+    assert fmt == case and (fmt.layout, fmt.depth, fmt.subsampling) == case and hash(fmt) == hash(FrameFormat(*case))
+    with pytest.raises(AttributeError):
+        fmt.depth = 8                                        # a value, not a record
+    new = fmt.new(h, w, 'cpu')
+    assert type(new) is FRAME_KIND[fmt.layout] and new.size == (h, w) and FrameFormat.of(new) == fmt
+    assert all(p.dtype == (torch.uint8 if fmt.depth == 8 else torch.int16) for p in new.planes())
+    frames = [_seeded_frame(fmt, h, w, 40 + i) for i in range(3)]
+    assert all(FrameFormat.of(f) == fmt for f in frames)
+    # files: write_frames then read
+    path = tmp_path / 'clip.yuv'
+    write_frames(frames[:2], path)
+    write_frames(frames[2:], path, append=True)
+    sx, sy = {'420': (1, 1), '422': (1, 0), '444': (0, 0)}[fmt.subsampling]
+    per = (h * w + 2 * (h >> sy) * (w >> sx)) * (1 if fmt.depth == 8 else 2)
+    assert fmt.frame_bytes(w, h) == per and path.stat().st_size == 3 * per
+    back = fmt.read(path, w, h)
+    assert len(back) == 3 and all(_same_planes(a, b) for a, b in zip(back, frames))
+    assert _same_planes(fmt.read(path, w, h, frames=1, start=2)[0], frames[2]) and len(fmt.read(path, w, h, frames=2)) == 2
+    with pytest.raises(ValueError, match='whole number'):
+        fmt.read(path, w + 2, h)
+    if fmt.subsampling != '444':
+        with pytest.raises(ValueError, match='does not fit'):
+            fmt.read(path, w + 1, h)
+    # crop: views of the frame's planes, and the window of the frame's conversion
+    fr = frames[0]
+    win = fmt.crop(fr, 4, 8, 8, 8)
+    assert type(win) is type(fr) and win.size == (8, 8) and FrameFormat.of(win) == fmt
+    assert all(p.untyped_storage().data_ptr() == q.untyped_storage().data_ptr() for p, q in zip(win.planes(), fr.planes()))
+    assert torch.equal(win.y, fr.y[4:12, 8:16])
+    convert = to_rgb01 if fmt.layout in ('i420', 'nv12') else to_rgb01_any
+    whole, part = convert([fr], chroma='nearest')[0], convert([win], chroma='nearest')[0]
+    assert tuple(part.shape) == (1, 3, 8, 8) and torch.equal(part, whole[:, :, 4:12, 8:16])
+    assert not torch.equal(part, whole[:, :, 4:12, 6:14])    # (the window is told apart from its neighbour)
 
 
 # ----------------------------------------------------------------------------------------------- the native entries' argument checks
