@@ -2,7 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-// erf(x) to < 1 ulp (max abs error 5.8e-8, checked against fp64 erf on a dense grid: tests/test_gpu_kernels.py::test_erf)
+// erf(x) to < 1 ulp (max abs error 5.8e-8; checked against fp64 erf on a dense grid: tests/test_gpu_entropy_kernels.py::test_rate_term_against_fp64,
+// through the only entry point that shows it, the erf form of the rate term, as differences Phi(a) - Phi(d) in absolute terms)
 // with 13 FMAs + one v_exp_f32, branch-free: a minimax polynomial in x^2 for |x| <= 0.9277 and 1 - exp(p(|x|)) beyond.
 // Replaces the device-library erff (about twice the VALU work) in the GELU epilogue, where it was ~15% of an fc1 launch.
 // No implicit mul+add contraction in these helpers (explicit fmaf only): the same GELU is evaluated in GEMM epilogues, GEMM
