@@ -363,6 +363,16 @@ int lvae_dwconv_ln_q8_v(const void* x, const float* wt, const float* bias, const
 int lvae_dwconv_ln_choice(int fmt, int affines, int per_image_vectors, int B, int H, int W, int C, int k,
                           int* family, int* tile_rows, int* tiles_per_wg);
 
+/* Which kernel instance lvae_gemm_f32 would launch for a prec 4 (f16x2) descriptor on a device of cu_count compute units, and how its
+ * split-K slices are reduced.  Host arithmetic only, no HIP call.  Reads the shape and mode fields of *d and the PRESENCE of A1, ws,
+ * cnt, res and gamma; never A0, Wt, Wt16, out, bias or status (they may be unset).
+ * *kernel: 1 gemm_h2_kernel, 2 gemm_h2n_kernel, 3 gemm_h2p_kernel.  params[5]: the instance's template arguments -- kernel 1: {TN,
+ * AGELU, AMODE}; 2: {NB, AMODE}; 3: {WM, TN, NBUF, FOLD, NLOAD}; unused slots 0.  *splitk: 0 none, 1 serial (inside gemm_h2n / the FOLD
+ * form of gemm_h2p), 2 parallel with in-kernel counters, 3 parallel + reduce launch, 4 parallel, reduction left to the consumer.
+ * Returns 0, or -22 for d == NULL, d->prec != 4, cu_count <= 0 and exactly where lvae_gemm_f32 returns -22 for these fields.  The
+ * launch path switches on the same function (csrc/gemm_h2_choice.h), so this is what it runs; the outputs may be NULL. */
+int lvae_gemm_h2_choice(const lvae_gemm_desc* d, int cu_count, int* kernel, int* params /* 5 ints */, int* splitk);
+
 int lvae_stem_bf16(const float* im, const float* wt, const float* bias, void* out,
                    int B, int H, int W, int Cout, float im_shift, float im_scale, int* range_flag, void* stream);
 int lvae_bias_expand_bf16(const float* bias, void* out, long M, int C, void* stream);

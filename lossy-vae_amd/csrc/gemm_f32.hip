@@ -24,6 +24,9 @@
 //  * the per-element accumulation order depends only on K (k-tile 32, substep 8, pairs (j, j+4)), never on the
 //    tile configuration or on M: a batch of 8 images gives bit-identical rows to 8 single-image calls, and the
 //    encoder and decoder (different M) derive bit-identical priors.  No split-K, no atomics.
+//
+// lvae_gemm_f32 is the entry point of every arithmetic.  For the f16x2 family (prec 4: gemm_h2.hip, gemm_h2n.hip, gemm_h2p.hip) the
+// rules -- which instance, whether the family takes the GEMM, how split-K is reduced -- are gemm_h2_choice.h's, not this file's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,6 +34,7 @@
 #include "device_math.h"
 
 #include "gemm_common.h"
+#include "gemm_h2_choice.h"
 
 namespace {
 
@@ -637,14 +641,45 @@ int lvae_splitk_reduce_launch(const lvae_gemm_desc* d, int S, hipStream_t st) {
 }
 
 int lvae_gemm_x3v2_try(const lvae_gemm_desc* d, hipStream_t st, int force_tn, int* rc);      // gemm_x3v2.hip
-int lvae_gemm_h2_try(const lvae_gemm_desc* d, hipStream_t st, int force_tn, int* rc);        // gemm_h2.hip
-int lvae_gemm_h2p_try(const lvae_gemm_desc* d, hipStream_t st, int force_tile, int* rc);     // gemm_h2p.hip
-int lvae_gemm_h2n_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc);          // gemm_h2n.hip
+int lvae_gemm_h2_launch(const lvae_gemm_desc* d, hipStream_t st, const int* params);          // gemm_h2.hip:  {TN, AGELU, AMODE}
+int lvae_gemm_h2n_launch(const lvae_gemm_desc* d, hipStream_t st, const int* params);         // gemm_h2n.hip: {NB, AMODE}
+int lvae_gemm_h2p_launch(const lvae_gemm_desc* d, hipStream_t st, const int* params);         // gemm_h2p.hip: {WM, TN, NBUF, FOLD, NLOAD}
 int lvae_gemm_launch_patch2(const lvae_gemm_desc* d, hipStream_t st);                        // gemm_f32_patch2.hip
 int lvae_gemm_launch_conv3(const lvae_gemm_desc* d, hipStream_t st);                         // gemm_f32_conv3.hip
 int lvae_gemm_lp_dispatch(const lvae_gemm_desc* d, hipStream_t st);                           // gemm_lp.hip
 int lvae_gemm_q8_dispatch(const lvae_gemm_desc* d, hipStream_t st);                           // gemm_q8.hip
 static int gemm_dispatch(const lvae_gemm_desc* d, hipStream_t st);
+
+// f16x2 (prec 4): one kernel family.  Which instance runs, whether the family takes the GEMM at all and how split-K slices are reduced
+// is gemm_h2_choice.h::choose -- every rule lives there; this function only does what the choice says.  The host asks for prec 4 only
+// where the family takes the GEMM (lvae/engine.py: Plan.gemm asks lvae_gemm_h2_choice), so -22 is an argument error upstream.
+static int gemm_h2_family(const lvae_gemm_desc* d, hipStream_t st) {
+    lvae_h2::Choice c;
+    if (const int rc = lvae_h2::choose(*d, lvae_cu_count(), &c)) return rc;
+    lvae_gemm_desc d2;
+    if (d->cnt && c.splitk >= 3) {             // counters the choice does not use: the kernel must not see them
+        d2 = *d;
+        d2.cnt = nullptr;
+        d = &d2;
+    }
+    const int rc = c.kernel == 1 ? lvae_gemm_h2_launch(d, st, c.params) : c.kernel == 2 ? lvae_gemm_h2n_launch(d, st, c.params)
+                                                                                        : lvae_gemm_h2p_launch(d, st, c.params);
+    if (rc || c.splitk != 3) return rc;        // 1: summed inside the kernel; 2: by each tile's last-arriving slice; 4: by the consumer
+    const long n = (long)d->M * (d->N >> 2);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *d, d->ksplit);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lvae_gemm_h2_choice(const lvae_gemm_desc* d, int cu_count, int* kernel, int* params, int* splitk) {
+    if (!d || d->prec != 4 || cu_count <= 0) return -22;
+    lvae_h2::Choice c;
+    if (const int rc = lvae_h2::choose(*d, cu_count, &c)) return rc;
+    if (kernel) *kernel = c.kernel;
+    if (params)
+        for (int i = 0; i < 5; ++i) params[i] = c.params[i];
+    if (splitk) *splitk = c.splitk;
+    return 0;
+}
 
 extern "C" int lvae_gemm_f32(const lvae_gemm_desc* d, void* stream) {
     if (!d || !d->A0 || (!d->Wt && !(d->prec != 0 && d->Wt16)) || !d->out || d->M <= 0 || d->N <= 0 || d->K <= 0) return -22;
@@ -665,18 +700,8 @@ extern "C" int lvae_gemm_f32(const lvae_gemm_desc* d, void* stream) {
     if (d->epi == LVAE_EPI_GAMMA_RES && !d->gamma) return -22;
     if (d->store != LVAE_ST_ROWMAJOR && (d->r <= 0 || d->N % (d->r * d->r) || d->H <= 0 || d->W <= 0)) return -22;
     hipStream_t st = (hipStream_t)stream;
+    if (d->prec == 4) return gemm_h2_family(d, st);
     const int S = ksp(d);
-    if (S > 1 && d->prec == 4 && d->a_h2) {
-        // pre-split operands: SERIAL split-K inside gemm_h2p_kernel (one workgroup adds the S slice sums in slice order: the parallel
-        // form's bits without workspace or reduce launch)
-        if (d->store != LVAE_ST_ROWMAJOR || (d->N & 3) || (d->ldo & 3) || (d->ldres & 3) || d->K % (32 * S)) return -22;
-        return gemm_dispatch(d, st);
-    }
-    if (S > 1 && d->prec == 4 && (d->cfg == 0 || d->cfg == 3)) {
-        // narrow outputs over large maps: gemm_h2n_kernel walks the slices serially too (same bits, no workspace traffic, no reduction)
-        int rc = 0;
-        if (lvae_gemm_h2n_try(d, st, d->cfg == 3, &rc)) return rc;
-    }
     if (S > 1) {
         if (!d->ws || d->store != LVAE_ST_ROWMAJOR || (d->N & 3) || (d->ldo & 3) || (d->ldres & 3) || d->K % (32 * S) ||
             (d->prec == 1 && d->K % (64 * S)))
@@ -684,10 +709,11 @@ extern "C" int lvae_gemm_f32(const lvae_gemm_desc* d, void* stream) {
         // In-kernel reduction only when no 128-B line of the workspace can hold columns of two different tiles (N % 32 == 0, or one
         // n-tile): a tile's reducer acquires at agent scope, which drops its CU's L1 but not lines its XCD's L2 fetched earlier in
         // this launch for a NEIGHBOURING tile's reduction.
+        lvae_gemm_desc d2;
         if (d->cnt && !((d->N & 31) == 0 || d->N <= 32)) {
-            lvae_gemm_desc d2 = *d;
+            d2 = *d;
             d2.cnt = nullptr;
-            return lvae_gemm_f32(&d2, stream);
+            d = &d2;
         }
         const int rc = gemm_dispatch(d, st);
         if (rc || d->cnt || d->defer_reduce) return rc;               // cnt: reduced in place by each tile's last-arriving slice; defer_reduce: by the consumer
@@ -698,15 +724,7 @@ extern "C" int lvae_gemm_f32(const lvae_gemm_desc* d, void* stream) {
     return gemm_dispatch(d, st);
 }
 
-static int gemm_dispatch(const lvae_gemm_desc* d, hipStream_t st) {
-    if (d->prec == 4) {                  // f16x2: one kernel family; the host asks for it only where it applies (engine.h2_eligible)
-        int rc = 0;
-        if (d->out_h2 && (d->store != LVAE_ST_ROWMAJOR || (d->epi != LVAE_EPI_BIAS && d->epi != LVAE_EPI_BIAS_GELU) || (d->N & 31) ||
-                          d->ldo != d->N || (d->ksplit > 1 && !d->a_h2)))
-            return -22;
-        if (d->a_h2) return lvae_gemm_h2p_try(d, st, d->cfg > 0 ? d->cfg : 0, &rc) ? rc : -22;     // cfg = 10 WM + TN: force a tile
-        return lvae_gemm_h2_try(d, st, d->cfg > 0 ? d->cfg : 0, &rc) ? rc : -22;                   // cfg: gemm_h2.hip's force codes
-    }
+static int gemm_dispatch(const lvae_gemm_desc* d, hipStream_t st) {      // fp32 / bf16 / bf16x3 (prec 0 .. 2)
     if (d->prec == 2 && d->cfg == 0 &&
         ((d->a_mode == LVAE_A_PLAIN && d->K0 + d->K1 == d->K) || d->a_mode == LVAE_A_CONV3)) {   // cfg -1: legacy kernel
         int rc = 0;

@@ -25,6 +25,9 @@
 // 20 r mod 64 is a permutation of the multiples of 4 for r = 0..15), a stage of one W row is 64 contiguous bytes, and a stage holds
 // 6*TN MFMAs per wave instead of 12*TN.  Per accumulator the MFMA sequence is fixed (k16 steps ascending; X: a_lo'*w_hi then
 // a_hi*w_lo'), so results do not depend on M, batch, tile shape (TN) or split-K workgroup placement.
+//
+// Dispatch.  Which GEMMs this kernel takes, its TN cost model and the order in which the family's kernels are tried are in
+// gemm_h2_choice.h (the one implementation; lvae_gemm_h2_choice reports it); this file holds the kernel and a launcher of a named instance.
 #include "gemm_common.h"
 
 #include <type_traits>
@@ -264,42 +267,15 @@ int launch_h2(const lvae_gemm_desc* d, hipStream_t st) {
 
 }  // namespace
 
-// Entry point for gemm_f32.hip's dispatcher (prec 4).  Returns 1 when the problem is one this kernel takes (*rc = launch status), 0
-// otherwise -- the host (lvae/engine.py: h2_eligible) only asks for prec 4 where it is, so 0 is an argument error upstream.
-// force (d.cfg): 0 = choose kernel and tile width; 1..2 = this kernel with that TN; 3 = gemm_h2n wherever it applies.  Every choice gives
-// the same bits.
-int lvae_gemm_h2n_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc);          // gemm_h2n.hip: narrow N over a large M
-
-int lvae_gemm_h2_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc) {
-    if ((force == 0 || force == 3) && lvae_gemm_h2n_try(d, st, force == 3, rc)) return 1;    // force 3: wherever that kernel can
-    const bool conv3 = d->a_mode == LVAE_A_CONV3, patch2 = d->a_mode == LVAE_A_PATCH2;
-    if (d->prec != 4 || (d->a_mode != LVAE_A_PLAIN && !conv3 && !patch2) || (d->K & 31) || d->ldw != d->K) return 0;
-    if (patch2 && ((d->K0 & 7) || d->K != 4 * d->K0 || d->K1 != 0 || d->H <= 0 || d->W <= 0 || d->a_gelu || (long)d->M * 4 * d->K0 * 4 > 0x7ffffff0L))
-        return 0;
-    if (!conv3 && !patch2 && ((d->lda0 & 3) || d->K0 + d->K1 != d->K)) return 0;
-    if (conv3 && ((d->K0 & 15) || d->K != 9 * d->K0 || d->K1 != 0 || d->H <= 0 || d->W <= 0 || (long)d->M * d->K0 * 4 > 0x7ffffff0L)) return 0;
-    const bool cat = d->K1 != 0 && !patch2;
-    if (cat && (!d->A1 || (d->K0 & 15) || (d->lda1 & 3) || (long)256 * d->lda1 * 4 > 0x7fffffffL)) return 0;
-    if ((long)128 * d->lda0 * 4 > 0x7fffffffL || (long)192 * 4 * d->K > 0x7fffffffL) return 0;
-    const int S = d->ksplit > 1 ? d->ksplit : 1;
-    if (S > 1 && (d->K % (32 * S))) return 0;
-    const int M = d->M, N = d->N, K = d->K / S;
-    int sel = force;
-    if (sel <= 0 || sel > 2) {
-        // rounds of 128 x 64c tiles over 2 x 256 workgroup slots x per-tile work / relative efficiency of the tile width
-        double best = 1e300;
-        const double eff[3] = {0, 0.70, 1.00};
-        for (int c = 1; c <= 2; ++c) {
-            const long tiles = (long)((M + 127) / 128) * ((N + 64 * c - 1) / (64 * c)) * S;
-            const long rounds = (tiles + 511) / 512;
-            const double cost = rounds * (128.0 * 64 * c) * (K + 96.0) / eff[c];
-            if (cost < best) { best = cost; sel = c; }
-        }
+// The instance gemm_h2_choice.h::choose named (kernel 1): params = {TN, AGELU, AMODE}.  Which GEMMs this kernel takes and the tile
+// width it gets are that header's rules; every choice gives the same bits.
+int lvae_gemm_h2_launch(const lvae_gemm_desc* d, hipStream_t st, const int* params) {
+    const int tn = params[0], gelu = params[1];
+#define LVAE_H2_LAUNCH(G, AM) (tn == 1 ? launch_h2<1, G, AM>(d, st) : launch_h2<2, G, AM>(d, st))
+    switch (params[2]) {
+        case LVAE_A_PATCH2: return LVAE_H2_LAUNCH(false, LVAE_A_PATCH2);
+        case LVAE_A_CONV3: return gelu ? LVAE_H2_LAUNCH(true, LVAE_A_CONV3) : LVAE_H2_LAUNCH(false, LVAE_A_CONV3);
+        default: return gelu ? LVAE_H2_LAUNCH(true, LVAE_A_PLAIN) : LVAE_H2_LAUNCH(false, LVAE_A_PLAIN);
     }
-#define LVAE_H2_LAUNCH(G, AM) (sel == 1 ? launch_h2<1, G, AM>(d, st) : launch_h2<2, G, AM>(d, st))
-    if (patch2) *rc = LVAE_H2_LAUNCH(false, LVAE_A_PATCH2);
-    else if (conv3) *rc = d->a_gelu ? LVAE_H2_LAUNCH(true, LVAE_A_CONV3) : LVAE_H2_LAUNCH(false, LVAE_A_CONV3);
-    else *rc = d->a_gelu ? LVAE_H2_LAUNCH(true, LVAE_A_PLAIN) : LVAE_H2_LAUNCH(false, LVAE_A_PLAIN);
 #undef LVAE_H2_LAUNCH
-    return 1;
 }

@@ -15,7 +15,7 @@
 //     double-buffered: ONE workgroup barrier per 48..72 MFMAs of a wave, no barrier on the A side at all.
 // Arithmetic: per accumulator the MFMA sequence of gemm_h2_kernel (k16 steps ascending; X += a_lo' w_hi, X += a_hi w_lo', H += a_hi w_hi),
 // fma(accX, 2^-11, accH), gemm_epilogue -- every output bit equals gemm_h2_kernel's (tests/test_gpu_f16x2.py::test_gemm_h2n_equals_gemm_h2),
-// so the choice between the two is the dispatcher's (shape only).  Split-K (d.ksplit = S, a function of the per-image shape) is taken in its
+// so the choice between the two is a rule in the shape only: gemm_h2_choice.h::h2n_takes, with this kernel's eligibility tests.  Split-K (d.ksplit = S, a function of the per-image shape) is taken in its
 // SERIAL form like gemm_h2p's FOLD: the wave restarts its accumulators at every slice boundary and adds the slices' partial sums in slice
 // order, then applies splitk_epilogue_store -- the operations of the parallel form + reduction in the same order, without the workspace.
 #include "gemm_common.h"
@@ -243,24 +243,11 @@ int launch_h2n(const lvae_gemm_desc* d, hipStream_t st) {
 
 }  // namespace
 
-// Entry point for gemm_h2.hip's dispatcher.  -> 1 when this kernel takes the problem (*rc = launch status).  force: take it whenever the
-// kernel CAN (tests); otherwise where it is the faster form (shape rule below; same bits either way).
-int lvae_gemm_h2n_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc) {
-    const bool conv3 = d->a_mode == LVAE_A_CONV3;
-    if (d->prec != 4 || d->a_h2 || d->a_gelu || d->out_h2 || (d->a_mode != LVAE_A_PLAIN && !conv3) || d->N > 96 || (d->K & 15) || d->ldw != d->K) return 0;
-    if (!conv3 && (d->K1 != 0 || d->K0 != d->K || (d->lda0 & 3) || (long)d->M * d->lda0 * 4 > 0x7ffffff0L)) return 0;
-    if (conv3 && ((d->K0 & 15) || d->K != 9 * d->K0 || d->K1 != 0 || d->H <= 0 || d->W <= 0 || (long)d->M * d->K0 * 4 > 0x7ffffff0L)) return 0;
-    if ((long)d->N * d->K * 4 > 0x7ffffff0L) return 0;
-    const int S = d->ksplit > 1 ? d->ksplit : 1;
-    if (S > 1 && ((d->K / 16) % S || d->store != LVAE_ST_ROWMAJOR || (d->N & 3) || (d->ldo & 3) || (d->ldres & 3))) return 0;
-    // shape rule: K = 16 (mod 32) has no other f16x2 kernel (gemm_h2_kernel walks the k16 steps in pairs) -- always; otherwise where it is
-    // the faster of the two (256-row workgroups: fewer than 128 of them leave the chip idle)
-    // (measured, profiles/r04_gemm_h2n_narrow_output.txt: 3x3 gathers and N = 65..96 from M = 49152 on: 1.1 - 1.25x; N <= 64 plain rows and
-    //  the split-K launches: gemm_h2_kernel is as fast or faster)
-    if (!force && !(d->K & 16) && !(d->M >= 32768 && S == 1 && (conv3 || d->N > 64))) return 0;
-    const int nb = (d->N + 31) / 32;
+// The instance gemm_h2_choice.h::choose named (kernel 2): params = {NB, AMODE}.  Which GEMMs this kernel takes, and where it is
+// preferred to gemm_h2_kernel, are that header's rules (same bits either way).
+int lvae_gemm_h2n_launch(const lvae_gemm_desc* d, hipStream_t st, const int* params) {
+    const int nb = params[0];
 #define LVAE_H2N_LAUNCH(AM) (nb == 1 ? launch_h2n<1, AM>(d, st) : nb == 2 ? launch_h2n<2, AM>(d, st) : launch_h2n<3, AM>(d, st))
-    *rc = conv3 ? LVAE_H2N_LAUNCH(LVAE_A_CONV3) : LVAE_H2N_LAUNCH(LVAE_A_PLAIN);
+    return params[1] == LVAE_A_CONV3 ? LVAE_H2N_LAUNCH(LVAE_A_CONV3) : LVAE_H2N_LAUNCH(LVAE_A_PLAIN);
 #undef LVAE_H2N_LAUNCH
-    return 1;
 }

@@ -21,6 +21,7 @@
 // Tiles: 64*WM x 64*TN, 2*WM waves (wave tile 64 x 32*TN, two accumulator sets): WM = 4 -> 256 rows, one workgroup per CU;
 // WM = 2 -> 128 rows, two per CU.  Per accumulator the MFMA sequence is gemm_h2_kernel's (k16 steps ascending; X: a_lo'*w_hi, a_hi*w_lo';
 // H: a_hi*w_hi), and the producers' split is the consumer's (exact), so every output bit equals gemm_h2_kernel's on the fp32 operand.
+// Dispatch: the tile rule, the force codes (d.cfg = 42 / 41 / 22 / 23 / 21) and the FOLD loader rule are in gemm_h2_choice.h::h2p_takes.
 #include "gemm_common.h"
 
 #include <type_traits>
@@ -313,47 +314,16 @@ int launch_h2p(const lvae_gemm_desc* d, hipStream_t st) {
 
 }  // namespace
 
-// Entry point for gemm_f32.hip's dispatcher (prec 4, a_h2 = 1).  force: 0 = choose; 10 * WM + TN = that tile (42 = 256 x 128,
-// 41 = 256 x 64, 22 = 128 x 128, 21 = 128 x 64).  Every choice gives the same bits.
-int lvae_gemm_h2p_try(const lvae_gemm_desc* d, hipStream_t st, int force, int* rc) {
-    if (d->prec != 4 || !d->a_h2 || d->a_mode != LVAE_A_PLAIN || d->K1 != 0 || d->K0 != d->K || (d->K & 31) || d->lda0 != d->K ||
-        d->ldw != d->K || d->a_gelu || (long)256 * d->K * 4 > 0x7fffffffL)
-        return 0;
-    const int M = d->M, N = d->N;
-    if (d->ksplit > 1) {
-        // serial split-K (FOLD): S slices of whole 32-deep stages, row-major fp32 / pre-split output with 16-B rows (what the reduce
-        // kernel's epilogue function stores), 128 x 64 tiles (the running sum lives beside two accumulator sets)
-        if ((d->K / 32) % d->ksplit || d->store != LVAE_ST_ROWMAJOR || (N & 3) || (d->ldo & 3) || (d->ldres & 3)) return 0;
-        // up to one workgroup per CU: eight loader waves beside the four compute waves (above); more tiles: two workgroups per CU hide
-        // each other's DMA issue as before
-        const int tiles = ((M + 127) / 128) * ((N + 63) / 64);
-        const bool loaders = tiles <= lvae_cu_count();
-        *rc = loaders ? launch_h2p<2, 1, 3, true, 8>(d, st) : launch_h2p<2, 1, 3, true>(d, st);
-        return 1;
+// The instance gemm_h2_choice.h::choose named (kernel 3): params = {WM, TN, NBUF, FOLD, NLOAD}, keyed here as 100 WM + 10 TN + NBUF.
+// Which tile a launch gets, and when the FOLD form runs with loader waves, are that header's rules; every choice gives the same bits.
+int lvae_gemm_h2p_launch(const lvae_gemm_desc* d, hipStream_t st, const int* params) {
+    if (params[3]) return params[4] ? launch_h2p<2, 1, 3, true, 8>(d, st) : launch_h2p<2, 1, 3, true>(d, st);
+    switch (100 * params[0] + 10 * params[1] + params[2]) {
+        case 423: return launch_h2p<4, 2, 3>(d, st);      // 256 x 128
+        case 413: return launch_h2p<4, 1, 3>(d, st);      // 256 x 64
+        case 222: return launch_h2p<2, 2, 2>(d, st);      // 128 x 128
+        case 212: return launch_h2p<2, 1, 2>(d, st);      // 128 x 64, two ring slots (48 KB): three workgroups per CU
+        case 213: return launch_h2p<2, 1, 3>(d, st);      // 128 x 64
     }
-    int sel = force;
-    if (sel != 42 && sel != 41 && sel != 22 && sel != 21 && sel != 23) {
-        // Tile by measurement (profiles/r03_gemm_h2p_tile_sweep.txt: every MLP shape of the model at batch 4 and 8 under each tile):
-        // least padded width first (N = 192: three 64-wide tiles, not two 128-wide); 64-wide: 128 x 64 everywhere; 128-wide: 128 x 64
-        // while 128 x 128 tiles would be fewer than ~4 per CU (the mid-size launches of one pipeline group: more, smaller workgroups
-        // fill the chip and overlap their epilogues), 256 x 128 only for the largest (stride-4, batch 8) launches
-        const int tn = (N % 128 == 0 || ((N + 127) / 128) * 128 - N < ((N + 63) / 64) * 64 - N + 1) ? 2 : 1;
-        const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-        sel = tn == 1 ? 21 : (t128 < 1024 ? 21 : (t128 >= 4096 ? 42 : 22));
-        // Round 5: the 128 x 64 tile with TWO ring slots (48 KB of LDS: three workgroups per CU instead of two; its 164 registers allow
-        // three waves per SIMD anyway).  One stage less of DMA look-ahead against a third workgroup whose epilogue can run under the
-        // other two's main loops: -2 ... -7 % where the K loop is short and the tiles are many, +5 ... +60 % on the few-tile long-K
-        // layers (profiles/r05_gemm_h2p_three_workgroups_per_cu.txt) -- taken for K <= 512 with at least two tiles per slot-pair
-        const long t64 = (long)((M + 127) / 128) * ((N + 63) / 64);
-        if (d->K <= 512 && t64 >= 512 && (sel == 21 || (sel == 22 && t128 < 2048))) sel = 23;
-    }
-    switch (sel) {
-        case 42: *rc = launch_h2p<4, 2, 3>(d, st); break;
-        case 41: *rc = launch_h2p<4, 1, 3>(d, st); break;
-        case 22: *rc = launch_h2p<2, 2, 2>(d, st); break;
-        case 23: *rc = launch_h2p<2, 1, 2>(d, st); break;      // 128 x 64, two ring slots (48 KB): three workgroups per CU
-
-        default: *rc = launch_h2p<2, 1, 3>(d, st); break;
-    }
-    return 1;
+    return -22;                                           // no such instance
 }

@@ -95,6 +95,7 @@ SIGNATURES = {
     'lvae_rans_decode_batch': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     'lvae_gemm_f32': (_i, [C.POINTER(GemmDesc), _vp]),
     'lvae_gemm_num_configs': (_i, []),
+    'lvae_gemm_h2_choice': (_i, [C.POINTER(GemmDesc), _i, _vp, _vp, _vp]),
     'lvae_mlp_h2f': (_i, [C.POINTER(MlpDesc), _vp]),
     'lvae_mlp_sk': (_i, [C.POINTER(MlpSkDesc), _vp]),
     'lvae_mlp_sk_supported': (_i, [_i, _i, _i, _i]),

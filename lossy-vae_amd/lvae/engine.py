@@ -43,34 +43,6 @@ def auto_ksplit(m1, N, K, store, ldo, ldres, prec):
     return best
 
 
-def h2_eligible(d):
-    """Does csrc/gemm_h2.hip / gemm_h2n.hip (prec 4, f16x2) take this GEMM?  Mirrors lvae_gemm_h2_try / lvae_gemm_h2n_try: a rule in the
-    GEMM's shape only (never in M), so batched and single-image calls, encoder and decoder agree."""
-    if d.ldw != d.K:
-        return False
-    if d.K % 32:
-        # K = 16 (mod 32) -- the 3x3 convs over 48 channels of the qres bottleneck blocks: gemm_h2_kernel walks the k16 steps in pairs;
-        # the narrow-output kernel (csrc/gemm_h2n.hip: N <= 96, plain rows or the 3x3 gather) takes any whole number of them
-        if d.K % 16 or d.N > 96 or d.a_gelu or d.out_h2 or d.ksplit > 1:
-            return False
-        if d.a_mode == _native.A_PLAIN:
-            return d.K1 == 0 and d.K0 == d.K and d.lda0 % 4 == 0 and d.M * d.lda0 * 4 <= 0x7ffffff0
-        if d.a_mode == _native.A_CONV3:
-            return d.K0 % 16 == 0 and d.K == 9 * d.K0 and d.K1 == 0 and d.H > 0 and d.W > 0 and d.M * d.K0 * 4 <= 0x7ffffff0
-        return False
-    if d.a_mode == _native.A_PLAIN:
-        if d.lda0 % 4 or d.K0 + d.K1 != d.K:
-            return False
-        if d.K1 and (not d.A1 or d.K0 % 16 or d.lda1 % 4):
-            return False
-        return True
-    if d.a_mode == _native.A_CONV3:
-        return d.K0 % 16 == 0 and d.K == 9 * d.K0 and d.K1 == 0 and d.H > 0 and d.W > 0 and d.M * d.K0 * 4 <= 0x7ffffff0
-    if d.a_mode == _native.A_PATCH2:
-        return d.K0 % 8 == 0 and d.K == 4 * d.K0 and d.K1 == 0 and d.H > 0 and d.W > 0 and not d.a_gelu and d.M * 16 * d.K0 <= 0x7ffffff0
-    return False
-
-
 _ORDER = object()        # marker of a stream-ordering entry in Plan.ops
 
 
@@ -215,12 +187,18 @@ class Plan:
     use_q8_pipeline = True             # reduced-precision plans: producer-side quantisation (False: the in-GEMM quantiser everywhere; A/B tool)
     H2P_MIN_ROWS_PER_IMAGE = 1536      # stride-4 / 8 / 16 maps of a 512x768 image; below, the few-tile layers want split-K (gemm_h2.hip)
 
+    def dwln_stores(self, fmt, C, k, n_affine):
+        """Has the depthwise + LayerNorm family a kernel that stores format fmt (2: H2K32 planes, 3: MX-fp8) for this block?  Those
+        formats exist in the channel-per-lane kernel only, so this is its rule in (C, k, affines), asked of the library
+        (lvae_dwconv_ln_choice on a 1 x 1 x 1 map)."""
+        return _native.lib().lvae_dwconv_ln_choice(fmt, n_affine, 0, 1, 1, 1, C, k, None, None, None) == 0
+
     def mlp_h2p_ok(self, C, hid, k, n_affine=1, rows_per_image=None):
         """f16x2 plans: can the MLP of a ConvNeXt block (dwconv+LN -> fc1 -> GELU -> fc2) run with pre-split operands -- the depthwise
         kernel and fc1's epilogue storing hi / lo' planes (H2K32) that fc1 / fc2 stream by LDS-DMA (csrc/gemm_h2p.hip)?  A rule in the
         block's shape and the rows of ONE image (never the batch size): the arithmetic -- hence every bit -- is the same either way
         (tests/test_gpu_f16x2.py), the rule only picks the faster pipeline."""
-        return (self.prec == 4 and self.w16_k32 is not None and C in (128, 192, 256, 384, 512) and k in (1, 3, 5, 7) and n_affine <= 1
+        return (self.prec == 4 and self.w16_k32 is not None and self.dwln_stores(2, C, k, n_affine)
                 and C % 32 == 0 and hid % 32 == 0 and (rows_per_image is None or rows_per_image >= self.H2P_MIN_ROWS_PER_IMAGE))
 
     # Serial split-K (gemm_h2p FOLD) against parallel split-K (gemm_h2 + reduce launch) on the few-tile layers: launch-time models fitted
@@ -258,7 +236,7 @@ class Plan:
         depthwise kernel and fc1's epilogue store MX-fp8 + block scales, csrc/gemm_q8.hip streams them by LDS-DMA)?  A rule in the
         block's shape only: in this mode the two pipelines differ in arithmetic (the producer quantises the fp32 value, the in-GEMM
         quantiser its bf16 rounding), so encoder and decoder must make the same choice for the same block."""
-        return (self.prec == 3 and self.use_q8_pipeline and self.w16_q8 is not None and C in (128, 192, 256, 384, 512) and k in (1, 3, 5, 7) and n_affine <= 1
+        return (self.prec == 3 and self.use_q8_pipeline and self.w16_q8 is not None and self.dwln_stores(3, C, k, n_affine)
                 and C % 64 == 0 and hid % 64 == 0)
 
     def gemm(self, *, A0, K0, M, N, Wt, bias, out, lda0=None, A1=None, K1=0, lda1=0, ldw=None, ldo=None,
@@ -300,10 +278,12 @@ class Plan:
             assert self.prec in (3, 4) and store == _native.ST_ROWMAJOR and N % (32 if self.prec == 4 else 64) == 0 and d.ldo == N, label
             if not a_h2:
                 ksplit = 1
-        if self.prec == 4 and not exact and not a_h2 and not (d.prec == 4 and h2_eligible(d)):
+        if self.prec == 4 and not exact and not a_h2 and not (d.prec == 4 and self.lib.lvae_gemm_h2_choice(ctypes.byref(d), 256, None, None, None) == 0):
             # f16x2 plans: what csrc/gemm_h2.hip / gemm_h2n.hip do not take (K % 16 != 0; K = 16 mod 32 with a wide output; a weight beyond fp16's range) runs on
             # the bf16x3 arithmetic -- decided by the GEMM's shape and weights only, so encoder and decoder, batched and single-image
-            # calls agree
+            # calls agree.  The rule is the library's own (csrc/gemm_h2_choice.h, the function its launch path switches on), asked
+            # for its return code on the descriptor as filled so far (ksplit, workspace and operand addresses unset): below the 2 GiB
+            # operand limits that code does not depend on M or the CU count (tests/test_gemm_h2_choice_host.py)
             Wt16 = self.w16_x3.get(Wt) if self.w16_x3 is not None else None
             d.prec = 2 if (Wt16 and K % 8 == 0) else 0
         d.Wt16 = Wt16 if d.prec else None

@@ -1,7 +1,8 @@
 """The instance and case table of the f16x2 GEMM family (prec 4: csrc/gemm_h2.hip, csrc/gemm_h2n.hip, csrc/gemm_h2p.hip), shared by
 tests/test_gpu_h2_instances.py (which launches every instance that can take a case and compares the forms bit for bit, and with fp64)
-and tests/test_h2_cases_host.py (which checks, without a GPU, that the table is the one the three sources declare and that every shape
-still straddles what it is listed for).
+and tests/test_h2_cases_host.py (which checks, without a GPU, that every form of the table runs the instance the table names -- asked of
+lvae_gemm_h2_choice, the function the launch path switches on -- and that every shape still straddles what it is listed for).
+h2_takes / h2n_takes / h2p_takes below are the tests' own statement of what the family takes; the library's is csrc/gemm_h2_choice.h.
 
 The family's contract: every launch form gives the same bits, so the dispatcher picks by speed alone.  A form is (a_h2, cfg, ksplit,
 cnt); `forms(case, cu)` lists the ones a case can take together with the kernel instance each of them runs:
@@ -24,7 +25,7 @@ EPIS = gc.EPIS
 EINVAL = -22
 
 # ------------------------------------------------------------------------------------------------ instances
-# gemm_h2.hip: the five uses of LVAE_H2_LAUNCH(G, AM), in the order lvae_gemm_h2_try writes them; each is two instances (TN = 1, 2)
+# gemm_h2.hip: the five uses of LVAE_H2_LAUNCH(G, AM), in the order lvae_gemm_h2_launch writes them; each is two instances (TN = 1, 2)
 H2_TNS = (1, 2)
 H2_LAUNCHES = ((0, A_PATCH2), (1, A_CONV3), (0, A_CONV3), (1, A_PLAIN), (0, A_PLAIN))          # (a_gelu, a_mode)
 H2_BM = 128
@@ -41,7 +42,7 @@ H2N_BM, H2N_WAVE_ROWS, H2N_MAX_N = 256, 32, 96
 H2N_CHUNK = 8                                   # N_CS: k16 steps per weight chunk
 H2N_PREFETCH = {1: 8, 2: 8, 3: 4}               # n_d<NB>(): k16 steps the A loads run ahead
 
-# gemm_h2p.hip: launch_h2p<WM, TN, NBUF[, FOLD[, NLOAD]]>; cfg = the force code of lvae_gemm_h2p_try's switch, 21 its `default:`
+# gemm_h2p.hip: launch_h2p<WM, TN, NBUF[, FOLD[, NLOAD]]>; cfg = the force code of gemm_h2_choice.h::h2p_takes, 21 its `default:`
 Tile = namedtuple('Tile', 'cfg WM TN NBUF FOLD NLOAD')
 H2P_TILES = (Tile(42, 4, 2, 3, False, 0), Tile(41, 4, 1, 3, False, 0), Tile(22, 2, 2, 2, False, 0), Tile(23, 2, 1, 2, False, 0),
              Tile(21, 2, 1, 3, False, 0))
@@ -75,7 +76,7 @@ def fold_tiles(M, N):
 
 
 def fold_loaders(M, N, cu):
-    """lvae_gemm_h2p_try under ksplit > 1: `tiles <= lvae_cu_count()` takes the instance with loader waves."""
+    """gemm_h2p_kernel under ksplit > 1: as many 128 x 64 tiles as the device has CUs, or fewer, take the instance with loader waves."""
     return fold_tiles(M, N) <= cu
 
 
@@ -124,8 +125,9 @@ def _patch2(Cin, N, epi):
     return Case(A_PATCH2, B * Ho * Wo, N, 4 * Cin, Cin, 0, Cin, 0, N, B, Ho, Wo, epi, 0, 0, 1)
 
 
-# ---- what each entry point takes (lvae_gemm_h2_try / lvae_gemm_h2n_try with force / lvae_gemm_h2p_try / the parallel split-K rule of
-# lvae_gemm_f32), for the shapes of this table (the 2^31 byte limits are out of reach here)
+# ---- what each kernel takes (gemm_h2_kernel / gemm_h2n_kernel when forced / gemm_h2p_kernel / the parallel split-K form), for the
+# shapes of this table (the 2^31 byte limits are out of reach here): the contract as the tests state it, independent of the library's
+# csrc/gemm_h2_choice.h
 def h2_takes(c):
     """gemm_h2_kernel (cfg = 1 / 2): k16 steps in pairs; S > 1 is the parallel form (workspace + reduction)."""
     if c.K % 32 or (c.out_h2 and (c.S > 1 or c.N % 32 or c.ldo != c.N or c.epi not in (EPI_BIAS, EPI_BIAS_GELU))):
@@ -167,7 +169,7 @@ def h2n_instance(c):
 
 def cnt_in_kernel(c):
     """With arrival counters the tile's last slice reduces in the kernel only when no 128-B line of the workspace holds columns of two
-    tiles; lvae_gemm_f32 sends the other shapes to the reduce launch."""
+    tiles; the other shapes go to the reduce launch."""
     return c.N % 32 == 0 or c.N <= 32
 
 
@@ -419,3 +421,45 @@ def all_cases():
     """Every case of the table with the test that runs it."""
     return ([('h2', c) for c in h2_cases()] + [('h2p', c) for c in h2p_cases()] + [('h2n', c) for c in h2n_cases()] +
             [('out_h2', c) for c in out_h2_cases()] + [('split', c) for c in split_cases()])
+
+
+# ---- asking the library: lvae_gemm_h2_choice (include/lvae_hip.h), the function lvae_gemm_f32 switches on
+def desc(c, f, present=1):
+    """The lvae_gemm_desc of form f of case c as tests/test_gpu_h2_instances.py launches it, operand addresses left out: the optional
+    pointers the choice looks at (A1, res, gamma, ws, cnt) are `present` where that launch passes one."""
+    from lvae._native import GemmDesc
+    d = GemmDesc()
+    d.M, d.N, d.K, d.K0, d.K1, d.H, d.W = c.M, c.N, c.K, c.K0, c.K1, c.H, c.W
+    d.lda0, d.lda1 = (c.K, 0) if f.a_h2 else (c.lda0, c.lda1)
+    d.ldw, d.ldo, d.ldres = c.K, c.ldo, c.ldo
+    d.a_mode, d.epi, d.a_gelu, d.out_h2, d.prec, d.cfg, d.a_h2 = c.a_mode, c.epi, c.a_gelu, c.out_h2, 4, f.cfg, f.a_h2
+    d.res = d.gamma = present
+    d.A1 = present if c.K1 and not f.a_h2 else None
+    if c.S > 1:
+        d.ksplit, d.ws, d.cnt = c.S, present, (present if f.cnt else None)
+    return d
+
+
+def choice(L, d, cu):
+    """lvae_gemm_h2_choice -> (return code, instance in the notation of all_instances(), split-K form); the last two None when rc != 0."""
+    import ctypes
+    kernel, params, splitk = ctypes.c_int(-1), (ctypes.c_int * 5)(), ctypes.c_int(-1)
+    rc = L.lvae_gemm_h2_choice(ctypes.byref(d), cu, ctypes.byref(kernel), params, ctypes.byref(splitk))
+    if rc != 0:
+        return rc, None, None
+    p = list(params)
+    inst = {1: ('h2', p[0], p[1], p[2]), 2: ('h2n', p[0], p[1]), 3: ('h2p', p[0], p[1], p[2], bool(p[3]), p[4])}[kernel.value]
+    assert not any(p[len(inst) - 1:]), p                   # unused slots are 0
+    return rc, inst, splitk.value
+
+
+SPLITK_NONE, SPLITK_SERIAL, SPLITK_COUNTERS, SPLITK_REDUCE_LAUNCH, SPLITK_DEFERRED = range(5)
+
+
+def form_splitk(c, f):
+    """The split-K form the table says form f of case c runs."""
+    if c.S == 1:
+        return SPLITK_NONE
+    if f.a_h2 or 'serial' in f.name:
+        return SPLITK_SERIAL
+    return SPLITK_COUNTERS if f.cnt and cnt_in_kernel(c) else SPLITK_REDUCE_LAUNCH

@@ -1,6 +1,7 @@
 """-m gpu: every kernel instance of the f16x2 GEMM family (prec 4: csrc/gemm_h2.hip, 10 instances; csrc/gemm_h2n.hip, 6;
 csrc/gemm_h2p.hip, 7) at the smallest shapes that straddle its tiles, stages and chunks -- the table of tests/h2_cases.py, whose
-arithmetic tests/test_h2_cases_host.py checks against the sources without a GPU.  Large shapes stay in tests/test_gpu_f16x2.py.
+arithmetic tests/test_h2_cases_host.py checks against lvae_gemm_h2_choice without a GPU; every launch here asks that function about
+its descriptor first, and it must give the launch's return code and the instance the form names.  Large shapes stay in tests/test_gpu_f16x2.py.
 
 One test id is (kernel, case); inside, every launch form that takes the case runs (h2_cases.forms: forced tile widths, the narrow-
 output kernel, every pre-split tile, the split-K forms), and
@@ -47,9 +48,13 @@ def L():
     return _native.lib()
 
 
+def _cu():
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
 @pytest.fixture(scope='module')
 def cu():
-    n = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    n = _cu()
     assert n >= hc.fold_tiles(hc.RAGGED_M, hc.FOLD_THRESHOLD_N), n
     return n
 
@@ -59,12 +64,14 @@ def _st():
 
 
 def _launch(L, **kw):
-    """lvae_gemm_f32 with the given descriptor fields -> return code (no synchronisation)."""
+    """lvae_gemm_f32 with the given descriptor fields -> (return code (no synchronisation), what lvae_gemm_h2_choice said of the same
+    descriptor just before: (return code, instance, split-K form))."""
     from lvae._native import GemmDesc
     d = GemmDesc()
     for k, v in kw.items():
         setattr(d, k, v.data_ptr() if torch.is_tensor(v) else v)
-    return L.lvae_gemm_f32(ctypes.byref(d), _st())
+    said = hc.choice(L, d, _cu())
+    return L.lvae_gemm_f32(ctypes.byref(d), _st()), said
 
 
 def _embed(t):
@@ -220,10 +227,13 @@ class Problem:
             kw.update(A0=self.Ak32, lda0=c.K, Wt16=self.Wk32, a_h2=1)
         else:
             kw.update(A0=self.A[0], A1=self.A[1], lda0=c.lda0, lda1=c.lda1, Wt16=self.W16)
-        rc = _launch(L, K0=c.K0, K1=c.K1, H=c.H, W=c.W, Wt=self.Wt, ldw=c.K, bias=self.bias, gamma=self.gamma, res=self.res, ldres=c.ldo,
+        rc, said = _launch(L, K0=c.K0, K1=c.K1, H=c.H, W=c.W, Wt=self.Wt, ldw=c.K, bias=self.bias, gamma=self.gamma, res=self.res, ldres=c.ldo,
                      out=out[GUARD:], ldo=c.ldo, M=c.M, N=c.N, K=c.K, a_mode=c.a_mode, epi=c.epi, a_gelu=c.a_gelu, prec=4, cfg=f.cfg,
                      out_h2=c.out_h2, **kw)
+        assert said[0] == expect, f'{f.name}: lvae_gemm_h2_choice returns {said[0]}'
         assert rc == expect, f'{f.name}: return code {rc}'
+        if f.instance is not None:
+            assert said[1] == f.instance, f'{f.name}: lvae_gemm_h2_choice names {said[1]}'
         return out
 
     def view(self, out, c=None):

@@ -1,8 +1,9 @@
-"""not-gpu: the arithmetic of tests/h2_cases.py.  The instance table is compared with the text of csrc/gemm_h2.hip, csrc/gemm_h2n.hip and
-csrc/gemm_h2p.hip (the launch_h2p<...> argument lists and force codes, the LVAE_H2_LAUNCH / LVAE_H2N_LAUNCH macros and their uses, the
-FOLD rule, N_CS, n_d<NB>() and the tile sizes), every instance must have a case, and every shape is checked to straddle what it is
-listed for -- so that an edit of a shape, or a new instance or force code in the source, fails here instead of quietly narrowing
-what tests/test_gpu_h2_instances.py covers."""
+"""not-gpu: the arithmetic of tests/h2_cases.py.  Every form of the table is put to lvae_gemm_h2_choice -- the function the launch path
+switches on (csrc/gemm_h2_choice.h) -- which must take it, name the table's instance and split-K form, and refuse the table's refusals;
+the instantiations and the geometry constants of csrc/gemm_h2.hip, csrc/gemm_h2n.hip and csrc/gemm_h2p.hip (the launch_*<...> argument
+lists, N_CS, n_d<NB>(), the tile sizes) are compared with the table, every instance must have a case, and every shape is checked to
+straddle what it is listed for -- so that an edit of a shape, a rule or a new instance in the source fails here instead of quietly
+narrowing what tests/test_gpu_h2_instances.py covers."""
 import os
 import re
 
@@ -34,83 +35,89 @@ def h2p():
     return _read('gemm_h2p.hip')
 
 
-def _tile(args, cfg=None):
+@pytest.fixture(scope='module')
+def L():
+    from lvae import _native
+    return _native.lib()
+
+
+def _tile(args):
     a = [x.strip() for x in args.split(',')]
     assert 3 <= len(a) <= 5, args
     fold = {'true': True, 'false': False}[a[3]] if len(a) > 3 else False
-    return hc.Tile(cfg, int(a[0]), int(a[1]), int(a[2]), fold, int(a[4]) if len(a) > 4 else 0)
+    return hc.Tile(None, int(a[0]), int(a[1]), int(a[2]), fold, int(a[4]) if len(a) > 4 else 0)
 
 
-# ------------------------------------------------------------------------------------------------ the table is the source
-def test_h2p_tiles_are_the_source(h2p):
+CUS = (64, 256, 304)
+
+
+def _sweep(cu):
+    return [c for _, c in hc.all_cases()] + [hc.fold_threshold_case(cu, *s) for s in hc.FOLD_THRESHOLD_SPECS]
+
+
+# ------------------------------------------------------------------------------------------------ the table is what a launch runs
+def test_forms_run_the_instances_the_table_names(L):
+    """Every form of every case, on devices of 64, 256 and 304 CUs: the library takes it, runs the instance the table names (where the
+    table leaves the choice to the library: one that a forced form of the case names) and reduces split-K the way the form says.  Over
+    the sweep the library reaches exactly the 23 instances of the table."""
+    reached = set()
+    for cu in CUS:
+        for c in _sweep(cu):
+            fs = hc.forms(c, cu)
+            named = {f.instance for f in fs if f.instance is not None}
+            for f in fs:
+                rc, inst, splitk = hc.choice(L, hc.desc(c, f), cu)
+                assert rc == 0, (cu, hc.case_id(c), f.name, rc)
+                assert inst == f.instance if f.instance is not None else inst in named, (cu, hc.case_id(c), f.name, inst)
+                assert splitk == hc.form_splitk(c, f), (cu, hc.case_id(c), f.name, splitk)
+                reached.add(inst)
+    assert reached == hc.all_instances(), reached ^ hc.all_instances()
+
+
+def test_refusals_get_their_return_code(L):
+    assert len(hc.refusals()) >= 12
+    for cu in CUS:
+        for c, cfg, want in hc.refusals():
+            rc, _, _ = hc.choice(L, hc.desc(c, hc.Form(f'cfg {cfg}', 0, cfg, False, None)), cu)
+            assert rc == want, (hc.case_id(c), cfg, rc)
+
+
+def test_sources_instantiate_what_the_table_names(h2, h2n, h2p):
+    """An instantiation added to a source without a case fails here; so does a change of the geometry the shapes are built around.
+    (Which instance a launch runs is not read from the text: test_forms_run_the_instances_the_table_names asks the library.)"""
+    # gemm_h2p.hip: the launch_h2p<...> argument lists are the five tiles and the FOLD pair
     assert re.search(r'template <int WM, int TN, int NBUF, bool FOLD = false, int NLOAD = 0>\s*int launch_h2p\(', h2p)
-    assert len(re.findall(r'constexpr int BM = 64 \* WM, BN = 64 \* TN', h2p)) == 2                 # the kernel and its launcher
-    assert 'const int nq = d.K / 32;' in h2p and hc.H2P_STAGE == 32
-    entry = h2p[h2p.index('int lvae_gemm_h2p_try('):]
-    # every instantiation is in the entry point: the switch, its default, and the FOLD pair
-    assert len(re.findall(r'launch_h2p<', h2p)) == len(re.findall(r'launch_h2p<', entry)) == len(hc.H2P_TILES) + 2
-    switch = entry[entry.index('switch (sel) {'):]
-    switch = switch[:switch.index('\n    }\n')]
-    cases = [(int(k), a) for k, a in re.findall(r'case (\d+): \*rc = launch_h2p<([^>]+)>\(d, st\)', switch)]
-    (default,) = re.findall(r'default: \*rc = launch_h2p<([^>]+)>\(d, st\)', switch)
-    assert hc.H2P_DEFAULT not in dict(cases)
-    found = tuple(_tile(a, k) for k, a in cases) + (_tile(default, hc.H2P_DEFAULT),)
-    assert found == hc.H2P_TILES
-    assert len(set(hc.instance_of(t) for t in found)) == len(found)
-    # the force codes the entry point keeps: exactly the switch's cases and the default
-    (keep,) = re.findall(r'if \((sel != \d+(?: && sel != \d+)*)\) \{', entry)
-    codes = tuple(int(x) for x in re.findall(r'sel != (\d+)', keep))
-    assert codes == hc.H2P_FORCE_CODES and sorted(codes) == sorted(t.cfg for t in hc.H2P_TILES)
+    found = [_tile(a) for a in re.findall(r'launch_h2p<([^>]+)>\(d, st\)', h2p)]
+    assert len(re.findall(r'launch_h2p<', h2p)) == len(found) == len(hc.H2P_TILES) + 2 == 7
+    assert {hc.instance_of(t) for t in found} == {hc.instance_of(t) for t in hc.H2P_TILES + (hc.FOLD_LOADERS, hc.FOLD_PLAIN)}
     for t in hc.H2P_TILES:                                   # cfg = 10 WM + TN, 23 the two-slot form of 21
         assert t.cfg == 10 * t.WM + t.TN or (t.cfg == 23 and (t.WM, t.TN, t.NBUF) == (2, 1, 2))
         assert t.NBUF in (2, 3) and not t.FOLD and not t.NLOAD
-    # FOLD: cfg is not read, the rule is the tile count of 128 x 64 tiles against the CU count
-    fold = entry[entry.index('if (d->ksplit > 1) {'):entry.index('int sel = force;')]
-    assert 'const int tiles = ((M + 127) / 128) * ((N + 63) / 64);' in fold
-    assert 'const bool loaders = tiles <= lvae_cu_count();' in fold
-    (a, b) = re.findall(r'\*rc = loaders \? launch_h2p<([^>]+)>\(d, st\) : launch_h2p<([^>]+)>\(d, st\);', fold)[0]
-    assert (_tile(a), _tile(b)) == (hc.FOLD_LOADERS, hc.FOLD_PLAIN)
-    assert 'force' not in fold and 'sel' not in fold and 'return 1;' in fold
+    assert sorted(hc.H2P_FORCE_CODES) == sorted(t.cfg for t in hc.H2P_TILES) and hc.H2P_DEFAULT in hc.H2P_FORCE_CODES
+    assert len(re.findall(r'constexpr int BM = 64 \* WM, BN = 64 \* TN', h2p)) == 2                 # the kernel and its launcher
+    assert 'const int nq = d.K / 32;' in h2p and hc.H2P_STAGE == 32
     assert (hc.tile_bm(hc.FOLD_LOADERS), hc.tile_bn(hc.FOLD_LOADERS)) == (128, 64) == (hc.tile_bm(hc.FOLD_PLAIN), hc.tile_bn(hc.FOLD_PLAIN))
-    assert '(d->K / 32) % d->ksplit' in fold and '(N & 3)' in fold and '(d->ldo & 3)' in fold
-    assert re.search(r"d->K1 != 0 \|\| d->K0 != d->K \|\| \(d->K & 31\) \|\| d->lda0 != d->K", entry) and 'd->a_gelu' in entry
-
-
-def test_h2_launches_are_the_source(h2):
-    (macro,) = re.findall(r'#define LVAE_H2_LAUNCH\(G, AM\) (.*)', h2)
-    assert macro == '(sel == 1 ? launch_h2<1, G, AM>(d, st) : launch_h2<2, G, AM>(d, st))'
-    assert tuple(int(x) for x in re.findall(r'launch_h2<(\d), G, AM>', macro)) == hc.H2_TNS
-    body = h2[h2.index('#define LVAE_H2_LAUNCH'):h2.index('#undef LVAE_H2_LAUNCH')]
-    uses = re.findall(r'LVAE_H2_LAUNCH\((true|false), (LVAE_A_\w+)\)', body)
+    # gemm_h2.hip: two tile widths in the macro, five uses of it
+    assert len(re.findall(r'launch_h2<', h2)) == 2
+    assert tuple(int(x) for x in re.findall(r'launch_h2<(\d), G, AM>', h2)) == hc.H2_TNS
+    uses = re.findall(r'LVAE_H2_LAUNCH\((true|false), (LVAE_A_\w+)\)', h2)
     assert tuple((int(g == 'true'), AMODE[a]) for g, a in uses) == hc.H2_LAUNCHES and len(set(uses)) == 5
-    assert len(re.findall(r'launch_h2<', h2)) == 2                              # no instantiation outside the macro
-    assert 'if (sel <= 0 || sel > 2) {' in h2                                   # cfg = 1 / 2 force TN, anything else chooses
     # tile: Cfg<WGM = 2, WGN = 2, TM = 2, TN> -> 32 * 2 * 2 rows, 32 * 2 * TN columns
     assert 'using C = Cfg<2, 2, 2, TN, 1, 32>;' in h2 and hc.H2_BM == 32 * 2 * 2 and hc.h2_bn(1) == 32 * 2
     assert 'constexpr int BN = 64 * TN' in h2 and '(d->M + 127) / 128' in h2
-    assert '(d->K & 31)' in h2 and 'if (S > 1 && (d->K % (32 * S))) return 0;' in h2
-    # cfg 0 and 3 go to the narrow-output kernel first
-    assert 'if ((force == 0 || force == 3) && lvae_gemm_h2n_try(d, st, force == 3, rc)) return 1;' in h2
     # the look-ahead the K list is built around: stage 0 stored, k16 tiles 1 and 2 in registers
     assert 'load_set(1, nq > 1 ? 1 : nq - 1);' in h2 and 'load_set(0, nq > 2 ? 2 : nq - 1);' in h2
-
-
-def test_h2n_launches_are_the_source(h2n):
-    (macro,) = re.findall(r'#define LVAE_H2N_LAUNCH\(AM\) (.*)', h2n)
-    assert macro == '(nb == 1 ? launch_h2n<1, AM>(d, st) : nb == 2 ? launch_h2n<2, AM>(d, st) : launch_h2n<3, AM>(d, st))'
-    assert tuple(int(x) for x in re.findall(r'launch_h2n<(\d), AM>', macro)) == hc.H2N_NBS
-    body = h2n[h2n.index('#define LVAE_H2N_LAUNCH'):h2n.index('#undef LVAE_H2N_LAUNCH')]
-    uses = re.findall(r'LVAE_H2N_LAUNCH\((LVAE_A_\w+)\)', body)
-    assert sorted(AMODE[a] for a in uses) == sorted(hc.H2N_AMODES) and len(uses) == 2
+    # gemm_h2n.hip: three block counts in the macro, two uses of it
     assert len(re.findall(r'launch_h2n<', h2n)) == 3
-    assert 'const int nb = (d->N + 31) / 32;' in h2n and f'd->N > {hc.H2N_MAX_N}' in h2n and '(d->K & 15)' in h2n
+    assert tuple(int(x) for x in re.findall(r'launch_h2n<(\d), AM>', h2n)) == hc.H2N_NBS
+    uses = re.findall(r'LVAE_H2N_LAUNCH\((LVAE_A_\w+)\)', h2n)
+    assert sorted(AMODE[a] for a in uses) == sorted(hc.H2N_AMODES) and len(uses) == 2
     assert hc.H2N_MAX_N == 32 * max(hc.H2N_NBS)
     assert f'constexpr int N_CS = {hc.H2N_CHUNK};' in h2n
     (nd,) = re.findall(r'template <int NB> constexpr int n_d\(\) \{ return (.*); \}', h2n)
     assert nd == 'NB <= 2 ? 8 : 4' and hc.H2N_PREFETCH == {nb: (8 if nb <= 2 else 4) for nb in hc.H2N_NBS}
     assert all(hc.H2N_CHUNK % v == 0 for v in hc.H2N_PREFETCH.values())
     assert 'dim3((d->M + 255) / 256), dim3(512)' in h2n and hc.H2N_BM == 256 == 8 * hc.H2N_WAVE_ROWS
-    assert '(d->K / 16) % S' in h2n and 'd->a_h2 || d->a_gelu || d->out_h2' in h2n
 
 
 def test_every_instance_has_a_case():
