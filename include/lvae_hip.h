@@ -776,6 +776,35 @@ int lvae_resample_f32(const float* src, long src_img, long src_plane, long src_r
                       const int* ystart, const float* ywgt, int ytaps, int yspan, const int* xstart, const float* xwgt, int xtaps,
                       int clamp, float* dst, long dst_img, int H, int W, void* stream);
 
+/* ---- Reduced-resolution coding of YUV frames (csrc/resample_yuv.hip): the resampler above fused with the colour conversions of the YUV
+ * entries, so that no full-resolution fp32 RGB image goes to memory.  All B frames of a call share one size and one kind: depth,
+ * subsampling, siting, matrix, range (and chroma, on the way in) are lvae_image_yuv_to_f32's, the plane arrays, row strides (in samples) and
+ * hw -- B (h, w) pairs, each of which must be the call's (h_in, w_in) on the way in, (h_out, w_out) on the way out -- too.  layout:
+ * LVAE_YUV_LAYOUT_PLANAR: y, u, v are the planes; LVAE_YUV_LAYOUT_SEMIPLANAR: u is the interleaved UV plane and v / v_row are not read -- at
+ * depth 8 that is NV12 (4:2:0, centre siting, BT.601 / BT.709), at depth 10 / 12 P010 / P012 / P210 / P212 with the code in the high bits.
+ * The geometry and the seven table arguments are lvae_resample_f32's, with its rules.
+ * The contract is bit equality with the composition of the existing entries:
+ *   lvae_resample_yuv_to_f32 = the layout's lvae_image_yuv*_to_f32 into an (h_in, w_in) canvas, then lvae_resample_f32 with clamp != 0 into
+ *     the canvas (H, W), replicate padding included.  A source pixel is converted once per tile and source row (into LDS), never per tap.
+ *     xspan: the largest number of source columns any 8 consecutive output columns read, max_i(min(xstart[min(i + 7, w_out - 1)] + xtaps,
+ *     w_in) - xstart[i]) (ignored when xtaps == 0): with yspan it sizes a workgroup's tile within the 64 KiB of LDS.
+ *   lvae_resample_f32_to_yuv = lvae_resample_f32 with clamp == 0 into an (h_out, w_out) image, then the layout's lvae_image_f32_to_yuv*: the
+ *     values are clamped where the codes are made (NaN -> 0), left-sited chroma reads the resized column before its own.  src is the
+ *     strided NCHW view of lvae_resample_f32; nothing outside a plane's extent is written.
+ * Whatever the tables, xspan and yspan hold, nothing outside an extent is read or written (wrong pixels, not a fault).  No atomics.  One
+ * launch per 16 frames.
+ * -22 before any HIP call: whatever lvae_resample_f32 and the YUV entry of the layout refuse; an unknown layout or one these parameters do
+ * not have; a frame whose size is not the call's; xspan <= 0 on a filtered horizontal axis; a tile that does not fit.
+ * Added without a change to lvae_abi_version(); they have no launch-plan kind. */
+int lvae_resample_yuv_to_f32(const void* const* y, const void* const* u, const void* const* v, const long* y_row, const long* u_row,
+                             const long* v_row, const int* hw, int B, int depth, int subsampling, int siting, int matrix, int range, int chroma,
+                             int layout, int h_in, int w_in, int h_out, int w_out, const int* ystart, const float* ywgt, int ytaps, int yspan,
+                             const int* xstart, const float* xwgt, int xtaps, int xspan, float* dst, long dst_img, int H, int W, void* stream);
+int lvae_resample_f32_to_yuv(const float* src, long src_img, long src_plane, long src_row, const int* hw, int B, int depth, int subsampling,
+                             int siting, int matrix, int range, int layout, int h_in, int w_in, int h_out, int w_out, const int* ystart,
+                             const float* ywgt, int ytaps, int yspan, const int* xstart, const float* xwgt, int xtaps, void* const* y,
+                             void* const* u, void* const* v, const long* y_row, const long* u_row, const long* v_row, void* stream);
+
 /* ---- rate maps (csrc/rate_map.hip): where an image's estimated bits go.  Deterministic: no atomics, every sum in the order stated, each
  * fp64 operation rounded on its own (no fused multiply-add), so a torch fp64 expression of the definitions gives the same bits and two
  * calls agree.  Every output is overwritten.  Launched by the callers between the ranges of a launch plan: the entries have no

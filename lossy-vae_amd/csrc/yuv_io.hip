@@ -8,6 +8,8 @@
 //
 // The RGB -> YUV half -- constants, matrix, chroma down-sampling of a lane's block, rounding, stores -- lives in yuv_convert.h, which
 // tile_stitch_yuv.hip is written against as well; its functions switch contraction off in their own bodies, so they round alike there.
+// The YUV -> RGB half of ONE pixel -- its rows, its codes, the conversion -- and the frames' descriptors live in yuv_fetch.h, which
+// resample_yuv.hip is written against as well: yuv_to_f32_kernel keeps the 4-pixel loads and calls it for the rest.
 //
 // All are streaming kernels in the mould of image_io.hip: up to YUV_CHUNK frames (plane pairs) per launch, their descriptors in the
 // kernel arguments -- no copy to the device, no scratch.  Samples of more than 8 bits are the low bits of 16-bit words (yuv420p10le ...);
@@ -33,17 +35,13 @@
 
 #include "../../include/lvae_hip.h"
 #include "yuv_convert.h"
+#include "yuv_fetch.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int YUV_CHUNK = 16;                                // frames (plane pairs) per launch
-constexpr int YUV_WG = 256;
-
-// one frame: planes, row strides in samples, valid extent
-struct PlaneDesc { void *y, *u, *v; long yrow, urow, vrow; int h, w; };
-struct PlaneBatch { PlaneDesc d[YUV_CHUNK]; };
+constexpr int YUV_WG = 256;                                  // (YUV_CHUNK frames per launch, their PlaneDesc in a PlaneBatch: yuv_fetch.h)
 
 // 4 consecutive samples: one 4-byte (8-bit) or 8-byte (16-bit) access where the address allows, scalars where not
 // (SP: the code is the word's high bits)
@@ -77,17 +75,15 @@ __global__ __launch_bounds__(YUV_WG) void yuv_to_f32_kernel(PlaneBatch fb, float
     if (idx >= (long)H * quads) return;
     const int y = (int)(idx / quads), x0 = (int)(idx - (long)y * quads) * 4;
     const PlaneDesc im = fb.d[blockIdx.y];
-    const int ch = im.h >> SY, cw = im.w >> SX;
-    auto code = [&](unsigned word) -> unsigned { return (SP ? word >> k.shift : word) & k.mask; };
+    auto code = [&](unsigned word) -> unsigned { return yuv_code<SP>(word, k); };
     const int ys = min(y, im.h - 1);                         // rows below the extent repeat its last row
-    const int cy = ys >> SY;
-    // the second chroma row of the vertical filter: the neighbour on the pixel's side, clamped (nearest, or no vertical subsampling: cy itself)
-    const int cyb = (SY && bilinear) ? min(max(cy + ((ys & 1) ? 1 : -1), 0), ch - 1) : cy;
-    const T* __restrict__ yr = (const T*)im.y + (long)ys * im.yrow;
-    const T* __restrict__ ua = (const T*)im.u + (long)cy * im.urow;
-    const T* __restrict__ ub = (const T*)im.u + (long)cyb * im.urow;
-    const T* __restrict__ va = (const T*)im.v + (long)cy * im.vrow;
-    const T* __restrict__ vb = (const T*)im.v + (long)cyb * im.vrow;
+    const YuvRows<T> rw = yuv_rows<T, SX, SY>(im, ys, bilinear);
+    const int cw = rw.cw;
+    const T* __restrict__ yr = rw.yr;
+    const T* __restrict__ ua = rw.ua;
+    const T* __restrict__ ub = rw.ub;
+    const T* __restrict__ va = rw.va;
+    const T* __restrict__ vb = rw.vb;
     // Y and CU, CV = (SX ? 4 : 1) * (SY ? 4 : 1) times the upsampled chroma, exact
     unsigned Y[4], CU[4], CV[4];
     if (x0 + 3 < im.w) {                                     // 4 valid pixels
@@ -130,47 +126,11 @@ __global__ __launch_bounds__(YUV_WG) void yuv_to_f32_kernel(PlaneBatch fb, float
         }
     } else {                                                 // at or beyond the right edge: every pixel from its nearest valid one
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int xs = min(x0 + i, im.w - 1);
-            Y[i] = code(yr[xs]);
-            if constexpr (!SX) {
-                CU[i] = code(ua[xs]);
-                CV[i] = code(va[xs]);
-            } else {
-                const int cx = (xs >> 1) * CS;               // in samples, as cxb
-                int cxb = cx;                                // the second tap and the weight of the first, in quarters
-                unsigned wa = 4u;
-                if (bilinear) {
-                    if (LEFT) {
-                        if (xs & 1) { cxb = min((xs >> 1) + 1, cw - 1) * CS; wa = 2u; }
-                    } else {
-                        cxb = min(max((xs >> 1) + ((xs & 1) ? 1 : -1), 0), cw - 1) * CS;
-                        wa = 3u;
-                    }
-                }
-                const unsigned wb = 4u - wa;
-                const unsigned pa = code(ua[cx]), pb = code(ua[cxb]), qa = code(va[cx]), qb = code(va[cxb]);
-                if (SY) {
-                    CU[i] = wa * (3u * pa + code(ub[cx])) + wb * (3u * pb + code(ub[cxb]));
-                    CV[i] = wa * (3u * qa + code(vb[cx])) + wb * (3u * qb + code(vb[cxb]));
-                } else {
-                    CU[i] = wa * pa + wb * pb;
-                    CV[i] = wa * qa + wb * qb;
-                }
-            }
-        }
+        for (int i = 0; i < 4; ++i) yuv_pixel_codes<T, SX, SY, LEFT, SP>(rw, min(x0 + i, im.w - 1), bilinear, k, Y[i], CU[i], CV[i]);
     }
-    constexpr float inv = 1.0f / (float)((SX ? 4 : 1) * (SY ? 4 : 1));
     float o3[3][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float yn = __fdiv_rn((float)Y[i] - k.yo, k.ys);
-        const float cb = __fdiv_rn((float)CU[i] * inv - k.co, k.cs);   // C / 16 (/ 4) is exact
-        const float cr = __fdiv_rn((float)CV[i] * inv - k.co, k.cs);
-        o3[0][i] = clamp01(yn + k.a * cr);
-        o3[2][i] = clamp01(yn + k.b * cb);
-        o3[1][i] = clamp01((yn - k.d * cb) - k.e * cr);
-    }
+    for (int i = 0; i < 4; ++i) yuv_codes_to_rgb<SX, SY>(Y[i], CU[i], CV[i], k, o3[0][i], o3[1][i], o3[2][i]);
     float* o = dst + (long)blockIdx.y * dst_img + (long)y * W + x0;
     const long plane = (long)H * W;
     if (vec_ok) {                                            // W % 4 == 0: the quad is whole and 16-byte aligned
@@ -261,34 +221,6 @@ __global__ __launch_bounds__(YUV_WG) void sse_kernel(SseBatch<T> pb, unsigned lo
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
     if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out + blockIdx.y, (unsigned long long)acc);
-}
-
-// The frames of a call as the entries take them: HOST arrays of plane addresses and row strides in samples, `bytes` per sample.  Planar:
-// three planes.  Semi-planar (sp): u is the UV plane, whose rows hold 2 * (w / 2) = w samples; v and v_row are not read.
-struct Planes { const void *const *y, *const *u, *const *v; const long *y_row, *u_row, *v_row; const int* hw; int bytes, sp; };
-
-// The frames' descriptors are valid: planes non-null, extents positive, even where subsampled and inside (H, W), rows that hold their plane's width
-bool frames_ok(const Planes& p, int B, int sx, int sy, int H, int W) {
-    if (!p.y || !p.u || !p.y_row || !p.u_row || !p.hw || (!p.sp && (!p.v || !p.v_row))) return false;
-    for (int b = 0; b < B; ++b) {
-        const int h = p.hw[2 * b], w = p.hw[2 * b + 1];
-        if (h <= 0 || w <= 0 || (h & sy) || (w & sx) || h > H || w > W) return false;
-        if (!p.y[b] || !p.u[b] || p.y_row[b] < w || p.u_row[b] < (p.sp ? w : w >> sx)) return false;
-        if (!p.sp && (!p.v[b] || p.v_row[b] < (w >> sx))) return false;
-    }
-    return true;
-}
-
-// frames b0 .. b0 + n for one launch.  Semi-planar: v = the UV plane one sample on, with the UV row stride: what the SP variants index with column * 2
-PlaneBatch plane_batch(const Planes& p, int b0, int n) {
-    PlaneBatch fb = {};
-    for (int i = 0; i < n; ++i) {
-        const int b = b0 + i;
-        void* u = const_cast<void*>(p.u[b]);
-        fb.d[i] = {const_cast<void*>(p.y[b]), u, p.sp ? (char*)u + p.bytes : const_cast<void*>(p.v[b]), p.y_row[b], p.u_row[b],
-                   p.sp ? p.u_row[b] : p.v_row[b], p.hw[2 * b], p.hw[2 * b + 1]};
-    }
-    return fb;
 }
 
 // Frames -> the fp32 canvas: every check of the three entries' common arguments, then one launch per YUV_CHUNK frames

@@ -159,6 +159,8 @@ SIGNATURES = {
     'lvae_resample_u8_to_f32': (_i, [_vp, _vp] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp, _l, _i, _i, _vp]),
     'lvae_resample_f32_to_u8': (_i, [_vp, _l, _l, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp, _vp, _vp]),
     'lvae_resample_f32': (_i, [_vp, _l, _l, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_i, _vp, _l, _i, _i, _vp]),
+    'lvae_resample_yuv_to_f32': (_i, [_vp] * 7 + [_i] * 8 + [_i] * 4 + [_vp, _vp, _i, _i, _vp, _vp, _i, _i] + [_vp, _l, _i, _i, _vp]),
+    'lvae_resample_f32_to_yuv': (_i, [_vp, _l, _l, _l, _vp] + [_i] * 7 + [_i] * 4 + [_vp, _vp, _i, _i, _vp, _vp, _i] + [_vp] * 7),
     'lvae_gaussian_nll_pos_f32': (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
     'lvae_pixel_nll_pos_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'lvae_rate_map_f32': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _l, _l, _i, _i, _vp]),

@@ -221,7 +221,7 @@ YUV_METRICS = ('psnr', 'ssim', 'ms-ssim')
 
 @torch.no_grad()
 def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, batch=8, lmb=None, depth=8, subsampling='420', siting='center',
-                 layout='planar', metrics=('psnr',), tile=None, overlap=0, **colour):
+                 layout='planar', metrics=('psnr',), tile=None, overlap=0, scale=None, resample='lanczos3', **colour):
     """A raw 8-bit 4:2:0 file coded frame by frame (an image codec as an intra-frame coder) -> dict of means over its frames: 'bpp'
     (8 * len(blob) / (h * w)) and the keys of lvae.metrics.psnr_yuv420 ('mse-y' ... 'psnr-yuv'), computed between the file's bytes and
     decompress_yuv420's.  colour: matrix / range / chroma of compress_yuv420 (matrix and range also go to decompress_yuv420).  Every frame
@@ -238,7 +238,10 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
     and the reconstruction's planes where they lie on the device, with data range 2^depth - 1; one more launch sequence per batch.  The
     other keys keep their values.
     tile = (th, tw), overlap: every frame is coded in tiles (compress_yuv_tiled / decompress_yuv_tiled, `batch` tiles at a time); 'bpp'
-    then counts the whole tiled container.  Only 'psnr' is measured on frames coded in tiles."""
+    then counts the whole tiled container.  Only 'psnr' is measured on frames coded in tiles.
+    scale=S: every frame is coded at reduced resolution (compress_yuv_scaled(scale=S, filter=resample) / decompress_yuv_scaled); 'bpp'
+    counts the whole scaled container against the ORIGINAL pixel count, and every metric is taken on the original-size frames.  ValueError
+    for scale together with tile."""
     from .metrics import PSNR_YUV_KEYS, PSNR_YUV_KEYS2, ms_ssim_yuv, psnr_yuv, psnr_yuv420, ssim_yuv
     from .utils.yuv import FORMATS, FrameFormat
     if layout not in ('planar', 'semiplanar'):
@@ -265,6 +268,11 @@ def yuv_evaluate(model, yuv_path, width, height, fmt='i420', max_frames=None, ba
     compress = lambda chunk, **enc: model.compress_yuv(chunk, siting=siting, **enc)
     decompress = lambda blobs: model.decompress_yuv(blobs, **how)
     measure, keys = (psnr_yuv420, PSNR_YUV_KEYS) if fmt.layout in FORMATS else (psnr_yuv, PSNR_YUV_KEYS2)      # their keys differ
+    if scale is not None:
+        if tile is not None:
+            raise ValueError('yuv_evaluate: scale and tile may not be combined (scaled and tiled coding are separate)')
+        compress = lambda chunk, **enc: model.compress_yuv_scaled(chunk, scale=scale, filter=resample, siting=siting, **enc)
+        decompress = lambda blobs: model.decompress_yuv_scaled(blobs, **how)
     if tile is not None:
         if set(metrics) - {'psnr'}:
             raise ValueError(f"yuv_evaluate: frames coded in tiles are measured by 'psnr' only, got metrics={tuple(metrics)}")

@@ -692,7 +692,8 @@ class CodecBase(nn.Module):
 
     @torch.no_grad()
     def compress_yuv_sequence(self, frames_or_path, width=None, height=None, depth=8, subsampling='420', layout='planar', siting='center',
-                              matrix='bt709', range='limited', chroma='bilinear', frames=None, lmb=None, max_batch=8, tile=None, overlap=0):
+                              matrix='bt709', range='limited', chroma='bilinear', frames=None, lmb=None, max_batch=8, tile=None, overlap=0,
+                              scale=None, size=None, filter='lanczos3'):
         """A sequence of frames -> the bytes of one self-describing container (utils.yuvseq.pack_sequence).  frames_or_path: a list of
         frames of ONE kind and size -- utils.yuv.YuvFrame, YuvSpFrame or Yuv420Frame; depth, subsampling and layout are then the frames' --
         or the path of a raw file of `width` x `height` frames of `depth`, `subsampling` and `layout` ('planar' | 'semiplanar' | 'i420' |
@@ -702,8 +703,18 @@ class CodecBase(nn.Module):
         matrix, range, chroma, the layout, this model's registry name and its GEMM precision: decompress_yuv_sequence needs nothing else.
         tile = (th, tw), overlap: every frame is coded in tiles and its entry is compress_yuv_tiled(frame k, tile, overlap, ...), a tiled
         container (the tiles of ONE frame then share a batch, `max_batch` at a time); the header does not change -- a frame's entry is
-        opaque bytes behind the length table -- and with tile=None every byte is as before."""
-        from ..utils import yuv, yuvseq
+        opaque bytes behind the length table -- and with tile=None every byte is as before.
+        scale or size = (h, w), filter: every frame is coded at reduced resolution and its entry is compress_yuv_scaled([frame k], ...)[0],
+        a scaled container; again the header does not change, and with neither every byte is as before.  ValueError: both of them, or
+        either together with tile."""
+        from ..utils import resample, yuv, yuvseq
+        scaled = scale is not None or size is not None
+        if scaled:
+            if tile is not None:
+                raise ValueError('compress_yuv_sequence: scale / size and tile may not be combined (scaled and tiled coding are separate)')
+            if scale is not None and size is not None:
+                raise ValueError('compress_yuv_sequence: give one of scale and size, not both')
+            resample._filter(filter)
         if lmb is not None and not self.variable_rate:
             raise ValueError(f'{type(self).__name__} is a fixed-rate model: it takes no lmb')
         if isinstance(frames_or_path, (str, os.PathLike)):
@@ -711,10 +722,10 @@ class CodecBase(nn.Module):
                 raise ValueError('compress_yuv_sequence: a raw file needs width and height')
             fmt = yuv.FrameFormat(layout, depth, subsampling, siting, matrix)
             path, limit = frames_or_path, None if frames is None else int(frames)
-            per, size = fmt.frame_bytes(width, height), os.path.getsize(path)
-            if size == 0 or size % per:
-                raise ValueError(f'compress_yuv_sequence: {path} holds {size} bytes, not a whole number of {width}x{height} frames of {per} bytes')
-            total = size // per if limit is None else min(limit, size // per)
+            per, nbytes = fmt.frame_bytes(width, height), os.path.getsize(path)
+            if nbytes == 0 or nbytes % per:
+                raise ValueError(f'compress_yuv_sequence: {path} holds {nbytes} bytes, not a whole number of {width}x{height} frames of {per} bytes')
+            total = nbytes // per if limit is None else min(limit, nbytes // per)
             source = lambda start, n: fmt.read(path, width, height, frames=min(n, total - start), start=start) if start < total else []
         else:
             source, fmt = yuv.FrameFormat.shared(frames_or_path, 'compress_yuv_sequence')
@@ -723,6 +734,10 @@ class CodecBase(nn.Module):
                 raise ValueError('compress_yuv_sequence: the frames of a sequence share one kind, one plane layout and one size')
             yuvseq.check_layout(*fmt, siting, matrix)
         compress = lambda chunk, **kw: self.compress_yuv(chunk, matrix=matrix, range=range, chroma=chroma, siting=siting, **kw)
+        if scaled:
+            resample.scaled_size(height, width, scale=scale, size=size)
+            compress = lambda chunk, **kw: self.compress_yuv_scaled(chunk, scale=scale, size=size, filter=filter, matrix=matrix, range=range,
+                                                                    chroma=chroma, siting=siting, **kw)
         if tile is not None:
             self._tile_args(tile, overlap)
 
@@ -737,10 +752,12 @@ class CodecBase(nn.Module):
 
     def yuv_sequence_info(self, blob):
         """utils.yuvseq.yuv_sequence_info (header parsing only, no GPU) plus 'lmb': the frames' lambdas from their blobs' own headers on
-        variable-rate models (as tiled_info), else None; a frame that was coded in tiles has tiled_info's (rows, cols) nested list."""
-        from ..utils import tiling, yuvseq
+        variable-rate models (as tiled_info), else None; a frame that was coded in tiles has tiled_info's (rows, cols) nested list, one
+        coded at reduced resolution the lambda of its payload (scaled_info)."""
+        from ..utils import resample, tiling, yuvseq
         info = yuvseq.yuv_sequence_info(blob)
-        lmb_of = lambda fb: self.tiled_info(fb)['lmb'] if tiling.is_tiled(fb) else self._blob_lmb(fb)
+        lmb_of = lambda fb: (self.tiled_info(fb)['lmb'] if tiling.is_tiled(fb) else self.scaled_info(fb)['lmb'] if resample.is_scaled(fb)
+                             else self._blob_lmb(fb))
         info['lmb'] = [lmb_of(yuvseq.frame_blob(blob, info, k)) for k in range(info['frames'])] if self.variable_rate else None
         return info
 
@@ -753,8 +770,9 @@ class CodecBase(nn.Module):
         return their number.  ValueError: a malformed container (utils.yuvseq.yuv_sequence_info), a header whose model name or GEMM
         precision is not this model's (both names are in the message; set_gemm_precision selects the arithmetic), a layout the header's
         parameters do not have.  A frame entry that is a tiled container (compress_yuv_sequence(tile=...)) is recognised by its magic and
-        decoded by decompress_yuv_tiled."""
-        from ..utils import tiling, yuv, yuvseq
+        decoded by decompress_yuv_tiled; one that is a scaled container (compress_yuv_sequence(scale=...)) likewise, by
+        decompress_yuv_scaled, at the sequence's frame size."""
+        from ..utils import resample, tiling, yuv, yuvseq
         info = yuvseq.yuv_sequence_info(blob)
         if info['model'] != self._registry_name:
             raise ValueError(f"decompress_yuv_sequence: the sequence was written by model {info['model']!r}, this model is {self._registry_name!r}")
@@ -769,9 +787,11 @@ class CodecBase(nn.Module):
         idxs, step, out = yuvseq.frame_indexes(info, frames), max(1, int(max_batch)), []
         for o in range(0, len(idxs), step):
             entries = [yuvseq.frame_blob(blob, info, k) for k in idxs[o:o + step]]
-            whole = [b for b in entries if not tiling.is_tiled(b)]
-            got = iter(decode(whole) if whole else [])
-            got = [decode_tiled(b) if tiling.is_tiled(b) else next(got) for b in entries]       # a frame coded in tiles: a tiled container
+            whole = [b for b in entries if not tiling.is_tiled(b) and not resample.is_scaled(b)]
+            small = [b for b in entries if resample.is_scaled(b)]
+            got, got_small = iter(decode(whole) if whole else []), iter(self.decompress_yuv_scaled(small, **how) if small else [])
+            # a frame coded in tiles: a tiled container; one coded at reduced resolution: a scaled container
+            got = [decode_tiled(b) if tiling.is_tiled(b) else next(got_small) if resample.is_scaled(b) else next(got) for b in entries]
             for f in got:
                 if f.size != (info['height'], info['width']):
                     raise ValueError(f"YUV sequence container: a frame holds {f.size[1]} x {f.size[0]} pixels, the header says {info['width']} x {info['height']}")
@@ -1153,6 +1173,79 @@ class CodecBase(nn.Module):
                 got = _resample_f32([x[r, :, :ch, :cw] for r, _ in rows], target, filt, False, out)
                 for k, (_, i) in enumerate(rows):
                     result[i] = got[k] if out == 'u8' else got[k:k + 1]
+        return result
+
+    # ---- YUV frames at reduced resolution: the two families above as one (csrc/resample_yuv.hip, utils.yuv.ScaledYuvBatch /
+    # from_rgb01_scaled).  The container is the unchanged `LVRS` one, so scaled_info reads it as it is.
+    @torch.no_grad()
+    def compress_yuv_scaled(self, frames, scale=None, size=None, filter='lanczos3', lmb=None, matrix='bt709', range='limited', chroma='bilinear',
+                            siting='center'):
+        """compress_scaled for YUV frames: a list of frames of ONE kind and size (anything compress_yuv takes: utils.yuv.YuvFrame,
+        YuvSpFrame or Yuv420Frame, on the CPU or the model's device) -> list of bytes, one scaled container (utils.resample.pack_scaled)
+        per frame.  scale / size / filter / lmb: as in compress_scaled.  The planes go to the device as their file holds them and
+        lvae_resample_yuv_to_f32 converts and resamples them into each pipeline group's plan input -- no full-resolution RGB image exists
+        anywhere.  The payload is the model's own blob: that of the float path on
+        utils.image.resize(utils.yuv.to_rgb01_any(frame), coded size, clamp=True), replicate-padded; with scale=1.0 it is compress_yuv's
+        bytes.  The colour parameters, depth, subsampling and siting are NOT stored, as in compress_yuv: decompress_yuv_scaled has to be
+        given them (compress_yuv_sequence(scale=...) stores them)."""
+        from ..utils import resample
+        from ..utils.yuv import FrameFormat
+        resample._filter(filter)
+        frames, fmt = FrameFormat.shared(frames, 'compress_yuv_scaled')
+        h, w = frames[0].size
+        coded = resample.scaled_size(h, w, scale=scale, size=size)
+        batch = fmt.batch(frames, self.max_stride, self._dummy.device, matrix, range, chroma, siting, coded=coded, filter=filter)
+        return [resample.pack_scaled(filter, (h, w), coded, blob) for blob in self._compress_byte_batch(batch, lmb, 'compress_yuv_scaled')]
+
+    @torch.no_grad()
+    def decompress_yuv_scaled(self, blobs, depth=8, subsampling='420', siting='center', matrix='bt709', range='limited', layout='planar',
+                              size=None):
+        """compress_yuv_scaled (or compress_scaled) containers -> frames of the kind decompress_yuv's arguments name, on the model's device.
+        size: None = each frame at its ORIGINAL size; 'coded' = the coded frame, no resampling (decompress_yuv of the payload); (h, w) = a
+        preview at that size.  Payloads of one latent shape decode as one batch, and lvae_resample_f32_to_yuv resamples the decoder's
+        padded batch, where it lies, straight into the planes: it equals
+        utils.yuv.from_rgb01_any(decompress_scaled(blobs, out='f32', size=size), ...) plane by plane, with no fp32 image in between.
+        ValueError: a malformed container, a payload whose size is not the header's coded size, a target size that does not fit the
+        subsampling (the message names both), a layout these parameters do not have."""
+        from ..utils import resample
+        from ..utils.yuv import _check2, _extent_ok, check_layout, from_rgb01_any, from_rgb01_scaled
+        _check2(range=range)
+        check_layout(layout, depth, subsampling, siting, matrix)
+        if size is not None and size != 'coded':
+            size = tuple(int(v) for v in size)
+            if len(size) != 2:
+                raise ValueError(f"size is None, 'coded' or (h, w), got {size!r}")
+        how = dict(depth=depth, subsampling=subsampling, siting=siting, matrix=matrix, range=range, layout=layout)
+        infos, bodies, groups = [], [], {}
+        for i, b in enumerate(blobs):
+            info, payload = resample.unpack_scaled(b)
+            body, coded, key = self._unpack_blob(payload)
+            if tuple(coded) != info['coded']:
+                raise ValueError(f"scaled container {i}: the payload holds a {tuple(coded)} image, the header says {info['coded']}")
+            target = info['coded'] if size == 'coded' else info['size'] if size is None else size
+            if not _extent_ok(target[0], target[1], subsampling):
+                raise ValueError(f'decompress_yuv_scaled: container {i} is asked for a {target[0]} x {target[1]} frame, which does not fit '
+                                 f'subsampling {subsampling}')
+            if size != 'coded':
+                resample.check_ratio(info['coded'][0], target[0])
+                resample.check_ratio(info['coded'][1], target[1])
+            infos.append(dict(info, target=tuple(target)))
+            bodies.append(body)
+            groups.setdefault(key, []).append(i)           # as _decompress_blobs: payloads that share a latent shape are one batch
+        result = [None] * len(blobs)
+        for idxs in groups.values():
+            x = self.decompress_batch([bodies[i] for i in idxs])
+            if size == 'coded':
+                for i, item in zip(idxs, from_rgb01_any(x, [infos[i]['coded'] for i in idxs], **how)):
+                    result[i] = item
+                continue
+            calls = {}                                     # one launch per (coded size, target size, filter) of the batch
+            for r, i in enumerate(idxs):
+                calls.setdefault((infos[i]['coded'], infos[i]['target'], infos[i]['filter']), []).append((r, i))
+            for ((ch, cw), target, filt), rows in calls.items():
+                got = from_rgb01_scaled([x[r, :, :ch, :cw] for r, _ in rows], target, filt, **how)
+                for k, (_, i) in enumerate(rows):
+                    result[i] = got[k]
         return result
 
     def compress_file_scaled(self, img_path, out_path, scale=None, size=None, filter='lanczos3', lmb=None):

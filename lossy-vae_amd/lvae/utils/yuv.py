@@ -25,6 +25,9 @@ What the three frame classes differ in is one value, `FrameFormat(layout, depth,
 frames of its kind, `to_rgb01_any` / `from_rgb01_any` take every kind through it (`to_rgb01` / `from_rgb01` forward to them), and which
 layout exists at which depth, subsampling, siting and matrix is the rule of utils.yuvseq.check_layout, stated nowhere else.
 
+`to_rgb01_scaled` / `from_rgb01_scaled` / `ScaledYuvBatch` are the two conversions with the resampler of utils/resample.py between them and
+the planes, each as ONE kernel (csrc/resample_yuv.hip) with the bits of the composition: frames coded at reduced resolution.
+
 `stitch_tiles_yuv` (the end of the file) writes a frame, or a window of one, straight from the decoded tiles of a tiled image
 (csrc/tile_stitch_yuv.hip): utils.image.stitch_tiles and from_rgb01_any as one kernel, with their bits.
 """
@@ -385,10 +388,13 @@ class FrameFormat(namedtuple('FrameFormat', 'layout depth subsampling')):
         cols = slice(x, x + tw) if self.layout == 'semiplanar' else slice(x >> sx, (x + tw) >> sx)
         return self.frame(frame.y[y:y + th, x:x + tw], *(p[rows, cols] for p in frame.planes()[1:]), scan=False)
 
-    def batch(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center'):
+    def batch(self, frames, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center', coded=None, filter='lanczos3'):
         """The _Batch of frames of this format that the codecs hand to compress_batch: Yuv420Batch (which takes no siting: ValueError
-        unless it is 'center'), YuvBatch or YuvSpBatch."""
+        unless it is 'center'), YuvBatch or YuvSpBatch.  coded = (h, w): a ScaledYuvBatch instead, whose `fill` resamples the frames
+        (of ONE size) to that size with `filter` on the way."""
         check_layout(*self, siting, matrix)
+        if coded is not None:
+            return ScaledYuvBatch(self, frames, coded, filter, div, device, matrix, range, chroma, siting)
         if self.layout in FORMATS:
             return Yuv420Batch(frames, div, device, matrix, range, chroma)
         return (YuvSpBatch if self.layout == 'semiplanar' else YuvBatch)(frames, div, device, matrix, range, chroma, siting)
@@ -727,6 +733,159 @@ def from_rgb01_any(x, sizes=None, depth=8, subsampling='420', siting='center', m
         return _from_rgb(xs, outs, _fmt_names(outs), 'image_f32_to_yuv420', (FORMATS.index(layout), MATRICES.index(matrix), RANGES.index(range)))
     codes = (depth, SUBSAMPLINGS.index(subsampling), SITINGS.index(siting), MATRICES2.index(matrix), RANGES.index(range))
     return _from_rgb(xs, outs, (YuvSpBatch if sp else YuvBatch).names, 'image_f32_to_yuvsp' if sp else 'image_f32_to_yuv', codes)
+
+
+# ----------------------------------------------------------------------------------------------- frames at reduced resolution
+# csrc/resample_yuv.hip: the resampler of utils/resample.py fused with the two conversions above.  The DEFINITION is the composition in
+# the RGB domain -- resize(to_rgb01_any(frames), size, clamp=True) on the way in, from_rgb01_any(resize(x, size)) on the way out -- and the
+# kernels give its bits without the full-resolution fp32 image it puts into memory.
+_XSPANS = {}
+
+
+def _scaled_tables(src, dst, filter, device):
+    """The table arguments of lvae_resample_yuv_to_f32 / lvae_resample_f32_to_yuv for (h, w) src -> dst: the seven of lvae_resample_*, then
+    `xspan`, the largest number of source columns 8 consecutive output columns read (0 for an axis that keeps its size)."""
+    from . import resample
+    from .image import _tables
+    tabs = _tables(*src, *dst, filter, device)
+    key = (int(src[1]), int(dst[1]), filter)
+    if key not in _XSPANS:
+        start, wgt = resample.axis_table(*key)
+        _XSPANS[key] = 0 if key[0] == key[1] else resample.tile_span(start, wgt.shape[1], key[0], rows=8)
+    return tabs, _XSPANS[key]
+
+
+def _kind_codes(fmt, siting, matrix, range):
+    """depth, subsampling, siting, matrix, range as the native entries take them, and the names of a frame's planes with its layout code."""
+    codes = (fmt.depth, SUBSAMPLINGS.index(fmt.subsampling), SITINGS.index(siting), MATRICES2.index(matrix), RANGES.index(range))
+    return codes, (('y', 'uv', None) if fmt.interleaved else ('y', 'u', 'v')), LAYOUTS.index('semiplanar' if fmt.interleaved else 'planar')
+
+
+def _one_kind(fs, who):
+    fmt, size = FrameFormat.of(fs[0]), fs[0].size
+    if any(FrameFormat.of(f) != fmt or f.size != size for f in fs):
+        raise ValueError(f'{who}: the frames of one scaled call share one kind, one plane layout and one size')
+    return size
+
+
+class ScaledYuvBatch(_Batch):
+    """B frames of ONE kind and size on one device, coded at `coded` = (h, w): what CodecBase.compress_yuv_scaled hands to compress_batch
+    as `u8=`, the utils.image.ScaledU8Batch of YUV frames.  `sizes` are the coded sizes (what the models' containers record), `shape` the
+    coded canvas; `fill` converts and resamples frames start .. start + n straight into an encode plan's input -- `filter`, clamped to
+    [0, 1], replicate-padded -- with one launch (lvae_resample_yuv_to_f32).  With coded == the frames' size that is the plain
+    conversion's result, bit for bit.  canvas: the (H, W) of `shape` instead of the coded size rounded up to multiples of `div`."""
+
+    def __init__(self, fmt, frames, coded, filter, div, device, matrix='bt709', range='limited', chroma='bilinear', siting='center', canvas=None):
+        from . import resample
+        fs = list(frames)
+        check_layout(*fmt, siting, matrix)
+        _check2(range=range, chroma=chroma)
+        resample._filter(filter)
+        if not fs:
+            raise ValueError('no frames')
+        self.src_size = _one_kind(fs, 'ScaledYuvBatch')
+        if FrameFormat.of(fs[0]) != fmt:
+            raise ValueError(f'ScaledYuvBatch: the frames are {tuple(FrameFormat.of(fs[0]))}, not {tuple(fmt)}')
+        coded = (int(coded[0]), int(coded[1]))
+        resample.check_ratio(self.src_size[0], coded[0])
+        resample.check_ratio(self.src_size[1], coded[1])
+        super().__init__(fs, 1, device)
+        self.fmt, self.filter, self.matrix, self.range, self.chroma, self.siting = fmt, filter, matrix, range, chroma, siting
+        self.sizes = [coded] * len(fs)
+        self.shape = (len(fs), 3) + (_canvas(self.sizes, div) if canvas is None else (int(canvas[0]), int(canvas[1])))
+        if self.shape[2] < coded[0] or self.shape[3] < coded[1]:
+            raise ValueError(f'ScaledYuvBatch: canvas {self.shape[2:]} is below the coded size {coded}')
+        self._tabs, self._xspan = _scaled_tables(self.src_size, coded, filter, self.device)
+
+    def fill(self, dst, start=0, n=None):
+        from .. import _native
+        n = len(self.frames) - start if n is None else n
+        _, _, H, W = self.shape
+        assert dst.dtype == torch.float32 and dst.device == self.device and tuple(dst.shape) == (n, 3, H, W) and dst[0].is_contiguous()
+        codes, names, layout = _kind_codes(self.fmt, self.siting, self.matrix, self.range)
+        ptrs, rows, hw, keep = _plane_args(self.frames[start:start + n], names)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().lvae_resample_yuv_to_f32(*ptrs, *rows, hw, n, *codes, CHROMA.index(self.chroma), layout, *self.src_size,
+                                                                 *self.sizes[0], *self._tabs, self._xspan, dst.data_ptr(),
+                                                                 dst.stride(0) if n > 1 else 3 * H * W, H, W, _stream(self.device)),
+                          'resample_yuv_to_f32')
+        del keep
+
+
+def to_rgb01_scaled(frames, size, filter='lanczos3', canvas=None, matrix='bt709', range='limited', chroma='bilinear', siting='center',
+                    device=None):
+    """Frames of ONE kind and size (anything to_rgb01_any takes) -> a (B, 3, H, W) fp32 tensor: every frame converted to RGB in [0, 1]
+    and resized to size = (h, w) with the resampler of utils/resample.py (`filter`), clamped to [0, 1] and replicate-padded to
+    canvas = (H, W) >= size (default: size).  The definition is utils.image.resize(to_rgb01_any(frames)[0], size, filter, clamp=True).
+    Frames on a GPU (or `device`): one launch of lvae_resample_yuv_to_f32 per 16 frames gives those bits, and no full-resolution RGB
+    image is made.  CPU frames with device=None take the composition of the two CPU paths (the defining expression of the conversion,
+    then resample.resize_reference, fp64 cast to fp32).  ValueError: frames of different kinds or sizes, an unknown filter, a ratio
+    outside [1/8, 8] on an axis, a canvas below size."""
+    from .image import resize
+    fs, fmt = FrameFormat.shared(frames, 'to_rgb01_scaled')
+    _one_kind(fs, 'to_rgb01_scaled')
+    size = (int(size[0]), int(size[1]))
+    H, W = size if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if H < size[0] or W < size[1]:
+        raise ValueError(f'to_rgb01_scaled: canvas {(H, W)} is below size {size}')
+    if device is None and all(f.device.type == 'cpu' for f in fs):
+        x = resize(to_rgb01_any(fs, 1, None, matrix, range, chroma, siting)[0], size, filter, clamp=True)
+        return F.pad(x, (0, W - size[1], 0, H - size[0]), mode='replicate') if (H, W) != size else x
+    device = next(f.device for f in fs if f.device.type != 'cpu') if device is None else device
+    b = ScaledYuvBatch(fmt, fs, size, filter, 1, device, matrix, range, chroma, siting, canvas=(H, W))
+    out = torch.empty(b.shape, dtype=torch.float32, device=b.device)
+    b.fill(out)
+    return out
+
+
+def from_rgb01_scaled(xs, size, filter='lanczos3', depth=8, subsampling='420', siting='center', matrix='bt709', range='limited',
+                      layout='planar', outs=None):
+    """The way out: fp32 RGB images of ONE size -- a (B, 3, h, w) tensor or a list of (1, 3, h, w) / (3, h, w) views (crops of a decoder's
+    padded batch are read in place) -> a list of frames of size = (h, w) on the same device, of the kind from_rgb01_any's arguments
+    name.  The definition is from_rgb01_any(utils.image.resize(x, size, filter), ...): the resized values are not clamped before the
+    conversion clamps them.  Device tensors: one launch of lvae_resample_f32_to_yuv per 16 images gives those bits with no fp32 image in
+    between; outs: frames of that kind and size on the images' device to write instead of new ones -- their planes may be views of larger
+    tensors (unit column stride), and nothing outside them is written.  CPU tensors take that composition of the two CPU paths.  ValueError: images of different sizes, a size that does not fit
+    the subsampling (it is named), a layout these parameters do not have, an unknown filter, a ratio outside [1/8, 8]."""
+    from .. import _native
+    from . import resample
+    from .image import resize
+    from .views import strided_batch
+    who = 'from_rgb01_scaled'
+    _check2(range=range)
+    resample._filter(filter)
+    fmt = FrameFormat(layout, depth, subsampling, siting, matrix)
+    vs = _rgb_items(xs, None, who)
+    h_in, w_in = int(vs[0].shape[1]), int(vs[0].shape[2])
+    if any(tuple(v.shape) != (3, h_in, w_in) for v in vs):
+        raise ValueError(f'{who}: the images of one call share one size')
+    h, w = int(size[0]), int(size[1])
+    if not _extent_ok(h, w, subsampling):
+        raise ValueError(f'{who}: size {(h, w)} does not fit subsampling {subsampling}')
+    resample.check_ratio(h_in, h)
+    resample.check_ratio(w_in, w)
+    device = vs[0].device
+    if device.type == 'cpu':
+        x = resize(torch.stack([v.to(torch.float32) for v in vs]), (h, w), filter)
+        return from_rgb01_any(x, None, depth, subsampling, siting, matrix, range, layout)
+    B = len(vs)
+    if outs is None:
+        outs = [fmt.new(h, w, device) for _ in vs]
+    elif len(outs) != B or any(FrameFormat.of(f) != fmt or f.size != (h, w) or f.device != device for f in outs):
+        raise ValueError(f'{who}: outs holds one frame of {h} x {w} per image, on {device}, with the layout, depth and subsampling asked for')
+    elif any(p.stride(-1) != 1 or (p.dim() == 3 and p.stride(1) != 2) for f in outs for p in f.planes()):
+        raise ValueError(f'{who}: the planes of outs have unit column stride')
+    codes, names, lay = _kind_codes(fmt, siting, matrix, range)
+    tabs, _ = _scaled_tables((h_in, w_in), (h, w), filter, device)
+    with torch.cuda.device(device):
+        keep, px, (s_img, s_plane, s_row) = strided_batch(vs, h_in, w_in, device)
+        if B > 1 and s_img < 2 * s_plane + (h_in - 1) * s_row + w_in:      # views that overlap as a batch are packed instead
+            keep, px, (s_img, s_plane, s_row) = strided_batch([v.clone() for v in vs], h_in, w_in, device)
+        ptrs, rows, hw, _ = _plane_args(outs, names)
+        _native.check(_native.lib().lvae_resample_f32_to_yuv(px, s_img if B > 1 else 3 * s_plane, s_plane, s_row, hw, B, *codes, lay, h_in, w_in,
+                                                             h, w, *tabs, *ptrs, *rows, _stream(device)), 'resample_f32_to_yuv')
+    del keep
+    return outs
 
 
 # ----------------------------------------------------------------------------------------------- tiled images straight into YUV planes

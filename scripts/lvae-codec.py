@@ -16,6 +16,8 @@ decompress_to_files: the bytes of an image are uploaded as they are, a reconstru
     python scripts/lvae-codec.py encode-yuv IN.yuv OUT.lvys --size 1920 1080 --container [--layout p010] [--siting left] [--matrix bt2020]
     python scripts/lvae-codec.py decode-yuv IN.lvys OUT.yuv [--layout p010]          # no colour flags: the container holds them
     python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 3840 2160 --depth 10 --tile 512 768 --overlap 32 [--container]   # frames in tiles
+    python scripts/lvae-codec.py encode-yuv IN.yuv BITS/ --size 3840 2160 --depth 10 --scale 0.5 [--filter bicubic] [--container]   # frames at reduced resolution
+    python scripts/lvae-codec.py decode-yuv BITS/ OUT.yuv --depth 10 [--preview 540 960]   # scaled frames: recognised by their magic
     python scripts/lvae-codec.py eval-yuv IN.yuv --size 1920 1080 [--depth 10 | --layout p010 ...] [--ssim] [--ms-ssim]   # bpp, PSNR-YUV, SSIM as JSON
     python scripts/lvae-codec.py ratemap IMAGES/ MAPS/ -m qarv_base [--lmb 256]      # where the bits go: <stem>.npy + <stem>.png per image
 
@@ -38,6 +40,9 @@ folder; decode-yuv recognises it by its magic, takes every parameter from its he
 / --format asks for another.  encode-yuv --tile TH TW [--overlap OV] codes every frame in tiles (CodecBase.compress_yuv_tiled: one tiled
 container per frame, as a .bits file or as the frame's entry of the --container file; the overlap is even where the chroma is
 subsampled); decode-yuv recognises such frames by their magic and writes the planes straight from the blend of the tiles.
+encode-yuv --scale S [--filter F] codes every frame at S times its size (CodecBase.compress_yuv_scaled: one scaled container per frame, as
+a .bits file or as the frame's entry of the --container file; not together with --tile); decode-yuv recognises such frames by their magic
+and writes them at their original size, or with --preview H W at that size.
 eval-yuv codes the frames of a raw file as encode-yuv would (the same --size / --format / --depth / --subsampling / --siting / --layout /
 colour flags, --frames, --batch, --lmb; --synthetic N writes seeded frames first), decodes them and prints lvae.evaluation.yuv_evaluate's
 dict of means as one JSON line: bpp and the PSNR keys, with --ssim also ssim-y / ssim-u / ssim-v, with --ms-ssim also ms-ssim-y (frames
@@ -138,20 +143,38 @@ def _decode_kw(fmt, colour):
     return dict(fmt._asdict(), **{k: v for k, v in colour.items() if k != 'chroma'})
 
 
-def encode_yuv_container(model, src, dst, size, fmt, frames, lmb, batch, colour, tile=None, overlap=0):
+def encode_yuv_container(model, src, dst, size, fmt, frames, lmb, batch, colour, tile=None, overlap=0, scale=None, filt='lanczos3'):
     blob = model.compress_yuv_sequence(src, size[0], size[1], frames=frames, lmb=lmb, max_batch=batch, tile=tile, overlap=overlap,
-                                       **fmt._asdict(), **colour)
+                                       scale=scale, filter=filt, **fmt._asdict(), **colour)
     Path(dst).write_bytes(blob)
     print(f'encoded {model.yuv_sequence_info(blob)["frames"]} frames -> {len(blob)} bytes')
 
 
-def decode_yuv_container(model, src, dst, batch, layout=None):
-    n = model.decompress_yuv_sequence(Path(src).read_bytes(), layout=layout, out_path=dst, max_batch=batch)
+def decode_yuv_container(model, src, dst, batch, layout=None, preview=None):
+    blob = Path(src).read_bytes()
+    if preview is not None:                                  # every frame at the preview size: the entries must be scaled containers
+        from lvae.utils.resample import is_scaled
+        from lvae.utils.yuv import write_frames
+        from lvae.utils.yuvseq import unpack_sequence
+        info, entries = unpack_sequence(blob)
+        if not all(is_scaled(b) for b in entries):
+            raise SystemExit('--preview: the sequence was not coded with --scale')
+        how = {k: info[k] for k in ('depth', 'subsampling', 'siting', 'matrix', 'range')}
+        how['layout'] = info['layout'] if layout is None else layout
+        for o in range(0, len(entries), batch):
+            write_frames(model.decompress_yuv_scaled(entries[o:o + batch], size=tuple(preview), **how), dst, append=o > 0)
+        print(f'decoded {len(entries)} frames at {preview[0]}x{preview[1]}')
+        return
+    n = model.decompress_yuv_sequence(blob, layout=layout, out_path=dst, max_batch=batch)
     print(f'decoded {n} frames')
 
 
-def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, tile=None, overlap=0):
+def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, tile=None, overlap=0, scale=None, filt='lanczos3'):
     fs, compress = fmt.read(src, size[0], size[1], frames=frames), model.compress_yuv
+    if scale is not None:                                    # a scaled container per frame
+        if tile is not None:
+            raise SystemExit('encode-yuv: --scale and --tile may not be combined')
+        compress = lambda chunk, **kw: model.compress_yuv_scaled(chunk, scale=scale, filter=filt, **kw)
     if tile is not None:                                     # every frame on its own, as a tiled container, its tiles --batch at a time
         compress = lambda chunk, **kw: [model.compress_yuv_tiled(f, tile=tile, overlap=overlap, max_batch=batch, **kw) for f in chunk]
     total = 0
@@ -163,13 +186,18 @@ def encode_yuv(model, src, dst, size, fmt, frames, lmb, batch, colour, tile=None
     print(f'encoded {len(fs)} frames -> {total} bytes')
 
 
-def decode_yuv(model, src, dst, fmt, batch, colour):
+def decode_yuv(model, src, dst, fmt, batch, colour, preview=None):
+    from lvae.utils.resample import MAGIC as SCALED_MAGIC
     from lvae.utils.tiling import MAGIC as TILED_MAGIC
     from lvae.utils.yuv import write_frames
     paths, how = sorted(Path(src).glob('*.bits')), _decode_kw(fmt, colour)
     for o in range(0, len(paths), batch):
         blobs = [p.read_bytes() for p in paths[o:o + batch]]
-        if all(b[:4] == TILED_MAGIC for b in blobs):         # encode-yuv --tile wrote them: one tiled container per frame
+        if preview is not None and not all(b[:4] == SCALED_MAGIC for b in blobs):
+            raise SystemExit('--preview: the frames were not coded with --scale')
+        if all(b[:4] == SCALED_MAGIC for b in blobs):        # encode-yuv --scale wrote them: one scaled container per frame
+            got = model.decompress_yuv_scaled(blobs, size=None if preview is None else tuple(preview), **how)
+        elif all(b[:4] == TILED_MAGIC for b in blobs):       # encode-yuv --tile wrote them: one tiled container per frame
             got = [model.decompress_yuv_tiled(b, max_batch=batch, **how) for b in blobs]
         else:
             got = model.decompress_yuv(blobs, **how)
@@ -214,9 +242,9 @@ def build_parser():
     ap.add_argument('-d', '--device', type=str, default='cuda:0')
     ap.add_argument('--tile', type=int, nargs=2, default=None, metavar=('TH', 'TW'), help='encode / encode-yuv: code every image (frame) in tiles of this size')
     ap.add_argument('--overlap', type=int, default=0, help='encode with --tile: pixels neighbouring tiles share')
-    ap.add_argument('--scale', type=float, default=None, help='encode: code every image at SCALE times its size (a scaled container per image)')
+    ap.add_argument('--scale', type=float, default=None, help='encode / encode-yuv: code every image (frame) at SCALE times its size (a scaled container each)')
     ap.add_argument('--filter', type=str, default='lanczos3', choices=['bilinear', 'bicubic', 'lanczos3'], help='encode with --scale: the resampling filter')
-    ap.add_argument('--preview', type=int, nargs=2, default=None, metavar=('H', 'W'), help='decode: write scaled files at this size')
+    ap.add_argument('--preview', type=int, nargs=2, default=None, metavar=('H', 'W'), help='decode / decode-yuv: write scaled files (frames) at this size')
     ap.add_argument('--box', type=int, nargs=4, default=None, metavar=('Y0', 'X0', 'H', 'W'), help='region: the window to decode')
     ap.add_argument('--synthetic', type=int, default=0, help='seeded weights; on encode / ratemap also write N seeded 120x180 / 128x192 PNGs to SRC')
     ap.add_argument('--size', type=int, nargs=2, default=None, metavar=('W', 'H'), help='encode-yuv: the frame size of the raw file')
@@ -246,7 +274,7 @@ def main(argv=None):
         if args.command == 'decode-yuv' and _is_sequence(args.src):      # every parameter comes from the container's header
             model = load_model(args.model, args.synthetic, torch.device(args.device))
             decode_yuv_container(model, args.src, args.dst, args.batch,
-                                 'semiplanar' if args.layout else args.format if args.format != 'i420' else None)
+                                 'semiplanar' if args.layout else args.format if args.format != 'i420' else None, args.preview)
             return
         from lvae.utils.yuv import SP_LAYOUTS, FrameFormat
         colour = dict(matrix=args.matrix, range=args.range, chroma=args.chroma, siting=args.siting)
@@ -277,10 +305,11 @@ def main(argv=None):
                 synthetic_yuv(args.src, args.synthetic, args.size, fmt, colour)
             model = load_model(args.model, args.synthetic, torch.device(args.device))
             (encode_yuv_container if args.container else encode_yuv)(model, args.src, args.dst, args.size, fmt, args.frames, args.lmb, args.batch, colour,
-                                                                     tuple(args.tile) if args.tile else None, args.overlap)
+                                                                     tuple(args.tile) if args.tile else None, args.overlap, args.scale,
+                                                                     args.filter)
         else:
             model = load_model(args.model, args.synthetic, torch.device(args.device))
-            decode_yuv(model, args.src, args.dst, fmt, args.batch, colour)
+            decode_yuv(model, args.src, args.dst, fmt, args.batch, colour, args.preview)
         return
     os.makedirs(args.dst, exist_ok=True)
     if args.synthetic and args.command in ('encode', 'ratemap'):
